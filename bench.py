@@ -9,16 +9,19 @@ ranks with no data-path collective (weak scaling); the per-step scalars are gath
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task description): metric/value = whole-job query-points/s, plus
+Prints ONE JSON line on rank 0 (contract in the task description): metric/value = whole-job query-points/s, ms_per_step, plus
   roofline      dominant kernel k_search1_flat<float> (both directions in one launch): SURVEY 8d algorithmic bytes of the
                 Chamfer row (24 B per query-point) / HIP-event launch time vs the 8 TB/s HBM peak; measured HBM traffic and the
                 issue-side counters (VALU busy, TA busy, SALU issue fraction, active lanes) come from profiles/hbm_traffic.json, which
                 profiles/postprocess.py derives from the round's rocprofv3 --pmc passes (stamped with the commit they were collected at:
-                roofline.counters_commit);
-  cpu_baseline  the reference's nanoflann path on this box's host cores (median of 3; search-only seconds beside it);
+                roofline.counters_commit).
+A plain run does only that: set-up, warm-up, the timed steps, the line. ``--full`` adds, behind the timed region:
+  device_ms_per_step, end_to_end_numpy   phase events on 3 extra steps; host arrays in, Python float out (median of 5);
+  cpu_baseline  the reference's nanoflann path on the host's cores (median of 3; search-only seconds beside it);
   parity        the GPU result of the timed pair against the reference's result on the SAME arrays (value + both index arrays);
-  configs       (N = 1, behind the timed region; --no-configs skips it) every BASELINE config c1 .. c5 run through the same code as
+  configs       (N = 1; --no-configs skips it) every BASELINE config c1 .. c5 run through the same code as
                 ``--config cN``: ms_per_step, value, roofline, parity against the reference and its cpu_baseline per entry.
+``--dump-outputs DIR`` writes what the last timed step returned (the Chamfer value, float32) to DIR/chamfer.npy (rank 0's pair).
 
 Other BASELINE configs (parity-test cases): ``--config c1|c2|c3|c4|c5`` prints the same kind of line for Chamfer 10k fp64,
 k_nearest_neighbors k=1 1M/1M, k=16 4M/4M, batched Hausdorff 256k pairs (32 pairs per GPU), Chamfer bunny-vs-1M f64.
@@ -44,11 +47,19 @@ def parse():
     ap.add_argument("--points", type=int, default=N_POINTS, help="points per cloud (default: the headline 1M)")
     ap.add_argument("--config", default="headline", choices=["headline", "c1", "c2", "c3", "c4", "c5", "gauss", "cluster", "outlier", "normals", "morton", "voxel", "sinkhorn"])
     ap.add_argument("--pairs", type=int, default=32, help="c4: pairs per GPU per step")
+    ap.add_argument("--full", action="store_true", help="headline line: also measure and check what lies behind the timed region (phase times, "
+                    "end-to-end numpy call, cpu_baseline, parity, BASELINE configs c1-c5); the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="headline line: write what the last timed step returned to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="headline line at N = 1: do not run BASELINE configs c1-c5 behind the timed region (the `configs` object)")
     ap.add_argument("--no-kernel-events", action="store_true", help="--config lines: skip the extra steps that time the dominant kernel with HIP events (profiler runs count the operator's calls)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != "headline":
+        ap.error("--dump-outputs is for the headline workload")
+    return args
 
 
 def cpu_model():
@@ -196,9 +207,12 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:     # the last timed step's return value: chamfer_distance gives a float32 scalar for f32 clouds
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "chamfer.npy"), np.float32(results[args.steps - 1]))
     # phase breakdown (diagnostic, OUTSIDE the timed region: 3 extra steps with phase events on)
     idx_ms = tot_ms = srch_ms = 0.0
-    if rank == 0:
+    if rank == 0 and args.full:
         pcu.set_timing(2)
         for _ in range(3):
             pcu.chamfer_distance(x, y)
@@ -209,7 +223,7 @@ def main():
     # protocol B of SURVEY 8d (diagnostic, OUTSIDE the timed region): end to end numpy -> numpy, i.e. incl. the H2D copies of both
     # clouds over PCIe and the Python shim; median of 5. Never the reported `value`.
     e2e_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ts = []
         for _ in range(6):
             t1 = time.perf_counter(); pcu.chamfer_distance(x_h, y_h); ts.append(time.perf_counter() - t1)
@@ -260,16 +274,17 @@ def main():
                        "points_per_cloud": n, "pairs_per_step": world, "parallelism": f"pairs x{world}",
                        **({"collectives": "gloo on host tensors: REHEARSAL, ranks share GPUs (PCU_BENCH_SHARE_GPU)"} if share else {})},
             "roofline": roof,
-            "device_ms_per_step": {"index_build": idx_ms, "search": srch_ms, "total": tot_ms,
-                                   "note": "3 extra steps outside the timed region, phase events on"},
             "chamfer": float(results[0]),
-            "end_to_end_numpy": {"ms_per_call": e2e_ms, "value": (2 * n / (e2e_ms * 1e-3)) if e2e_ms else None, "unit": "query-points/s",
-                                 "note": "SURVEY 8d protocol B: host arrays in, Python float out (24 MB H2D inside the call); median of 5, outside the timed region"},
         }
+        if args.full:
+            out["device_ms_per_step"] = {"index_build": idx_ms, "search": srch_ms, "total": tot_ms,
+                                         "note": "3 extra steps outside the timed region, phase events on"}
+            out["end_to_end_numpy"] = {"ms_per_call": e2e_ms, "value": (2 * n / (e2e_ms * 1e-3)) if e2e_ms else None, "unit": "query-points/s",
+                                       "note": "SURVEY 8d protocol B: host arrays in, Python float out (24 MB H2D inside the call); median of 5, outside the timed region"}
         ref = None
-        if not args.no_cpu_baseline and world == 1:      # reported baseline: rank 0, N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported baseline: rank 0, N = 1 only
             out["cpu_baseline"], ref = cpu_baseline(x_h, y_h)
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             # parity on the arrays that were timed (N > 1: rank 0's pair): the reference's value and BOTH index arrays
             import oracle
             if ref is None:
@@ -287,7 +302,7 @@ def main():
             assert idx_equal, "Chamfer correspondences differ from the reference"
         # Every BASELINE config in front of the driver (N = 1 only; OUTSIDE the timed region above): c1-c5 through the same code as
         # `--config cN`, a few steps each, parity against the reference and its CPU time inside each entry.
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             del x, y
             out["configs"] = {}
             for cfg, steps_c, warm_c in (("c1", 50, 5), ("c2", 30, 3), ("c3", 8, 2), ("c4", 8, 2), ("c5", 30, 3)):

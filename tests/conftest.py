@@ -29,6 +29,13 @@ def cloud(seed, n, dtype, scale=1.0, offset=0.0):
     return a
 
 
+def digest(a):
+    """SHA-256 of an array's dtype, shape and bytes: tests/golden/ref_pins.json stores the reference's answers this way."""
+    import hashlib
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).hexdigest()
+
+
 def mesh_samples(v, f, n, seed=5):
     """BASELINE config 5: n area-weighted uniform samples on the triangles (v, f) -- face ~ areas, barycentric
     (1 - sqrt(u), sqrt(u) (1 - w), sqrt(u) w) -- in float64, C-contiguous."""

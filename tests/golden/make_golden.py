@@ -131,6 +131,39 @@ def nonfinite_metric_cases(rng):
     print("wrote the non-finite metric fixtures")
 
 
+def ref_pin_cases():
+    """ref_pins.json: SHA-256 digests (tests/conftest.py:digest) of what oracle/_ref answers on the seeded inputs of
+    tests/test_oracle.py's two port-against-reference tests, so that those tests pin the restatements bit for bit wherever
+    oracle/_ref cannot be built. Digests, not arrays: the answers are 2.3 MB, most of it incompressible Morton codes."""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import cloud, digest
+    pins = {}
+    for dt, tag in ((np.float32, "f32"), (np.float64, "f64")):
+        q, r = cloud(1, 3000, dt), cloud(2, 2500, dt)
+        r = np.concatenate([r, r[:500]])
+        for leaf in (1, 10, 37):
+            for k in (1, 6):
+                d, c = oracle.knn(q, r, k, max_points_per_leaf=leaf, kind="ref")
+                pins[f"knn_{tag}_leaf{leaf}_k{k}_d"], pins[f"knn_{tag}_leaf{leaf}_k{k}_c"] = digest(d), digest(c)
+    assert oracle.have_ref_morton(), "needs oracle/_ref/libpcu_ref_morton.so"
+    rng = np.random.default_rng(0)
+    p = rng.integers(-(1 << 20), 1 << 20, (50000, 3)).astype(np.int32)
+    p[:4] = [[0, 0, 0], [-1, -1, -1], [(1 << 20) - 1] * 3, [-(1 << 20)] * 3]
+    c = oracle.morton_encode(p, "ref")
+    assert np.array_equal(oracle.morton_decode(c, "ref"), p)
+    c2 = oracle.morton_encode(rng.integers(-2000, 2000, (50000, 3)).astype(np.int32), "ref")
+    cs = np.sort(c)
+    pins.update(morton_c=digest(c), morton_c2=digest(c2), morton_add=digest(oracle.morton_addsub(c, c2, False, "ref")),
+                morton_sub=digest(oracle.morton_addsub(c, c2, True, "ref")),
+                **{f"morton_knn_{k}": digest(oracle.morton_knn_window(cs, c2[:2000], k, "ref")) for k in (1, 7, 16)},
+                morton_knn_short=digest(oracle.morton_knn_window(cs[:10], c2[:100], 15, "ref")))
+    with open(os.path.join(HERE, "ref_pins.json"), "w") as f:
+        json.dump(pins, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote ref_pins.json:", len(pins), "digests")
+
+
 def main():
     oracle.build()
     assert oracle.have_ref(), "needs /root/reference (oracle/_ref)"
@@ -138,8 +171,11 @@ def main():
         return nonfinite_cases()
     if "--only-near-ties" in sys.argv:
         return near_tie_cases()
+    if "--only-ref-pins" in sys.argv:
+        return ref_pin_cases()
     nonfinite_cases()
     near_tie_cases()
+    ref_pin_cases()
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from conftest import read_ply_vertices
     rng = np.random.default_rng(20250321)

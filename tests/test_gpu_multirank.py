@@ -102,7 +102,7 @@ def test_bench_multi_rank_launch_rehearsal(config):
     small = ["--points", "200000"] if config == "headline" else []
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--no-cpu-baseline", "--config", config] + small
+           "--full", "--no-cpu-baseline", "--config", config] + small
     r = subprocess.run(cmd, env=dict(os.environ, PCU_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True,
                        timeout=300, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])

@@ -1,15 +1,18 @@
 """CPU tests: the oracle (plain-C restatement) against the golden vectors generated from the reference's own
 nanoflann, against oracle/_ref when present, and against exact brute force."""
 import glob
+import json
 import os
 
 import numpy as np
 import pytest
 
 import oracle
-from conftest import cloud
+from conftest import cloud, digest
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+with open(os.path.join(GOLD, "ref_pins.json")) as _f:
+    REF_PINS = json.load(_f)
 CASES = sorted(p for p in glob.glob(os.path.join(GOLD, "*.npz")) if not p.endswith(("metrics.npz", "sinkhorn.npz", "config1.npz")))
 
 
@@ -24,14 +27,17 @@ def test_port_matches_golden(path):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("leaf", [1, 10, 37])
 def test_port_matches_ref_when_present(dtype, leaf):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built on this box")
+    """The port against the reference's own nanoflann: its answers pinned in tests/golden/ref_pins.json (make_golden.py
+    --only-ref-pins), and live as well where oracle/_ref is built."""
     q, r = cloud(1, 3000, dtype), cloud(2, 2500, dtype)
     r = np.concatenate([r, r[:500]])      # duplicates: tie order depends on the tree
+    tag = "f32" if dtype == np.float32 else "f64"
     for k in (1, 6):
-        d0, c0 = oracle.knn(q, r, k, max_points_per_leaf=leaf, kind="ref")
         d1, c1 = oracle.knn(q, r, k, max_points_per_leaf=leaf, kind="port")
-        assert np.array_equal(c0, c1) and np.array_equal(d0, d1)
+        assert digest(c1) == REF_PINS[f"knn_{tag}_leaf{leaf}_k{k}_c"] and digest(d1) == REF_PINS[f"knn_{tag}_leaf{leaf}_k{k}_d"]
+        if oracle.have_ref():
+            d0, c0 = oracle.knn(q, r, k, max_points_per_leaf=leaf, kind="ref")
+            assert np.array_equal(c0, c1) and np.array_equal(d0, d1)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -116,22 +122,30 @@ def test_oracle_normals_on_planes():
 
 def test_oracle_morton_port_pinned_to_reference():
     """The numpy restatement of MortonCode64 against the reference's own class (src/common/morton_code.cpp compiled in place
-    into oracle/_ref/libpcu_ref_morton.so) -- skipped where /root/reference never existed."""
-    if not oracle.have_ref_morton():
-        pytest.skip("oracle/_ref/libpcu_ref_morton.so not built (no /root/reference)")
+    into oracle/_ref/libpcu_ref_morton.so): its answers pinned in tests/golden/ref_pins.json (make_golden.py --only-ref-pins,
+    which also checks that the class decodes its codes back to the points), and live as well where that library is built."""
     rng = np.random.default_rng(0)
     p = rng.integers(-(1 << 20), 1 << 20, (50000, 3)).astype(np.int32)
     p[:4] = [[0, 0, 0], [-1, -1, -1], [(1 << 20) - 1] * 3, [-(1 << 20)] * 3]
-    c = oracle.morton_encode(p, "ref")
-    assert np.array_equal(c, oracle.morton_encode(p, "port"))
-    assert np.array_equal(oracle.morton_decode(c, "ref"), p) and np.array_equal(oracle.morton_decode(c, "port"), p)
-    c2 = oracle.morton_encode(rng.integers(-2000, 2000, (50000, 3)).astype(np.int32), "ref")
-    for sub in (False, True):
-        assert np.array_equal(oracle.morton_addsub(c, c2, sub, "ref"), oracle.morton_addsub(c, c2, sub, "port"))
+    c = oracle.morton_encode(p, "port")
+    assert digest(c) == REF_PINS["morton_c"]
+    assert np.array_equal(oracle.morton_decode(c, "port"), p)
+    c2 = oracle.morton_encode(rng.integers(-2000, 2000, (50000, 3)).astype(np.int32), "port")
+    assert digest(c2) == REF_PINS["morton_c2"]
+    for sub, name in ((False, "morton_add"), (True, "morton_sub")):
+        assert digest(oracle.morton_addsub(c, c2, sub, "port")) == REF_PINS[name]
     cs = np.sort(c)
     for k in (1, 7, 16):
-        assert np.array_equal(oracle.morton_knn_window(cs, c2[:2000], k, "ref"), oracle.morton_knn_window(cs, c2[:2000], k, "port"))
-    assert np.array_equal(oracle.morton_knn_window(cs[:10], c2[:100], 15, "ref"), oracle.morton_knn_window(cs[:10], c2[:100], 15, "port"))
+        assert digest(oracle.morton_knn_window(cs, c2[:2000], k, "port")) == REF_PINS[f"morton_knn_{k}"]
+    assert digest(oracle.morton_knn_window(cs[:10], c2[:100], 15, "port")) == REF_PINS["morton_knn_short"]
+    if oracle.have_ref_morton():
+        assert np.array_equal(c, oracle.morton_encode(p, "ref"))
+        assert np.array_equal(oracle.morton_decode(c, "ref"), p)
+        for sub in (False, True):
+            assert np.array_equal(oracle.morton_addsub(c, c2, sub, "ref"), oracle.morton_addsub(c, c2, sub, "port"))
+        for k in (1, 7, 16):
+            assert np.array_equal(oracle.morton_knn_window(cs, c2[:2000], k, "ref"), oracle.morton_knn_window(cs, c2[:2000], k, "port"))
+        assert np.array_equal(oracle.morton_knn_window(cs[:10], c2[:100], 15, "ref"), oracle.morton_knn_window(cs[:10], c2[:100], 15, "port"))
 
 
 def test_oracle_voxel_and_dedup_restatements():
