@@ -36,16 +36,7 @@ constexpr int kXPartStride = 8;             // per scatter block: [0..2] finite 
 constexpr int kStagedMaxBuckets = 2048;     // the scatter's bucket tables (12 bytes each) sit beside its 128 KB stage
 constexpr int kFillWords = 2 * kStagedMaxBuckets + 8;      // one set of fill words: [side][bucket], then [2 * kStagedMaxBuckets + side] = slot-overflow flag
 
-// A wave-uniform value pinned into scalar registers (the compiler cannot prove uniformity of values read back from LDS or from global memory
-// that the kernel also writes, and then keeps them in vector registers or re-reads them at every use).
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-__device__ __forceinline__ double uniform(double v) {
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-// What cell_linear needs of a grid, in scalar registers.
+// What cell_linear needs of a grid, in scalar registers (uniform(): pcu_types.h).
 template <typename T>
 struct CellMap {
     T org[3], inv_h; int G[3];

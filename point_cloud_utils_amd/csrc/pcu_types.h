@@ -54,6 +54,16 @@ __device__ __forceinline__ bool cancel_seen(const unsigned* word, unsigned gen) 
     return word != nullptr && (int)(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - gen) > 0;
 }
 
+// A wave-uniform value pinned into scalar registers (the compiler cannot prove uniformity of values read back from LDS or from global memory
+// that the kernel also writes, and then keeps them in vector registers or re-reads them at every use).
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ unsigned long long uniform(unsigned long long v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ double uniform(double v) { return __longlong_as_double((long long)uniform((unsigned long long)__double_as_longlong(v))); }
+
 template <typename T> struct Limits;
 template <> struct Limits<float>  { static constexpr float  max_v = FLT_MAX; static constexpr float  eps = FLT_EPSILON; };
 template <> struct Limits<double> { static constexpr double max_v = DBL_MAX; static constexpr double eps = DBL_EPSILON; };
@@ -94,6 +104,23 @@ struct GridParams {
     int nonfinite;            // kNf* flags (grid.h): non-finite coordinates met by the bbox pass
     unsigned long long sumsq; // sum over cells of count^2 (balance metric: sumsq / n = mean number of cell mates)
 };
+
+// A kernel's private copy of a grid's parameters, every field pinned into scalar registers. Read once at the top of a kernel, the
+// fields stay in SGPRs for its whole run; read through the pointer at every use, a late use after a fence or an atomic becomes a
+// vector reload, and the compiler then merges the early reads with it into vector loads whose values it keeps live (or spills).
+// (Unused fields cost nothing: a readfirstlane whose result is unused is removed with its load.)
+template <typename T>
+__device__ __forceinline__ GridParams<T> uniform_params(const GridParams<T>& g) {
+    GridParams<T> u;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        u.gmin[j] = uniform(g.gmin[j]); u.gmax[j] = uniform(g.gmax[j]); u.slack[j] = uniform(g.slack[j]);
+        u.G[j] = uniform(g.G[j]); u.org[j] = uniform(g.org[j]);
+    }
+    u.h = uniform(g.h); u.inv_h = uniform(g.inv_h); u.ncells = uniform(g.ncells);
+    u.closed = uniform(g.closed); u.has_large = uniform(g.has_large); u.nonfinite = uniform(g.nonfinite); u.sumsq = uniform(g.sumsq);
+    return u;
+}
 
 // Cell coordinate of value v along one axis. Separate subtract and multiply (the TU is built with
 // -ffp-contract=off); NaN maps to cell 0; values on/after the last face are clamped into the last cell.

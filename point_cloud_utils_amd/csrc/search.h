@@ -659,19 +659,22 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
     const int tid = threadIdx.x;
     const int nq = a.qcount_dev ? *a.qcount_dev : nq_arg;
     if (vb * kBlock >= nq) return;                     // (block-uniform)
-    const GridParams<T>& g = *a.gp;
+    const GridParams<T> g = uniform_params(*a.gp);
     if (const int hl = index_not_ready(a, g)) { if (vb == 0 && tid == 0) a.skew_flag[kLargeFlag] = hl; return; }
-    if (a.skew_limit > 0.f && ((float)g.sumsq > a.skew_limit || (float)g.sumsq < a.skew_lo)) { if (vb == 0 && tid == 0) *a.skew_flag = (float)g.sumsq > a.skew_far ? 2 : 1; return; }
+    const float ssq = uniform((float)g.sumsq);
+    if (a.skew_limit > 0.f && (ssq > a.skew_limit || ssq < a.skew_lo)) { if (vb == 0 && tid == 0) *a.skew_flag = ssq > a.skew_far ? 2 : 1; return; }
     const int t = vb * kBlock + tid;
     if (t >= nq) return;
     constexpr bool valid = true;
-    const int qpos = a.qlist ? a.qlist[t] : t;
-    Pt4<T> q;                                         // (from the coordinate stream; the row id only where an epilogue uses it)
+    // (the query's position and row id are fetched again by the epilogue instead of being held across the scan: kept live, they were
+    // spilled to scratch with the grid constants -- 68 bytes per lane written and read back through the texture path)
+    auto query_pos = [&]() { return a.qlist ? a.qlist[t] : t; };
+    Pt4<T> q;                                         // (from the coordinate stream; an epilogue that needs the row id reads it itself)
     {
         struct __attribute__((packed, aligned(4))) Q3 { T v[3]; };
-        const Q3 c = *reinterpret_cast<const Q3*>(a.q_xyz + 3 * (size_t)qpos);
+        const Q3 c = *reinterpret_cast<const Q3*>(a.q_xyz + 3 * (size_t)query_pos());
         q.x = c.v[0]; q.y = c.v[1]; q.z = c.v[2];
-        q.idx = FUSE == FUSE_SUM ? 0 : a.q_idx[qpos];
+        q.idx = 0;
     }
     // (FUSE_MAXVAL, round 6: Hausdorff's lane pass on the fused sum's value-only program -- no winner, no tie flags, adoption -- whose partial names
     // the arg-max QUERY; k_fuse_tail resolves that one query's neighbour, reduce.h: FuseTail::maxval)
@@ -1014,11 +1017,12 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
             if (h2 == 1 && ro2 == ro) tie = false;        // the same record met twice (groups run past their run's end)
         }
     }
+    const int qpos = query_pos();
     if (FUSE == FUSE_NONE) {                              // result rows (finish_lane for k = 1, with the bound computed above)
         if (defer) { wave_append(valid, qpos, a.ties, a.n_ties); return; }       // nothing was scanned: the wave-per-query pass at the same radius takes over
         const bool certified = valid && best < lb;
         if (certified) {
-            const size_t o = (size_t)(a.row_out ? (int)q.idx : qpos) * (size_t)a.kreq;
+            const size_t o = (size_t)(a.row_out ? a.q_idx[qpos] : qpos) * (size_t)a.kreq;
             const bool found = bi[0] != 0x7fffffff;
             a.out_i[o] = found ? (long long)bi[0] : -1ll;
             a.out_d[o] = found ? (a.squared ? best : sqrt(best)) : (T)-1;
@@ -1038,8 +1042,9 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
     if (us >= 0 && a.ubound) a.ubound[us] = best;
     f_ok = certified;
     f_v = a.squared ? best : sqrt(best);
-    f_key = FUSE == FUSE_MAXVAL ? (((long long)q.idx << 32) | kKeyUnresolved | (long long)qpos)
-                                : (((long long)q.idx << 32) | (long long)((unsigned)bi[0] | (tie ? 0x80000000u : 0u)));
+    const long long qrow = FUSE == FUSE_SUM ? 0ll : (long long)a.q_idx[qpos];
+    f_key = FUSE == FUSE_MAXVAL ? ((qrow << 32) | kKeyUnresolved | (long long)qpos)
+                                : ((qrow << 32) | (long long)((unsigned)bi[0] | (tie ? 0x80000000u : 0u)));
 }
 // -------------------------------------------------------------------------------------------------------
 // Main pass for k > 1 on an OPEN index (round 5): k_search's scan on the k = 1 kernel's plan. k_search walks the nine rows one after the
