@@ -11,8 +11,11 @@
 //   earth_movers_distance :133-156  (P * M).sum()
 // Arithmetic is done in the input dtype with the reference's operation order per element ((-M + v) / eps, exp(x - max), ...);
 // what differs is the ORDER OF THE SUMS (numpy: pairwise blocks; here: fixed trees over a block, and a streaming
-// log-sum-exp for the column pass so that the matrix is read once per pass). Tolerance: 1e-5 relative for float32, 1e-11 for
-// float64 on u, v, P (tests/test_gpu_sinkhorn.py). All reductions run in a fixed order: results are reproducible run to run.
+// log-sum-exp for the column pass so that the matrix is read once per pass). pairwise_distances sums in numpy's order as well:
+// its result is numpy's bit for bit for ord None / 2, 1, 0, +-inf, and within a few ulps per entry for any other ord (the powers
+// are taken in double; tests/test_gpu_dense.py). The Sinkhorn plan is held to the reference per entry within c u_T max|M| / eps
+// (u_T: unit roundoff of the dtype), its column marginal likewise (tests/test_gpu_dense.py). All reductions run in a fixed
+// order: results are reproducible run to run.
 #pragma once
 #include "pcu_types.h"
 #include "grid.h"
@@ -21,9 +24,46 @@
 namespace pcu {
 
 // ---- pairwise distances ----------------------------------------------------------------------------------------------------
+// numpy's norm sums with add.reduce, i.e. numpy's pairwise summation over the contiguous last axis: left to right below 8 terms;
+// 8 strided accumulators combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the rest left to right, up to 128;
+// above 128 the two halves (split at n / 2 rounded down to a multiple of 8) summed recursively. Restated in oracle/__init__.py
+// (pairwise_sum_last), pinned to numpy by tests/test_oracle.py. pw_leaf sums terms lo .. lo + n - 1 for n <= 128.
+template <typename T, typename F>
+__device__ __forceinline__ T pw_leaf(const F& term, int lo, int n) {
+    if (n < 8) { T r = 0; for (int c = 0; c < n; ++c) r += term(lo + c); return r; }
+    T r[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = term(lo + k);
+    int c = 8;
+    for (; c < n - n % 8; c += 8) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] += term(lo + c + k);
+    }
+    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; c < n; ++c) res += term(lo + c);
+    return res;
+}
+// n > 128: the recursion over halves as an explicit stack (depth <= 25 for n < 2^31): descend left to a leaf, then fold the
+// finished right halves into their pending left sums
+template <typename T, typename F>
+__device__ T pw_sum_wide(const F& term, int n) {
+    T left[32]; int mid[32], end[32]; bool in_right[32];
+    int sp = 0, lo = 0, hi = n;
+    for (;;) {
+        while (hi - lo > 128) { int n2 = (hi - lo) / 2; n2 -= n2 % 8; mid[sp] = lo + n2; end[sp] = hi; in_right[sp] = false; ++sp; hi = lo + n2; }
+        T r = pw_leaf<T>(term, lo, hi - lo);
+        while (sp > 0 && in_right[sp - 1]) { r = left[sp - 1] + r; --sp; }
+        if (sp == 0) return r;
+        left[sp - 1] = r; in_right[sp - 1] = true; lo = mid[sp - 1]; hi = end[sp - 1];
+    }
+}
 // one thread per output element; a block covers 64 consecutive j of 4 consecutive i (coalesced stores, the a rows and b rows it
-// reads are shared through L1)
-template <typename T>
+// reads are shared through L1). Per element, numpy's norm (axis=-1) operation by operation: x = a - b; ord 2: sqrt(sum(x * x));
+// 1: sum(|x|); 0: sum(x != 0); +-inf: max / min of |x|, a NaN wins as in numpy's maximum / minimum; other ord: sum(|x| ** ord)
+// ** (1 / ord). The sums run in numpy's order (pw_leaf; WIDE = d > 128: pw_sum_wide, kept out of the common instantiation so
+// that its stack stays out of it), so every ord but the general one gives numpy's bits. The general ord raises to ord and 1 / ord
+// in double and rounds to T, where numpy raises in T (pow / powf, with fast paths for -1, 0.5, 2): a few ulps, not bits.
+template <typename T, bool WIDE>
 __global__ __launch_bounds__(256) void k_pairwise(const T* __restrict__ a, const T* __restrict__ b, int m, int n, int d, int pcode, double p, T* __restrict__ out, int col_blocks) {
     // (rows x column blocks are folded into gridDim.x -- 2^31-1 blocks -- because gridDim.y / .z end at 65535: 100k points against 100
     // centroids is a legitimate call)
@@ -31,19 +71,26 @@ __global__ __launch_bounds__(256) void k_pairwise(const T* __restrict__ a, const
     const int j = bx * 64 + (threadIdx.x & 63), i = by * 4 + (threadIdx.x >> 6), bt = blockIdx.y;
     if (i >= m || j >= n) return;
     const T* ai = a + ((size_t)bt * m + i) * d; const T* bj = b + ((size_t)bt * n + j) * d;
-    T acc = pcode == P_NINF ? (T)INFINITY : (T)0;
-    for (int c = 0; c < d; ++c) {
-        const T x = ai[c] - bj[c];
-        const T ax = x < 0 ? -x : x;
-        if (pcode == P_TWO) acc += x * x;                       // sqrt(add.reduce(x * x)) -- numpy's 2-norm of a real vector
-        else if (pcode == P_ONE) acc += ax;
-        else if (pcode == P_INF) acc = ax > acc ? ax : acc;
-        else if (pcode == P_NINF) acc = ax < acc ? ax : acc;
-        else if (pcode == P_ZERO) acc += (T)(x != 0);
-        else acc += (T)pow((double)ax, p);
+    T acc;
+    if (pcode == P_INF || pcode == P_NINF) {
+        acc = fabs(ai[0] - bj[0]);
+        for (int c = 1; c < d; ++c) {
+            const T ax = fabs(ai[c] - bj[c]);
+            const bool keep = pcode == P_INF ? acc >= ax : acc <= ax;
+            acc = keep || acc != acc ? acc : ax;                 // numpy's maximum / minimum: (r >= x || isnan(r)) ? r : x
+        }
+    } else {
+        const auto term = [&](int c) -> T {
+            const T x = ai[c] - bj[c];
+            if (pcode == P_TWO) return x * x;                   // sqrt(add.reduce(x * x)) -- numpy's 2-norm of a real vector
+            if (pcode == P_ONE) return fabs(x);
+            if (pcode == P_ZERO) return (T)(x != 0);
+            return (T)pow((double)fabs(x), p);
+        };
+        acc = WIDE ? pw_sum_wide<T>(term, d) : pw_leaf<T>(term, 0, d);
+        if (pcode == P_TWO) acc = sqrt(acc);
+        else if (pcode == P_GEN) acc = (T)pow((double)acc, 1.0 / p);
     }
-    if (pcode == P_TWO) acc = sqrt(acc);
-    else if (pcode == P_GEN) acc = (T)pow((double)acc, 1.0 / p);
     out[((size_t)bt * m + i) * n + j] = acc;
 }
 
@@ -125,7 +172,10 @@ __global__ __launch_bounds__(1024) void k_sink_cols(const SinkArgs<T> s, T* __re
         T M2 = s_mx[0][c];
         for (int k = 1; k < 32; ++k) M2 = s_mx[k][c] > M2 ? s_mx[k][c] : M2;
         T tot = 0;
-        for (int k = 0; k < 32; ++k) tot += s_mx[k][c] == -(T)INFINITY ? (T)0 : s_sum[k][c] * exp(s_mx[k][c] - M2);
+        // A partial counts unless its sum is 0 (it saw x = -inf only). A NaN x -- from a NaN u, e.g. an all-+inf row -- leaves a NaN
+        // sum while the running maximum is still -inf; it must reach v, as the reference's max() passes a NaN on. (Here and in the
+        // merges below.)
+        for (int k = 0; k < 32; ++k) tot += s_sum[k][c] == 0 ? (T)0 : s_sum[k][c] * exp(s_mx[k][c] - M2);
         const size_t o = ((size_t)slab * s.nb + bt) * s.n + j;
         part_mx[o] = M2; part_sum[o] = tot;
     }
@@ -205,7 +255,7 @@ __global__ __launch_bounds__(256) void k_sink_cols_finish(const SinkArgs<T> s, c
     T M2 = part_mx[o];
     for (int k = 1; k < n_slabs; ++k) { const T v = part_mx[o + k * stride]; M2 = v > M2 ? v : M2; }
     T tot = 0;
-    for (int k = 0; k < n_slabs; ++k) { const T v = part_mx[o + k * stride]; tot += v == -(T)INFINITY ? (T)0 : part_sum[o + k * stride] * exp(v - M2); }
+    for (int k = 0; k < n_slabs; ++k) { const T v = part_mx[o + k * stride], ps = part_sum[o + k * stride]; tot += ps == 0 ? (T)0 : ps * exp(v - M2); }
     const T lse = log(tot) + M2;
     const T vn = s.eps * (log(s.b[o]) - lse);
     const T d = s.v[o] - vn;
@@ -223,7 +273,7 @@ __global__ __launch_bounds__(1024) void k_sink_cols_merge(const SinkArgs<T> s, c
     if (j < s.n)
         for (int k = r; k < n_slabs; k += 32) {
             const T pm = part_mx[o + k * stride], ps = part_sum[o + k * stride];
-            if (pm == -(T)INFINITY) continue;
+            if (ps == 0) continue;
             if (pm > mx) { acc = acc * exp(mx - pm) + ps; mx = pm; } else acc += ps * exp(pm - mx);
         }
     s_mx[r][c] = mx; s_sum[r][c] = acc;
@@ -232,7 +282,7 @@ __global__ __launch_bounds__(1024) void k_sink_cols_merge(const SinkArgs<T> s, c
         T M2 = s_mx[0][c];
         for (int k = 1; k < 32; ++k) M2 = s_mx[k][c] > M2 ? s_mx[k][c] : M2;
         T tot = 0;
-        for (int k = 0; k < 32; ++k) tot += s_mx[k][c] == -(T)INFINITY ? (T)0 : s_sum[k][c] * exp(s_mx[k][c] - M2);
+        for (int k = 0; k < 32; ++k) tot += s_sum[k][c] == 0 ? (T)0 : s_sum[k][c] * exp(s_mx[k][c] - M2);
         const T lse = log(tot) + M2;
         const T vn = s.eps * (log(s.b[o]) - lse);
         const T d = s.v[o] - vn;
@@ -263,14 +313,29 @@ __global__ __launch_bounds__(256) void k_sink_plan(const SinkArgs<T> s, T* __res
     const size_t o = ((size_t)bt * s.m + i) * s.n + j;
     P[o] = exp(((-s.M[o] + s.u[(size_t)bt * s.m + i]) + s.v[(size_t)bt * s.n + j]) / s.eps);
 }
-// sum of x * y in double (earth_movers_distance's (P * M).sum(), :156): per-block partials, folded by the host
+// sum of x * y (earth_movers_distance's (P * M).sum(), :156): each product rounded to T, summed in double-double (error-free
+// TwoSum, valid under -ffp-contract=off), so that the result is the exact sum of the products to within about one ulp of double
+// (a plain double sum over ~10^6 products drifts by several ulps); per-block (hi, lo) partials, folded by the host the same way
+__host__ __device__ __forceinline__ void dd_add(double& hi, double& lo, double h2, double l2) {
+    const double s = hi + h2;
+    if (!(s - s == 0)) { hi = s; lo = 0; return; }     // inf / NaN: no error term (a later finite term leaves inf / NaN as it is)
+    const double bb = s - hi, e = ((hi - (s - bb)) + (h2 - bb)) + (lo + l2);
+    hi = s + e; lo = e - (hi - s);
+}
 template <typename T>
 __global__ __launch_bounds__(256) void k_dot_partial(const T* __restrict__ x, const T* __restrict__ y, size_t count, double* __restrict__ partial) {
-    __shared__ double sm[4];
-    double acc = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) acc += (double)(T)(x[i] * y[i]);
-    acc = blk_sum(acc, sm);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+    __shared__ double sm[2][4];
+    double hi = 0, lo = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) dd_add(hi, lo, (double)(T)(x[i] * y[i]), 0.0);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const double h2 = __shfl_xor(hi, o, 64), l2 = __shfl_xor(lo, o, 64); dd_add(hi, lo, h2, l2); }
+    if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = hi; sm[1][threadIdx.x >> 6] = lo; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        hi = sm[0][0]; lo = sm[1][0];
+        for (int w = 1; w < 4; ++w) dd_add(hi, lo, sm[0][w], sm[1][w]);
+        partial[2 * blockIdx.x] = hi; partial[2 * blockIdx.x + 1] = lo;
+    }
 }
 
 }  // namespace pcu

@@ -277,7 +277,8 @@ static int pairwise_impl(pcu_hip_ctx* c, const T* a, const T* b, int64_t nb, int
         const int pc = std::isnan(p_norm) ? P_TWO : pcode_of(p_norm);                 // ord=None: the 2-norm
         const long long pw_cols = (n + 63) / 64, pw_blocks = pw_cols * ((m + 3) / 4);
         if (pw_blocks > 0x7fffffffll || nb > 65535) { rc = fail(PCU_HIP_ERR_INVALID, "pairwise_distances: problem too large (more than 2^31-1 tiles of 4 x 64 entries per batch, or more than 65535 batches)"); break; }
-        hipLaunchKernelGGL((k_pairwise<T>), dim3((unsigned)pw_blocks, (unsigned)nb), dim3(256), 0, s, da, db, (int)m, (int)n, (int)d, pc, p_norm, dout, (int)pw_cols);
+        if (d > 128) hipLaunchKernelGGL((k_pairwise<T, true>), dim3((unsigned)pw_blocks, (unsigned)nb), dim3(256), 0, s, da, db, (int)m, (int)n, (int)d, pc, p_norm, dout, (int)pw_cols);
+        else hipLaunchKernelGGL((k_pairwise<T, false>), dim3((unsigned)pw_blocks, (unsigned)nb), dim3(256), 0, s, da, db, (int)m, (int)n, (int)d, pc, p_norm, dout, (int)pw_cols);
         HIP_TRY(hipGetLastError());
         if (!on_dev) HIP_TRY(hipMemcpyAsync(out, dout, no * sizeof(T), hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
@@ -371,14 +372,14 @@ static int dot_impl(pcu_hip_ctx* c, const T* x, const T* y, int64_t count, doubl
     int rc = 0;
     do {
         const T *dx, *dy; double* part = nullptr;
-        if ((rc = stage_any(ar, x, (size_t)count, on_dev, s, &dx)) || (rc = stage_any(ar, y, (size_t)count, on_dev, s, &dy)) || (rc = aalloc(ar, &part, kParts))) break;
+        if ((rc = stage_any(ar, x, (size_t)count, on_dev, s, &dx)) || (rc = stage_any(ar, y, (size_t)count, on_dev, s, &dy)) || (rc = aalloc(ar, &part, 2 * kParts))) break;
         hipLaunchKernelGGL((k_dot_partial<T>), dim3(kParts), dim3(256), 0, s, dx, dy, (size_t)count, part);
         HIP_TRY(hipGetLastError());
-        double h[kParts];
+        double h[2 * kParts];
         HIP_TRY(hipMemcpyAsync(h, part, sizeof h, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
-        double r = 0; for (int i = 0; i < kParts; ++i) r += h[i];
-        *out = r;
+        double hi = 0, lo = 0; for (int i = 0; i < kParts; ++i) dd_add(hi, lo, h[2 * i], h[2 * i + 1]);
+        *out = hi;
     } while (0);
     ctx_end(c);
     return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;

@@ -200,3 +200,27 @@ def test_config1_cpu():
     if oracle.have_ref():
         ch1, cxy1, cyx1 = oracle.chamfer_distance(x, y, return_index=True, kind="ref")
         assert float(ch1) == float(ch) and np.array_equal(cxy1, cxy) and np.array_equal(cyx1, cyx)
+
+
+def test_oracle_norm_order_pinned_to_numpy():
+    """oracle.vector_norm_numpy_order -- numpy's pairwise summation restated, the order k_pairwise follows -- equals
+    np.linalg.norm(..., axis=-1) bit for bit for d = 1 .. 300 at every ord the kernel reproduces exactly (and at the general ords,
+    whose powers it also takes as numpy does). If a numpy release changes its summation order, this says so before a GPU test does."""
+    rng = np.random.default_rng(17)
+    for dt in (np.float32, np.float64):
+        for d in range(1, 301):
+            x = (rng.standard_normal((3, 4, d)) * 10.0 ** rng.uniform(-3, 3, (3, 4, d))).astype(dt)
+            x[0, 0, : d // 2] = 0                       # zero components: ord 0 counts, negative ords meet 0 ** ord = inf
+            for o in (None, 2, 1, np.inf, -np.inf, 0, 3, 0.5, -1, 2.5):
+                with np.errstate(divide="ignore"):
+                    ref = np.linalg.norm(x, ord=o, axis=-1)
+                    got = oracle.vector_norm_numpy_order(x, o)
+                assert got.dtype == ref.dtype and got.tobytes() == ref.tobytes(), (dt, d, o)
+    # the order matters: a left-to-right sum of squares is not numpy's 2-norm once d >= 8
+    x = rng.standard_normal((500, 17)).astype(np.float32)
+    seq = np.zeros(500, np.float32)
+    for c in range(17):
+        seq = seq + x[:, c] * x[:, c]
+    assert not np.array_equal(np.sqrt(seq), np.linalg.norm(x, axis=-1))
+    a, b = rng.random((2, 5, 9)), rng.random((2, 6, 9))
+    assert oracle.pairwise_distances_numpy_order(a, b).tobytes() == oracle.pairwise_distances(a, b).tobytes()
