@@ -29,7 +29,7 @@ from ._lib import Stats, set_cell_occupancy, device_count  # noqa: F401
 __all__ = ["k_nearest_neighbors", "one_sided_hausdorff_distance", "hausdorff_distance", "chamfer_distance",
            "estimate_point_cloud_normals_knn", "estimate_point_cloud_normals_ball",
            "morton_encode", "morton_decode", "morton_add", "morton_subtract", "morton_knn",
-           "downsample_point_cloud_on_voxel_grid", "deduplicate_point_cloud",
+           "downsample_point_cloud_on_voxel_grid", "deduplicate_point_cloud", "downsample_point_cloud_poisson_disk",
            "pairwise_distances", "sinkhorn", "earth_movers_distance",
            "last_stats", "set_timing", "set_cell_occupancy", "device_count", "DatasetIndex", "cancel"]
 
@@ -436,3 +436,4 @@ from ._normals import estimate_point_cloud_normals_knn, estimate_point_cloud_nor
 from ._voxel import (morton_encode, morton_decode, morton_add, morton_subtract, morton_knn,  # noqa: E402,F401
                      downsample_point_cloud_on_voxel_grid, deduplicate_point_cloud)
 from ._sinkhorn import pairwise_distances, sinkhorn, earth_movers_distance  # noqa: E402,F401
+from ._poisson import downsample_point_cloud_poisson_disk  # noqa: E402,F401

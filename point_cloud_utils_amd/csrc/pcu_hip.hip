@@ -36,6 +36,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "morton.h"
 #include "voxel.h"
 #include "sinkhorn.h"
+#include "poisson.h"
 
 using namespace pcu;
 
@@ -2763,6 +2764,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 }
 
 #include "voxel_host.h"
+#include "poisson_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2930,6 +2932,13 @@ int pcu_hip_dedup_f32(pcu_hip_ctx* c, const float* pts, int64_t n, double epsilo
     CallGuard dg(c); return abi_rc(dedup_impl<float>(c, pts, n, epsilon, out_pts, out_svi, out_svj, out_count, flags, stream)); }
 int pcu_hip_dedup_f64(pcu_hip_ctx* c, const double* pts, int64_t n, double epsilon, double* out_pts, int32_t* out_svi, int32_t* out_svj, int64_t* out_count, unsigned flags, void* stream) {
     CallGuard dg(c); return abi_rc(dedup_impl<double>(c, pts, n, epsilon, out_pts, out_svi, out_svj, out_count, flags, stream)); }
+
+int pcu_hip_poisson_disk_f32(pcu_hip_ctx* c, const float* pts, int64_t n, double radius, int64_t target, uint32_t seed, double tol, int32_t* out_idx,
+                             int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
+    CallGuard dg(c); return abi_rc(poisson_disk_impl<float>(c, pts, n, radius, target, seed, tol, out_idx, out_count, flags, stream, st)); }
+int pcu_hip_poisson_disk_f64(pcu_hip_ctx* c, const double* pts, int64_t n, double radius, int64_t target, uint32_t seed, double tol, int32_t* out_idx,
+                             int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
+    CallGuard dg(c); return abi_rc(poisson_disk_impl<double>(c, pts, n, radius, target, seed, tol, out_idx, out_count, flags, stream, st)); }
 
 #define PCU_SINK(SUF, T)                                                                                                                             \
 int pcu_hip_pairwise_##SUF(pcu_hip_ctx* c, const T* a, const T* b, int64_t nb, int64_t m, int64_t n, int64_t d, double p_norm, T* out, unsigned flags, void* stream) {  \
