@@ -489,11 +489,10 @@ __global__ __launch_bounds__(kBlock) void k_scan_apply(unsigned* counts, const G
     }
 }
 
-// `rank` is turned into the row's slot in place (rank[i] := cell_start[cell_of[i]] + rank[i]): the row -> slot map
-// k_unpermute needs.
+// Row i goes to slot cell_start[cell_of[i]] + rank[i].
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_scatter(const T* __restrict__ pts, int n, const unsigned* __restrict__ cell_of,
-                                                    unsigned* rank, const unsigned* __restrict__ cell_start,
+                                                    const unsigned* rank, const unsigned* __restrict__ cell_start,
                                                     Pt4<T>* __restrict__ sorted) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
@@ -503,7 +502,6 @@ __global__ __launch_bounds__(kBlock) void k_scatter(const T* __restrict__ pts, i
     const unsigned pos = cell_start[cell_of[i]] + rank[i];
     sorted[pos] = p;
     put_xyz(sorted, n, pos, p);
-    rank[i] = pos;
 }
 
 // ---- bucketed build (the default for the whole-cloud indexes) -------------------------------------------------------
@@ -627,7 +625,7 @@ template <typename T>
 struct BucketSide {        // one cloud's view of the bucket passes
     const T* pts; int n; GridParams<T>* gp; int shift; int nb_stride;
     unsigned *bucket_total, *block_base, *bucket_start; Pt4<T>* tmp; unsigned *cell_start, *rank_tmp;
-    Pt4<T>* sorted; unsigned *pos_of, *large_list, *n_large;
+    Pt4<T>* sorted; unsigned *large_list, *n_large;
     unsigned cap;          // > 0: one-pass build -- bucket b owns the slot tmp[b * cap, (b + 1) * cap), bucket_total[b] = its fill (k_bucket_onepass)
 };
 template <typename T>
@@ -780,7 +778,7 @@ __global__ __launch_bounds__(kBkThreads) void k_bucket_scatter(const BucketSide<
 template <typename T>
 __device__ __forceinline__ void bucket_sort_body(const int bid, GridParams<T>* gp, int shift, const unsigned* __restrict__ bucket_start,
                                                               const Pt4<T>* __restrict__ tmp, unsigned* cell_start, Pt4<T>* __restrict__ sorted,
-                                                              unsigned* __restrict__ pos_of, unsigned* __restrict__ large_list, unsigned* n_large,
+                                                              unsigned* __restrict__ large_list, unsigned* n_large,
                                                               long long* prof, const int cnt_cap, const unsigned cap, const unsigned* __restrict__ fill, const int n_pts) {
     // diagnostics (PCU_HIP_PROF_BUILD): per-stage time of every block's thread 0, summed; 100 MHz ticks
     long long t_prev = prof ? wall_clock64() : 0;
@@ -907,7 +905,6 @@ __device__ __forceinline__ void bucket_sort_body(const int bid, GridParams<T>* g
             const Pt4<T> r = s_stage[i];
             sorted[s + i] = r;
             put_xyz(sorted, n_pts, s + i, r);
-            if (pos_of) pos_of[r.idx] = s + i;
         }
     } else {
 #pragma unroll
@@ -923,7 +920,6 @@ __device__ __forceinline__ void bucket_sort_body(const int bid, GridParams<T>* g
                     const unsigned pos = s + s_cnt[rr[it0 + u] >> 16] + (rr[it0 + u] & 0xffffu);
                     sorted[pos] = rec[u];
                     put_xyz(sorted, n_pts, pos, rec[u]);
-                    if (pos_of) pos_of[rec[u].idx] = pos;
                 }
             }
         }
@@ -936,7 +932,7 @@ template <typename T>
 __global__ __launch_bounds__(kSortThreads) void k_bucket_sort(const BucketSide<T> a0, const BucketSide<T> a1, int nb0, long long* prof, int cnt_cap) {
     const bool second = (int)blockIdx.x >= nb0;
     const BucketSide<T>& a = second ? a1 : a0;
-    bucket_sort_body<T>(second ? (int)blockIdx.x - nb0 : (int)blockIdx.x, a.gp, a.shift, a.bucket_start, a.tmp, a.cell_start, a.sorted, a.pos_of,
+    bucket_sort_body<T>(second ? (int)blockIdx.x - nb0 : (int)blockIdx.x, a.gp, a.shift, a.bucket_start, a.tmp, a.cell_start, a.sorted,
                         a.large_list, a.n_large, prof, cnt_cap, a.cap, a.bucket_total, a.n);
 }
 template <typename T>
@@ -946,7 +942,7 @@ static size_t bucket_sort_lds_bytes(int cnt_cap) { return (size_t)cnt_cap * 4 + 
 template <typename T>
 struct LargeJob {
     const GridParams<T>* gp; const unsigned* bucket_start; const unsigned* large_list; const unsigned* n_large;
-    const Pt4<T>* tmp; const unsigned* rank_tmp; const unsigned* cell_start; Pt4<T>* sorted; unsigned* pos_of; int n_pts;
+    const Pt4<T>* tmp; const unsigned* rank_tmp; const unsigned* cell_start; Pt4<T>* sorted; int n_pts;
 };
 // One launch serves the indexes built back to back (both clouds of a two-sided call): njobs <= 2.
 template <typename T>
@@ -968,7 +964,6 @@ __global__ __launch_bounds__(kBlock) void k_bucket_large(const LargeJob<T> j0, c
                 const unsigned pos = J.cell_start[cell_linear(g, rec.x, rec.y, rec.z)] + J.rank_tmp[p];
                 J.sorted[pos] = rec;
                 put_xyz(J.sorted, J.n_pts, pos, rec);
-                if (J.pos_of) J.pos_of[rec.idx] = pos;
             }
         }
     }

@@ -70,14 +70,14 @@ struct Build2Side {
     unsigned long long* ovf;        // != 0: some bucket overflowed its slot (the index is unusable; -> GridParams::has_large = 2)
     Pt4<T>* tmp; unsigned cap;      // bucket b owns tmp[b * cap, (b + 1) * cap)
     T* xpartial; int n_xpart;       // exact bbox / non-finite partials, one per scatter block
-    unsigned* cell_start; Pt4<T>* sorted; unsigned* pos_of; int want_pt4;
+    unsigned* cell_start; Pt4<T>* sorted; int want_pt4;
     unsigned* n_large;              // (the two-pass build's count of over-full buckets: none here, but k_bucket_large may be launched on this index)
     unsigned long long* zero_next; int n_zero_next;       // the other set of fill words, zeroed for the context's next build (side 0 only)
     unsigned* zero2; int n_zero2;   // the call's result block (side 0 only)
     long long* prof;                // diagnostics (PCU_HIP_PROF_BUILD2): per-stage time of every block's thread 0, summed; 100 MHz ticks
     // SHARED GRID (round 6; two-sided calls between clouds of comparable size): both clouds of the call are laid over ONE grid -- same origin,
     // cell edge and cell counts -- so that a query's cell in its own cloud's order IS its cell in the dataset's grid and a block of consecutive
-    // queries needs a compact box of dataset rows (search_brick.h stages that box in LDS). The layout then comes from 512 samples of EACH cloud,
+    // queries needs a compact box of dataset rows (the lanes of a wave look at neighbouring cells). The layout then comes from 512 samples of EACH cloud,
     // read in the same order by the blocks of both sides (identical arithmetic on identical inputs: identical grids), for n_layout = the larger
     // cloud's size. spts1 == nullptr: the cloud's own grid from its own 1024 samples, as before.
     const T* spts0; int sn0; const T* spts1; int sn1; int n_layout;
@@ -540,7 +540,6 @@ __device__ __forceinline__ void sort2_body(const int b, const Build2Side<T>& a, 
                     const unsigned pos = s + s_cnt[r >> 16] + (r & 0xffffu);
                     if (a.want_pt4) a.sorted[pos] = rec[u];
                     put_xyz(a.sorted, n_pts, pos, rec[u]);
-                    if (a.pos_of) a.pos_of[rec[u].idx] = pos;
                 }
             }
         }
@@ -572,7 +571,6 @@ __device__ __forceinline__ void sort2_body(const int b, const Build2Side<T>& a, 
         const int id = sidx[i];
         idx32[s + i] = id;
         if (a.want_pt4) { Pt4<T> r; const T* const o = st + phase + 3u * i; r.x = o[0]; r.y = o[1]; r.z = o[2]; r.idx = id; a.sorted[s + i] = r; }
-        if (a.pos_of) a.pos_of[id] = s + i;
     }
     {
         // stage scalar L <-> output scalar 3 s - phase + L; the packed stream is stage[phase, end)

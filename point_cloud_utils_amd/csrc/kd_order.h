@@ -96,17 +96,17 @@ __device__ __forceinline__ bool kd_in_roi(const KdBuild<T>& b, const T* lo, cons
 template <typename T>
 __device__ __forceinline__ T kd_coord(const Pt4<T>* E, int p, int d) { return reinterpret_cast<const T*>(E + p)[d]; }
 
-// Regions of interest from the list of tied queries (cell-ordered result rows give the k-th distance).
+// Regions of interest from the list of tied queries (their result rows give the k-th distance).
 constexpr int kKdMaxRoi = 64;
 template <typename T>
 __global__ void k_kd_roi(const Pt4<T>* __restrict__ qsorted, const int* __restrict__ qlist, int n_tied, const T* __restrict__ res_d, int k, int squared,
-                         int row_out, T* __restrict__ roi, int* n_roi) {
+                         T* __restrict__ roi, int* n_roi) {
     const int t = threadIdx.x;
     if (t == 0) *n_roi = n_tied;
     if (t >= n_tied) return;
     const int qpos = qlist[t];
     const Pt4<T> q = qsorted[qpos];
-    const T dk = res_d[(size_t)(row_out ? (int)q.idx : qpos) * k + (k - 1)];
+    const T dk = res_d[(size_t)(int)q.idx * k + (k - 1)];
     T r2 = squared ? dk : dk * dk;
     r2 = dk < 0 ? (T)INFINITY : r2 * (T)9 * ((T)1 + (T)1e-3);            // R = 3 x the k-th distance (fewer than k found: everything)
     roi[4 * t] = q.x; roi[4 * t + 1] = q.y; roi[4 * t + 2] = q.z; roi[4 * t + 3] = r2;
@@ -1060,7 +1060,7 @@ template <typename T>
 struct KdSearchArgs {
     const Pt4<T>* E; const KdNode<T>* nodes;
     const Pt4<T>* qsorted; const int* qlist; const int* qcount_dev;
-    int k, squared, row_out;
+    int k, squared;
     T* out_d; long long* out_i;
     void* stack; int stack_cap;         // per work item: stack_cap frames (tree depth + 2) in global memory
     const unsigned* cancel_word = nullptr; unsigned cancel_gen = 0;       // pcu_types.h: cancel_seen (looked at every 1024 traversal steps)
@@ -1227,7 +1227,7 @@ __global__ __launch_bounds__(64) void k_kd_search(const KdSearchArgs<T> a) {
     __shared__ T s_dists[3]; __shared__ T s_vec[3];                     // indexed by the split dimension: kept in LDS so
                                                                         // that no select chain on a uniform index is generated
     const Pt4<T> q = a.qsorted[a.qlist[t]];
-    kd_search_one<T, false>(a, t, t, q, (size_t)(a.row_out ? (int)q.idx : a.qlist[t]), rd, ri, s_dists, s_vec);      // cell-ordered result rows unless row_out
+    kd_search_one<T, false>(a, t, t, q, (size_t)(int)q.idx, rd, ri, s_dists, s_vec);      // the query's own result row
 }
 
 // Whole-cloud mode: blocks (one wave each) stride over the raw query rows.

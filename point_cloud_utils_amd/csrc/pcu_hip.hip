@@ -25,7 +25,6 @@
 #include "grid2.h"
 #include "reduce.h"
 #include "search.h"
-#include "search_brick.h"
 namespace pcu {          // the k > 1 search kernels are compiled in search_kernels.hip (second translation unit, built in parallel)
 #define PCU_SEARCH_INST extern template
 #include "search_inst.h"
@@ -240,8 +239,6 @@ struct pcu_hip_ctx {
                                               // sub-call's use of the arena
     // grid2.h: GridGeo -- the layout of this context's last two-sided fused build, per cloud, on the device; what it was computed for, on the host
     struct GeoCache { char* dev = nullptr; bool valid[2] = {false, false}; int n[2] = {0, 0}; double occ = 0, h_want = 0; int max_cells = 0, n_layout = 0, tsize = 0; bool shared = false; } geo;
-    bool brick_off = false;                   // sticky: a staged k = 1 pass of this context (search_brick.h) fell back to global scans in more than a quarter of its
-                                              // blocks (surfaces, clusters: short uneven rows): its fused calls take k_search1_flat on per-cloud grids again
     unsigned cancel_epoch = 0;                // g_cancel_epoch at this context's last call (ctx_begin: reset of the cross-call device state after an abandoned call)
     std::vector<pcu_hip_ctx*> lanes; int n_lanes_wanted = 4;   // (262k-point pairs, round 4, us per pair at 1 / 2 / 3 / 4 / 5 / 6 / 8 lanes: 83 / 51 / 43 / 41 / 47 / 44 / 41 -- scratch/lanes.py; the host is the limit from 3 on)
     hipEvent_t batch_ev = nullptr;
@@ -382,7 +379,6 @@ struct GridIndex {
     unsigned* cell_of = nullptr; unsigned* rank = nullptr; unsigned* block_sums = nullptr;
     T* bbox_partial = nullptr;
     int n = 0, max_cells = 0, scan_blocks = 0;
-    unsigned* pos_of = nullptr;           // row -> slot in `sorted` (only when asked for: k_unpermute)
     // bucketed build (grid.h): cells per bucket = 1 << shift; nb_max = host bound on the number of buckets
     bool bucketed = false; int shift = 0, nb_max = 0, n_zero = 0;
     double h_want = 0.0;                  // > 0: cells at least this large (fixed-radius searches)
@@ -435,7 +431,7 @@ static size_t index_bytes(int64_t n, double occ) {
     return b;
 }
 template <typename T>
-static int index_alloc(Arena& a, GridIndex<T>& g, int64_t n, double occ, bool want_pos = false, bool allow_bucketed = true, bool one_pass = false, int64_t n_plan = 0) {
+static int index_alloc(Arena& a, GridIndex<T>& g, int64_t n, double occ, bool allow_bucketed = true, bool one_pass = false, int64_t n_plan = 0) {
     // (n_plan: the cell / bucket plan of a larger cloud -- the partner this cloud shares its grid with, see GridIndex::shared_grid)
     const int64_t np = n_plan > n ? n_plan : n;
     g.n = (int)n; g.max_cells = max_cells_for(np, occ); g.scan_blocks = g.max_cells / kScanChunk + 1;
@@ -459,15 +455,12 @@ static int index_alloc(Arena& a, GridIndex<T>& g, int64_t n, double occ, bool wa
         if (aalloc(a, &g.bucket_start, (size_t)g.nb_max + 1) || aalloc(a, &g.large_list, (size_t)g.nb_max + 1)) return -1;
         if (aalloc(a, &g.block_base, (size_t)((n + kBkBlockPts - 1) / kBkBlockPts) * g.nb_max)) return -1;
         if (one_pass && aalloc(a, &g.xpartial, (size_t)((n + 2047) / 2048) * kXPartStride)) return -1;        // (one partial per scatter block: 2048 points at least, grid2.h)
-        g.pos_of = want_pos ? g.cell_of : nullptr;      // cell_of is not used by this build
-    } else {
-        g.pos_of = g.rank;                              // k_scatter turns rank into the slot, in place
     }
     return 0;
 }
 // Placement of the records of over-full buckets (grid.h): one launch for up to two indexes built back to back.
 template <typename T>
-static LargeJob<T> large_job(const GridIndex<T>& g) { return LargeJob<T>{g.gp, g.bucket_start, g.large_list, g.n_large, g.tmp, g.rank, g.cell_start, g.sorted, g.pos_of, g.n}; }
+static LargeJob<T> large_job(const GridIndex<T>& g) { return LargeJob<T>{g.gp, g.bucket_start, g.large_list, g.n_large, g.tmp, g.rank, g.cell_start, g.sorted, g.n}; }
 template <typename T>
 static void index_large_pass(const GridIndex<T>& a, const GridIndex<T>* b, hipStream_t s) {
     const bool ua = a.bucketed, ub = b && b->bucketed;
@@ -484,7 +477,7 @@ static void index_large_pass(const GridIndex<T>& a, const GridIndex<T>* b, hipSt
 template <typename T>
 static BucketSide<T> bucket_side(const GridIndex<T>& g, const T* pts) {
     return BucketSide<T>{pts, g.n, g.gp, g.shift, g.nb_max, g.bucket_total, g.block_base, g.bucket_start, g.tmp, g.cell_start, g.rank,
-                         g.sorted, g.pos_of, g.large_list, g.n_large, g.one_pass ? kLargeBucket : 0u};
+                         g.sorted, g.large_list, g.n_large, g.one_pass ? kLargeBucket : 0u};
 }
 template <typename T>
 static int index_build_pair(GridIndex<T>& a, const T* pa, double occa, GridIndex<T>* b, const T* pb, double occb, hipStream_t s,
@@ -511,8 +504,7 @@ static int index_build_pair(GridIndex<T>& a, const T* pa, double occa, GridIndex
         kBkThreads * StagedPts<T>::n >= run_floor) {
         unsigned long long* const fw = ctx->fill2 + (size_t)ctx->fill_parity * kFillWords;
         unsigned long long* const fw_next = ctx->fill2 + (size_t)(ctx->fill_parity ^ 1) * kFillWords;
-        // points per thread of the scatter blocks: the most (longest runs per (block, bucket), fewest reservations); PCU_HIP_BUILD_PTS fixes it (A/B)
-        static const int pts_env = getenv("PCU_HIP_BUILD_PTS") ? atoi(getenv("PCU_HIP_BUILD_PTS")) : 0;
+        // points per thread of the scatter blocks: the most (longest runs per (block, bucket), fewest reservations)
         int pts = StagedPts<T>::n;
         {
             const long long ntot = (long long)a.n + (b ? b->n : 0);
@@ -520,13 +512,12 @@ static int index_build_pair(GridIndex<T>& a, const T* pa, double occa, GridIndex
             // (measured, profiles/r06_build_ab.txt: halving the blocks to get a block per CU -- or two per CU at 2 x 1M -- LOSES: every stage of a
             // block takes as long with half the points, reservations and padding double; only launches of a handful of blocks are cut up)
             while (pts > 2 && (ntot + (long long)kBkThreads * pts - 1) / ((long long)kBkThreads * pts) < n_cu / 16 && kBkThreads * (pts / 2) >= run_floor) pts /= 2;
-            if (pts_env == 2 || pts_env == 4 || pts_env == 8) pts = std::min(pts_env, (int)StagedPts<T>::n);
         }
         const int bpts = kBkThreads * pts;
         const int nbcap = (std::max(a.nb_max, b ? b->nb_max : 0) + 63) / 64 * 64;
         auto side = [&](const GridIndex<T>& g, const T* p, double occ, int k) {
             return Build2Side<T>{p, g.n, g.gp, g.shift, occ, g.max_cells, g.h_want, fw + (size_t)k * kStagedMaxBuckets, fw + 2 * kStagedMaxBuckets + k,
-                                 g.tmp, kLargeBucket, g.xpartial, (g.n + bpts - 1) / bpts, g.cell_start, g.sorted, g.pos_of, g.lean ? 0 : 1, g.n_large,
+                                 g.tmp, kLargeBucket, g.xpartial, (g.n + bpts - 1) / bpts, g.cell_start, g.sorted, g.lean ? 0 : 1, g.n_large,
                                  k == 0 ? fw_next : nullptr, k == 0 ? kFillWords : 0, k == 0 ? (unsigned*)zero2 : nullptr, k == 0 ? n_zero2 : 0, nullptr,
                                  p, g.n, nullptr, 0, g.n, nullptr, nullptr};
         };
@@ -759,11 +750,10 @@ static double call_occupancy(const pcu_hip_ctx* c, int k, int role) { return c->
 #endif
 constexpr int kWaveBlocks = PCU_WAVE_BLOCKS;    // fixed grid of the wave-cooperative passes: 2048 waves striding a device-side list
 
-// ONE grid over both clouds of a two-sided call (grid2.h: Build2Side::spts1; what search_brick.h's staged pass needs): clouds of comparable size
-// indexed at the same occupancy. PCU_HIP_NO_SHARED_GRID=1: every cloud its own grid, as before round 6.
+// ONE grid over both clouds of a two-sided call (grid2.h: Build2Side::spts1): clouds of comparable size indexed at the same occupancy. PCU_HIP_NO_SHARED_GRID=1: every cloud its own grid, as before round 6.
 static bool shared_grid_wanted(const pcu_hip_ctx* c, int64_t nx, int64_t ny, double occ_x, double occ_y) {
     static const bool off = getenv("PCU_HIP_NO_SHARED_GRID") != nullptr;
-    return !off && !c->brick_off && occ_x == occ_y && std::min(nx, ny) >= kPrepSamples && std::max(nx, ny) <= 2 * std::min(nx, ny);
+    return !off && occ_x == occ_y && std::min(nx, ny) >= kPrepSamples && std::max(nx, ny) <= 2 * std::min(nx, ny);
 }
 // whole-call index builds use the one-pass bucket scatter until a cloud of this context overflows a slot (PCU_HIP_TWO_PASS=1: never)
 static bool use_one_pass(const pcu_hip_ctx* c) { static const bool off = getenv("PCU_HIP_TWO_PASS") != nullptr; return !off && !c->two_pass; }
@@ -774,10 +764,6 @@ static int wave_escalates() { static const bool off = getenv("PCU_HIP_NO_ESCALAT
 static bool use_k1_kernel() { static const bool v = getenv("PCU_HIP_NO_K1") == nullptr; return v; }
 static int grid8(int nwork, int tb) { return (((nwork + tb - 1) / tb) + 7) / 8 * 8; }       // multiple of 8: XCD-aware block map
 
-template <typename T> static void launch_brick(const SearchArgs2<T>&, int, int, hipStream_t) {}
-template <> void launch_brick<float>(const SearchArgs2<float>& p2, int b0, int b1, hipStream_t s) {
-    hipLaunchKernelGGL((k_search1_brick<float, kBrickNT>), dim3(b0 + b1), dim3(kBrickNT), 0, s, p2, b0);
-}
 // Main (lane-per-query) pass of one direction, or -- k = 1 on open indexes -- of both directions of a two-sided call in
 // one launch (a1 / nwork1).
 template <typename T>
@@ -789,12 +775,6 @@ static int launch_search_fast(int K, const SearchArgs<T>& a, int nwork, hipStrea
     const int tb = kBlock;
     if (K == 1 && use_k1_kernel() && open_index) {        // k = 1 on an open index: the group-wise flat kernel
         SearchArgs2<T> p2; p2.a[0] = a; p2.a[1] = a1 ? *a1 : a;
-        if (sizeof(T) == 4 && a.fuse == FUSE_SUM && a.brick && a1 && a1->brick && !a.qlist && !a1->qlist) {       // shared grid: the staged pass (search_brick.h)
-            const int b0 = grid8(nwork, kBrickNT), b1 = grid8(nwork1, kBrickNT);
-            launch_brick<T>(p2, b0, b1, s);
-            HIP_TRY(hipGetLastError());
-            return 0;
-        }
         const int g0 = grid8(nwork, tb), g1 = a1 ? grid8(nwork1, tb) : 0;
         // (An LDS-staged, block-cooperative variant of this pass -- the north-star's tile design -- was measured again in round 4: 243-593 us
         // against 77 us, profiles/r04_flat_tile_ab.txt; removed.)
@@ -807,19 +787,19 @@ static int launch_search_fast(int K, const SearchArgs<T>& a, int nwork, hipStrea
 #define PCU_FLAT(FUSE) hipLaunchKernelGGL((k_search1_flat<T, false, sizeof(T) == 4 ? (FUSE == FUSE_SUM ? PCU_FLAT_MINW : PCU_FLAT_MINW_ROWS) : 4, FUSE>), dim3(g0 + g1), dim3(tb), 0, s, p2, g0)
         // (a variant that deals a wave's candidate groups evenly to its lanes -- LDS list + atomic min -- measured 75.6 vs 76.5 us: the loop is
         // not where the instructions are, profiles/r04_flat_deal_ab.txt; removed)
+        // (fused arg-max: the value-only program, FUSE_MAXVAL; k_fuse_tail resolves the winner's neighbour, reduce.h)
         if (a.fuse == FUSE_SUM) PCU_FLAT(FUSE_SUM);
-        else if (a.fuse == FUSE_ARGMAX && a.maxval && (!a1 || a1->maxval)) hipLaunchKernelGGL((k_search1_flat<T, false, sizeof(T) == 4 ? PCU_FLAT_MINW : 4, FUSE_MAXVAL>), dim3(g0 + g1), dim3(tb), 0, s, p2, g0);
-        else if (a.fuse == FUSE_ARGMAX) PCU_FLAT(FUSE_ARGMAX);
-        else PCU_FLAT(FUSE_NONE);
+        else if (a.fuse == FUSE_ARGMAX) hipLaunchKernelGGL((k_search1_flat<T, false, sizeof(T) == 4 ? PCU_FLAT_MINW : 4, FUSE_MAXVAL>), dim3(g0 + g1), dim3(tb), 0, s, p2, g0);
+        else if (a.fuse == FUSE_NONE) PCU_FLAT(FUSE_NONE);
+        else return fail(PCU_HIP_ERR_RUNTIME, "internal: no k = 1 lane kernel for fuse mode %d", a.fuse);
 #undef PCU_FLAT
         HIP_TRY(hipGetLastError());
         return 0;
     }
     if (a1) return fail(PCU_HIP_ERR_RUNTIME, "internal: paired main pass without the k = 1 kernel");
     dim3 grid(grid8(nwork, tb)), block(tb);
-    // k > 1 on an open index: the run-list kernel (search.h: k_search_runs, round 5); PCU_HIP_KSEARCH_V1=1 keeps k_search everywhere (A/B, switch test)
-    static const bool runs_off = getenv("PCU_HIP_KSEARCH_V1") != nullptr;
-    if (K > 1 && open_index && !runs_off) {
+    // k > 1 on an open index: the run-list kernel (search.h: k_search_runs, round 5); k_search serves closed sub-box levels
+    if (K > 1 && open_index) {
 #define PCU_CASE(KK) case KK: hipLaunchKernelGGL((k_search_runs<T, KK>), grid, block, 0, s, a); break;
         switch (K) {
             case 2: PCU_CASE(4) PCU_CASE(8) PCU_CASE(16) PCU_CASE(32)
@@ -886,7 +866,6 @@ struct SearchJob {           // one direction: queries of `qidx` against the dat
     const T* d_ref_pts = nullptr;
     double occ = 1.5;
     int k = 1; bool squared = false;
-    bool row_out = false;                       // results written straight to the caller's row order (k_nearest_neighbors, k >= 4)
     int leaf_max = 10; bool tie_order = true;   // reference's max_points_per_leaf: defines the order of exact ties
     int n_tt = 0;                               // genuine-tie queries found (filled by search_finish)
     bool skew_check = true;                     // give up early on a badly unbalanced dataset grid (then: refitted finer grids)
@@ -900,8 +879,6 @@ struct SearchJob {           // one direction: queries of `qidx` against the dat
     SearchScratch<T> sc;
     // fused epilogue (reduce.h): per-block partials of the k = 1 lane pass instead of result rows
     int fuse = FUSE_NONE; int n_flat = 0;
-    bool maxval = false;                        // fused arg-max: value-only lane pass, the winner's neighbour resolved by k_fuse_tail (reduce.h: FuseTail::maxval)
-    bool brick = false;                         // the lane pass is search_brick.h's staged pass (shared grid, fused sum, float)
     double* f_sum = nullptr; T* f_max_v = nullptr; long long* f_max_k = nullptr;
     unsigned long long* f_limbs = nullptr; double* f_special = nullptr; T* f_wave_v = nullptr; long long* f_wave_k = nullptr;
 };
@@ -914,7 +891,7 @@ static SearchArgs<T> base_args(const SearchJob<T>& j, const GridIndex<T>& ridx) 
     a.q_xyz = xyz_of(j.qidx.sorted, j.qidx.n); a.q_idx = idx32_of(j.qidx.sorted, j.qidx.n);
     a.lean = (ridx.lean || j.qidx.lean) ? 1 : 0;
     a.qlist = nullptr; a.qcount_dev = nullptr; a.nq = 0; a.R = 1; a.kreq = j.k; a.squared = j.squared ? 1 : 0;
-    a.qlist2 = nullptr; a.qcount2_dev = nullptr; a.R2 = 0; a.row_out = j.row_out ? 1 : 0;
+    a.qlist2 = nullptr; a.qcount2_dev = nullptr; a.R2 = 0;
     a.out_d = j.out_d; a.out_i = j.out_i;
     a.unresolved = nullptr; a.n_unresolved = nullptr; a.ties = nullptr; a.n_ties = nullptr; a.ubound = nullptr; a.qbound2 = nullptr;
     a.skew_limit = 0.f; a.skew_far = 3.0e38f; a.skew_lo = 0.f; a.skew_flag = j.sc.counters + C_SKEW;      // only the first whole-cloud pass checks the balance
@@ -927,7 +904,6 @@ static SearchArgs<T> base_args(const SearchJob<T>& j, const GridIndex<T>& ridx) 
     a.f_limbs = j.f_limbs; a.f_special = j.f_special; a.f_wave_v = j.f_wave_v; a.f_wave_k = j.f_wave_k; a.f_accum = 0;
     a.bad_r = j.bad_r; a.bad_q = j.bad_q; a.escalate = 0;
     a.cancel_word = g_cancel_mirror.load(std::memory_order_relaxed); a.cancel_gen = t_call_gen;
-    a.brick = j.brick ? 1 : 0; a.n_fallback = j.sc.counters + C_SPARE; a.maxval = j.maxval ? 1 : 0;
     return a;
 }
 
@@ -935,8 +911,6 @@ static SearchArgs<T> base_args(const SearchJob<T>& j, const GridIndex<T>& ridx) 
 // device-side lists: possible ties (radius 1, total order) and stragglers (radius 2). What is still uncertified after
 // that (list u2; next to nothing on balanced clouds) is finished by search_finish's host-driven loop.
 // what: 1 = the lane passes only, 2 = only the wave-per-query launch that follows them, 3 = both (wave-only jobs: always everything)
-template <typename T>
-static bool lazy_wave_job(const SearchJob<T>& j);
 template <typename T>
 static int search_enqueue(pcu_hip_ctx* c, hipStream_t s, const SearchJob<T>& j, pcu_hip_stats* st, bool zero_counters = true, int what = 3) {
     const SearchScratch<T>& sc = j.sc;
@@ -1021,16 +995,13 @@ static bool lane_k1_job(const SearchJob<T>& j) { return j.k == 1 && j.qidx.n >= 
 // A k = 1 lane job on an open index finishes its stragglers inside the lane launch (search.h: radius 2 by the query's own wave): its wave pass
 // can wait until the counters say that something is left.
 template <typename T>
-static bool lazy_wave_job(const SearchJob<T>& j) { static const bool off = getenv("PCU_HIP_FUSED_WAVE") != nullptr; return !off && lane_k1_job(j); }
-template <typename T>
 static int search_enqueue_pair(pcu_hip_ctx* c, hipStream_t s, const SearchJob<T>& j0, const SearchJob<T>& j1, pcu_hip_stats* st, int what = 3) {
     if (!(lane_k1_job(j0) && lane_k1_job(j1))) {
         if (j0.fuse || j1.fuse) return fail(PCU_HIP_ERR_RUNTIME, "internal: fused epilogue without the paired k = 1 pass");
         // Two small clouds (wave-per-query from the start, see search_enqueue): both directions share each of the two launches -- such a
         // call is a chain of launch latencies (config 1, 10k-vs-10k: 4 wave launches of 46 + 9 + 43 + 10 us were 60 % of its GPU time).
         auto wave_only = [](const SearchJob<T>& j) { return (j.k > kMaxKLane || j.qidx.n < kWaveOnlyBelow) && j.n_fine == 0; };
-        static const bool no_merge = getenv("PCU_HIP_NO_WAVE_MERGE") != nullptr;
-        if (!no_merge && what == 3 && wave_only(j0) && wave_only(j1) && j0.k == j1.k) {
+        if (what == 3 && wave_only(j0) && wave_only(j1) && j0.k == j1.k) {
             const int KL = std::max(2, pow2_at_least(j0.k + 1));
             SearchArgs<T> b[2];
             for (int d = 0; d < 2; ++d) {
@@ -1162,7 +1133,7 @@ static int kd_build_device(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const T* d_
         static const bool no_roi = getenv("PCU_HIP_KD_FULL") != nullptr;
         if (roi_job && n_tied > 0 && n_tied <= kKdMaxRoi && !no_roi)
             hipLaunchKernelGGL(k_kd_roi<T>, dim3(1), dim3(kKdMaxRoi), 0, s, roi_job->qidx.sorted, roi_job->sc.tt, n_tied, roi_job->out_d, roi_job->k,
-                               roi_job->squared ? 1 : 0, roi_job->row_out ? 1 : 0, roi, n_roi);
+                               roi_job->squared ? 1 : 0, roi, n_roi);
     } else {
     if (speculative) HIP_TRY(hipStreamWaitEvent(s, sp.ev_fork, 0));
     HIP_TRY(hipMemsetAsync(counters, 0, 16 * sizeof(int), s));
@@ -1170,7 +1141,7 @@ static int kd_build_device(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const T* d_
     static const bool no_roi = getenv("PCU_HIP_KD_FULL") != nullptr;
     if (!speculative && roi_job && n_tied > 0 && n_tied <= kKdMaxRoi && !no_roi)
         hipLaunchKernelGGL(k_kd_roi<T>, dim3(1), dim3(kKdMaxRoi), 0, s, roi_job->qidx.sorted, roi_job->sc.tt, n_tied, roi_job->out_d, roi_job->k,
-                           roi_job->squared ? 1 : 0, roi_job->row_out ? 1 : 0, roi, n_roi);
+                           roi_job->squared ? 1 : 0, roi, n_roi);
     else HIP_TRY(hipMemsetAsync(n_roi, 0, sizeof(int), s));
     hipLaunchKernelGGL(k_kd_init_elems<T>, dim3((M + kBlock - 1) / kBlock), dim3(kBlock), 0, s, d_pts, M, b.E);
     hipLaunchKernelGGL(k_kd_root<T>, dim3(1), dim3(64), 0, s, b, gp, M);
@@ -1373,7 +1344,7 @@ static int tie_order_resolve(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob
         if (lazy) levels = kDepthBound;
         KdSearchArgs<T> a;
         a.E = b.E; a.nodes = b.nodes; a.qsorted = j.qidx.sorted; a.qlist = j.sc.tt; a.qcount_dev = j.sc.counters + C_TT;
-        a.k = j.k; a.squared = j.squared ? 1 : 0; a.row_out = j.row_out ? 1 : 0; a.out_d = j.out_d; a.out_i = j.out_i; a.error_flag = err;
+        a.k = j.k; a.squared = j.squared ? 1 : 0; a.out_d = j.out_d; a.out_i = j.out_i; a.error_flag = err;
         a.qraw = nullptr; a.nq_raw = 0; a.rs_d = nullptr; a.rs_i = nullptr;
         a.cancel_word = g_cancel_mirror.load(std::memory_order_relaxed); a.cancel_gen = t_call_gen;
         KdFrame<T>* frames = nullptr;
@@ -1628,18 +1599,6 @@ struct ResultBlock {
 };
 static_assert(sizeof(ResultBlock) == 256, "ResultBlock layout");
 
-// Row-order restore of a job's cell-ordered results (either destination may be null).
-template <typename T>
-static int unpermute_enqueue(hipStream_t s, const SearchJob<T>& j, T* dst_d, long long* dst_i,
-                             const ResultBlock* rb = nullptr, int* host_block = nullptr, unsigned seq = 0) {
-    const long long n_elems = (long long)j.qidx.n * j.k;
-    hipLaunchKernelGGL(k_unpermute<T>, dim3((unsigned)((n_elems + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                       j.qidx.pos_of, j.out_d, j.out_i, dst_d, dst_i, n_elems, j.k, reinterpret_cast<const int*>(rb), host_block, seq,
-                       j.sc.counters + C_SKEW);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------ validation
 static int validate_sizes(int64_t nq, int64_t nr, const char* qname, const char* rname) {
     if (nq <= 0 || nr <= 0)
@@ -1727,7 +1686,7 @@ static int knn_big_k(pcu_hip_ctx* c, const T* query, int64_t nq, const T* datase
         if ((rc = kd_build_device(c, ar, s, dr, (int)nr, gi.gp, max_leaf > 0 ? max_leaf : 10, b, &err, &levels, nullptr))) break;
         KdSearchArgs<T> a;
         a.E = b.E; a.nodes = b.nodes; a.qsorted = nullptr; a.qlist = nullptr; a.qcount_dev = nullptr;
-        a.k = k; a.squared = squared ? 1 : 0; a.row_out = 1; a.out_d = dd; a.out_i = di; a.error_flag = err;
+        a.k = k; a.squared = squared ? 1 : 0; a.out_d = dd; a.out_i = di; a.error_flag = err;
         a.qraw = dq; a.nq_raw = (int)nq; a.rs_d = nullptr; a.rs_i = nullptr;
         a.cancel_word = g_cancel_mirror.load(std::memory_order_relaxed); a.cancel_gen = t_call_gen;
         if (!rs_lds && ((rc = aalloc(ar, &a.rs_d, (size_t)grid * k)) || (rc = aalloc(ar, &a.rs_i, (size_t)grid * k)))) break;
@@ -1778,8 +1737,7 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
     // cells of one dataset row, profiles/r06_flat_aligned_ab.txt; both indexes are planned for the larger cloud)
     const bool share = !pidx && shared_grid_wanted(c, nq, nr, occ_q, occ);
     const int64_t n_plan = share ? std::max(nq, nr) : 0;
-    size_t need = (pidx ? 0 : index_bytes<T>(std::max(nr, n_plan), occ)) + index_bytes<T>(std::max(nq, n_plan), occ_q) + scratch_bytes<T>(nq) + 8192 +
-                  align_up((size_t)nq * k * sizeof(T), 256) + align_up((size_t)nq * k * 8, 256);     // cell-ordered results
+    size_t need = (pidx ? 0 : index_bytes<T>(std::max(nr, n_plan), occ)) + index_bytes<T>(std::max(nq, n_plan), occ_q) + scratch_bytes<T>(nq) + 8192;
     if (!on_dev) need += align_up((size_t)nq * 3 * sizeof(T), 256) + (pidx ? 0 : align_up((size_t)nr * 3 * sizeof(T), 256)) +
                          align_up((size_t)nq * k * sizeof(T), 256) + align_up((size_t)nq * k * 8, 256);
     if (ctx_begin(c, need)) return PCU_HIP_ERR_RUNTIME;
@@ -1795,16 +1753,12 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         if (!on_dev) { if ((rc = aalloc(ar, &dd, (size_t)nq * k))) break; if ((rc = aalloc(ar, &di, (size_t)nq * k))) break; }
         SearchJob<T> job;
         // Every kernel writes a result row straight to the query's ORIGINAL row: no cell-ordered copy, no row-order restore pass, no row -> slot
-        // table from the index build. For k >= 4 (rows >= 48 bytes) that was always so; for k < 4 the rows used to be written coalesced in the
-        // queries' cell order and gathered back by k_unpermute -- two scattered line fetches per query (185 MB for a 12 MB result at 1M, k = 1) plus
-        // 37 MB of scattered row -> slot stores in the build. The scattered 4 / 8-byte row stores cost 67 MB instead (profiles/r04_c2_ab.txt):
-        // config 2 0.184 -> 0.154 ms. PCU_HIP_ROW_OUT_MIN_K=4 restores the old split.
-        static const int row_out_min_k = getenv("PCU_HIP_ROW_OUT_MIN_K") ? atoi(getenv("PCU_HIP_ROW_OUT_MIN_K")) : 1;
-        const bool row_out = k >= row_out_min_k;
-        job.row_out = row_out;
+        // table from the index build. (Rows written coalesced in the queries' cell order and gathered back cost two scattered line fetches per
+        // query -- 185 MB for a 12 MB result at 1M, k = 1 -- plus 37 MB of scattered row -> slot stores in the build. The scattered 4 / 8-byte
+        // row stores cost 67 MB instead (profiles/r04_c2_ab.txt): config 2 0.184 -> 0.154 ms.)
         if (pidx) job.ridx = index_grid<T>(pidx);
-        else if ((rc = index_alloc(ar, job.ridx, nr, occ, false, true, use_one_pass(c), n_plan))) break;
-        if ((rc = index_alloc(ar, job.qidx, nq, occ_q, /*want_pos=*/!row_out, true, use_one_pass(c), n_plan))) break;
+        else if ((rc = index_alloc(ar, job.ridx, nr, occ, true, use_one_pass(c), n_plan))) break;
+        if ((rc = index_alloc(ar, job.qidx, nq, occ_q, true, use_one_pass(c), n_plan))) break;
         job.ridx.shared_grid = job.qidx.shared_grid = share;
         job.qidx.src = dq; job.qidx.occ_built = occ_q;
         if (!pidx) { job.ridx.src = dr; job.ridx.occ_built = occ; }
@@ -1813,16 +1767,12 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         if ((rc = scratch_alloc(ar, job.sc, nq, rb->counters[0]))) break;
         job.d_ref_pts = dr; job.occ = occ; job.k = k; job.squared = squared;
         job_rescale_setup(c, job, !pidx && restarts < 2, 1);
-        if (row_out) { job.out_d = dd; job.out_i = di; }
-        else {
-            if ((rc = aalloc(ar, &job.out_d, (size_t)nq * k))) break;
-            if ((rc = aalloc(ar, &job.out_i, (size_t)nq * k))) break;
-        }
+        job.out_d = dd; job.out_i = di;
         job.leaf_max = max_leaf > 0 ? max_leaf : 10; job.tie_order = !(flags & PCU_HIP_NO_TIE_ORDER);
         {   // k = 1 on a fresh pair of indexes: the lane kernel reads the coordinate and row-id streams only, so the Pt4 records are not
             // written (grid2.h; 16 MB less per million points); whatever runs after the first read-back fills them in first (job_unlean)
             static const bool no_lean = getenv("PCU_HIP_NO_LEAN") != nullptr;
-            const bool lean = !pidx && !no_lean && row_out && lane_k1_job(job) && job.ridx.bucketed && job.qidx.bucketed && job.ridx.one_pass && job.qidx.one_pass;
+            const bool lean = !pidx && !no_lean && lane_k1_job(job) && job.ridx.bucketed && job.qidx.bucketed && job.ridx.one_pass && job.qidx.one_pass;
             job.ridx.lean = job.qidx.lean = lean;
         }
         tm.mark(0);
@@ -1831,11 +1781,10 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         if (st) st->n_grid_builds += pidx ? 1 : 2;
         tm.mark(1);
         const bool spec = kd_speculate_fork(c, s, job);
-        const bool lazy_wave = lazy_wave_job(job);          // (k = 1: the wave pass only if the lane launch leaves something, see below)
+        const bool lazy_wave = lane_k1_job(job);            // (k = 1: the wave pass only if the lane launch leaves something, see below)
         if ((rc = search_enqueue(c, s, job, st, /*zero_counters=*/false, lazy_wave ? 1 : 3))) break;
         if (spec && (rc = kd_speculate(c, ar, s, job))) break;
-        if (row_out) { hipLaunchKernelGGL(k_result_block_to_host, dim3(1), dim3(64), 0, s, reinterpret_cast<const int*>(rb), c->h_pinned, ++c->seq); HIP_TRY(hipGetLastError()); }
-        else if ((rc = unpermute_enqueue(s, job, dd, di, rb, c->h_pinned, ++c->seq))) break;   // optimistic: redone below if stragglers / ties remain
+        hipLaunchKernelGGL(k_result_block_to_host, dim3(1), dim3(64), 0, s, reinterpret_cast<const int*>(rb), c->h_pinned, ++c->seq); HIP_TRY(hipGetLastError());
         tm.mark(2);
         HIP_WAIT(s);         // the per-row outputs must be complete, so this call waits for the stream, not for the word
         if ((unsigned)*(volatile int*)(c->h_pinned + 63) != c->seq) { rc = fail(PCU_HIP_ERR_RUNTIME, "internal: the result block did not arrive"); break; }
@@ -1856,14 +1805,7 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         }
         if ((rc = search_finish(c, ar, s, job, st, ((ResultBlock*)c->h_pinned)->counters[0])) < 0) { if (rc == PCU_NONFINITE) rc = nonfinite_error(false); break; }
         if (rc == 3) { rc = PCU_RETRY; break; }
-        if (row_out) { if (rc > 0) tm.mark(2); }
-        else if (rc == 1) { if ((rc = unpermute_enqueue(s, job, dd, di))) break; tm.mark(2); }
-        else if (rc == 2) {       // the resolver rewrote only the tied queries' rows: restore just those
-            hipLaunchKernelGGL(k_unpermute_rows<T>, dim3((unsigned)((job.n_tt * (long long)k + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                               job.sc.tt, job.n_tt, job.qidx.sorted, job.out_d, job.out_i, dd, di, k);
-            HIP_TRY(hipGetLastError());
-            tm.mark(2);
-        }
+        if (rc > 0) tm.mark(2);
         rc = 0;
         if (!on_dev) {
             HIP_TRY(hipMemcpyAsync(out_d, dd, (size_t)nq * k * sizeof(T), hipMemcpyDeviceToHost, s));
@@ -1929,12 +1871,11 @@ static size_t pair_bytes(int64_t nx, int64_t ny, double occ_x, double occ_y, boo
 }
 // A fused two-sided attempt is lane pass + fold: the k = 1 lane kernel finishes its own stragglers (search.h: radius 2 inside the lane), so the
 // wave-per-query pass -- a launch on the critical path of every call for a few hundred queries -- runs only when a direction's lists are not
-// empty afterwards (fused_needs_wave; then: wave pass + a second fold). PCU_HIP_FUSED_WAVE=1 launches it up front as before.
+// empty afterwards (fused_needs_wave; then: wave pass + a second fold).
 static int wait_result_block(pcu_hip_ctx* c, hipStream_t s);
-static bool fused_wave_upfront() { static const bool v = getenv("PCU_HIP_FUSED_WAVE") != nullptr; return v; }
 template <typename T>
 static int pair_search_enqueue(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, pcu_hip_stats* st) {
-    const bool lazy_wave = P.fuse && P.two && !fused_wave_upfront() && lane_k1_job(P.xy) && lane_k1_job(P.yx);
+    const bool lazy_wave = P.fuse && P.two && lane_k1_job(P.xy) && lane_k1_job(P.yx);
     if (P.two) { if (search_enqueue_pair(c, s, P.xy, P.yx, st, lazy_wave ? 1 : 3)) return -1; }
     else if (search_enqueue(c, s, P.xy, st, /*zero_counters=*/false)) return -1;
     P.wave_pending = lazy_wave;
@@ -1951,10 +1892,6 @@ template <typename T>
 static int fused_wave_if_needed(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, pcu_hip_stats* st, ResultBlock& host) {
     // The layout handed down from the previous call no longer fits these clouds (grid2.h: kGeoStale; every pass gave up): once more, laid out afresh.
     if ((host.counters[0][C_LARGE] | (P.two ? host.counters[1][C_LARGE] : 0)) & kGeoStale) { c->geo.valid[0] = c->geo.valid[1] = false; return PCU_RETRY; }
-    if (P.xy.brick) {           // the staged pass's report: blocks that scanned from global memory (search_brick.h)
-        const long long fb = (long long)host.counters[0][C_SPARE] + host.counters[1][C_SPARE], nb = (long long)P.xy.n_flat + P.yx.n_flat;
-        if (4 * fb > nb) c->brick_off = true;
-    }
     if (!P.wave_pending) return 0;
     P.wave_pending = false;
     bool need = false, broken = false;
@@ -1977,8 +1914,6 @@ static int pair_setup(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const T* x, int6
                       pcu_hip_stats* st, bool two_sided, int max_leaf, bool tie_order_xy, bool tie_order_yx, int fuse_mode = FUSE_NONE) {
     // (ext_ixy / ext_iyx: device arrays of the caller that take the correspondences directly. Result rows of the row-based path are in the
     // caller's ROW order -- the search kernels write them there, see knn_attempt -- so no row -> slot table is built and no restore pass runs.)
-    constexpr bool want_pos_x = false, want_pos_y = false;
-    P.xy.row_out = P.yx.row_out = true;
     P.two = two_sided;
     P.xy.leaf_max = P.yx.leaf_max = max_leaf > 0 ? max_leaf : 10; P.xy.tie_order = tie_order_xy; P.yx.tie_order = tie_order_yx;
     if (stage_in(ar, x, nx, on_dev, s, &P.dx)) return -1;
@@ -1986,7 +1921,7 @@ static int pair_setup(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const T* x, int6
     GridIndex<T> ix, iy;
     const bool share = two_sided && shared_grid_wanted(c, nx, ny, occ_x, occ_y);
     const int64_t n_plan = share ? std::max(nx, ny) : 0;
-    if (index_alloc(ar, ix, nx, occ_x, want_pos_x, true, use_one_pass(c), n_plan) || index_alloc(ar, iy, ny, occ_y, want_pos_y, true, use_one_pass(c), n_plan)) return -1;
+    if (index_alloc(ar, ix, nx, occ_x, true, use_one_pass(c), n_plan) || index_alloc(ar, iy, ny, occ_y, true, use_one_pass(c), n_plan)) return -1;
     ix.shared_grid = iy.shared_grid = share;
     ix.src = P.dx; iy.src = P.dy; ix.occ_built = occ_x; iy.occ_built = occ_y;        // (the jobs below hold copies: what a rebuild after a slot overflow starts from)
     if (ix.bucketed && iy.bucketed && ix.one_pass != iy.one_pass) ix.one_pass = iy.one_pass = false;
@@ -2026,11 +1961,7 @@ static int pair_setup(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const T* x, int6
             t.flat_sum[d] = J.f_sum; t.flat_v[d] = J.f_max_v; t.flat_k[d] = J.f_max_k; t.nflat[d] = J.n_flat;
             t.wave_v[d] = J.f_wave_v; t.wave_k[d] = J.f_wave_k; t.limbs[d] = J.f_limbs; t.special[d] = J.f_special;
         }
-        {   // Hausdorff: the value-only lane pass + the tail's resolution of the one winning query (PCU_HIP_NO_MAXVAL=1: the winner-tracking lane pass)
-            static const bool maxval_off = getenv("PCU_HIP_NO_MAXVAL") != nullptr;
-            t.maxval = (fuse_mode == FUSE_ARGMAX && !maxval_off) ? 1 : 0; t.squared = squared ? 1 : 0;
-            P.xy.maxval = P.yx.maxval = t.maxval != 0;
-        }
+        t.squared = squared ? 1 : 0;       // Hausdorff: the value-only lane pass + the tail's resolution of the one winning query
         {   // PCU_HIP_PROF_TAIL=1: stage timers of k_fuse_tail, printed every 256 calls (diagnostics)
             static const bool prof_tail = getenv("PCU_HIP_PROF_TAIL") != nullptr;
             static long long* tail_prof = nullptr; static long n_tail = 0;
@@ -2052,7 +1983,7 @@ static int pair_setup(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const T* x, int6
     // point less to write); whoever takes the call over when the attempt does not stand fills them in first (pair_unlean).
     {
         static const bool no_lean = getenv("PCU_HIP_NO_LEAN") != nullptr;
-        const bool lean = P.fuse != FUSE_NONE && !no_lean && ix.bucketed && iy.bucketed && ix.one_pass && iy.one_pass && !want_pos_x && !want_pos_y;
+        const bool lean = P.fuse != FUSE_NONE && !no_lean && ix.bucketed && iy.bucketed && ix.one_pass && iy.one_pass;
         ix.lean = iy.lean = P.xy.qidx.lean = P.xy.ridx.lean = P.yx.qidx.lean = P.yx.ridx.lean = lean;
     }
     tm.mark(0);
@@ -2062,13 +1993,6 @@ static int pair_setup(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const T* x, int6
     if (index_build_pair<T>(ix, P.dx, occ_x, &iy, P.dy, occ_y, s, /*defer_large=*/!c->eager_large, P.cb, (int)(sizeof(CallBlock) / 4), c, /*keep_layout=*/P.fuse != FUSE_NONE)) return -1;
     P.xy.qidx.lean = P.yx.ridx.lean = ix.lean; P.xy.ridx.lean = P.yx.qidx.lean = iy.lean;      // (the build says what it wrote)
     P.xy.qidx.shared_grid = P.yx.ridx.shared_grid = ix.shared_grid; P.xy.ridx.shared_grid = P.yx.qidx.shared_grid = iy.shared_grid;
-    {   // shared grid + fused sum + float: the staged lane pass (search_brick.h); its per-block partials follow its block size
-        // (measured: 118 us against k_search1_flat's 60.5 on the same shared grid, profiles/r06_flat_aligned_ab.txt -- OFF unless PCU_HIP_BRICK=1)
-        static const bool brick_env_on = getenv("PCU_HIP_BRICK") && atoi(getenv("PCU_HIP_BRICK")) != 0;
-        const bool brick = sizeof(T) == 4 && P.fuse == FUSE_SUM && two_sided && ix.shared_grid && iy.shared_grid && brick_env_on && !c->brick_off;
-        P.xy.brick = P.yx.brick = brick;
-        if (brick) for (int d = 0; d < 2; ++d) { SearchJob<T>& J = d ? P.yx : P.xy; J.n_flat = grid8(J.qidx.n, kBrickNT); P.tail.nflat[d] = J.n_flat; }
-    }
     if (P.fuse == FUSE_ARGMAX) for (int d = 0; d < (two_sided ? 2 : 1); ++d) {       // what the tail needs to resolve a winner: the direction's dataset index and query stream
         const SearchJob<T>& J = d ? P.yx : P.xy;
         P.tail.r_gp[d] = J.ridx.gp; P.tail.r_cs[d] = J.ridx.cell_start; P.tail.r_xyz[d] = xyz_of(J.ridx.sorted, J.ridx.n); P.tail.r_idx[d] = idx32_of(J.ridx.sorted, J.ridx.n);
@@ -2265,7 +2189,7 @@ template <typename T>
 static int argmax_enqueue(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, bool two_sided) {
     auto side = [&](const SearchJob<T>& j) {
         const int n = j.qidx.n;
-        return ArgmaxSide<T>{j.out_d, j.row_out ? nullptr : j.qidx.sorted, j.out_i, n, std::min((n + kBlock - 1) / kBlock, kRedBlocksFused)};
+        return ArgmaxSide<T>{j.out_d, j.out_i, n, std::min((n + kBlock - 1) / kBlock, kRedBlocksFused)};
     };
     const ArgmaxSide<T> a = side(P.xy);
     ArgmaxSide<T> b = a; b.n = 0; b.nb = 0;
@@ -2808,16 +2732,10 @@ int pcu_hip_ctx_create(int device, pcu_hip_ctx** out_ctx) {
     c->device = device;
     HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-    {   // The speculative top of the tie-order tree runs beside a call's searches on a stream of its own. PCU_HIP_SPEC_PRIORITY=1 gives it the
-        // highest stream priority: the tree top then ends 0.12 ms after config 3's searches instead of 0.3 -- but the mere existence of a
-        // prioritised stream in the process slows calls that alternate two ordinary streams (config 4: 1.41 -> 1.9-2.1 ms), so it is off.
-        int lo_p = 0, hi_p = 0;
-        const char* e = getenv("PCU_HIP_SPEC_PRIORITY");
-        if (e && atoi(e) != 0 && hipDeviceGetStreamPriorityRange(&lo_p, &hi_p) == hipSuccess && hi_p != lo_p)
-            HIP_TRY(hipStreamCreateWithPriority(&c->spec_stream, hipStreamNonBlocking, hi_p));
-        else
-            HIP_TRY(hipStreamCreateWithFlags(&c->spec_stream, hipStreamNonBlocking));
-    }
+    // The speculative top of the tie-order tree runs beside a call's searches on a stream of its own, at normal priority. (The highest priority
+    // ends the tree top 0.12 ms after config 3's searches instead of 0.3, but the mere existence of a prioritised stream in the process slows
+    // calls that alternate two ordinary streams: config 4 1.41 -> 1.9-2.1 ms.)
+    HIP_TRY(hipStreamCreateWithFlags(&c->spec_stream, hipStreamNonBlocking));
     for (auto& e : c->jev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (auto& e : c->ev) HIP_TRY(hipEventCreate(&e));
     for (auto& e : c->kev) HIP_TRY(hipEventCreate(&e));

@@ -26,7 +26,7 @@ __device__ __forceinline__ void argmax_combine(T& v, long long& i, T v2, long lo
 // partials, the last block to finish folds them, writes {value, i, j} per direction and copies the call's result
 // block to pinned host memory (see k_pnorm_pair).
 template <typename T>
-struct ArgmaxSide { const T* d; const Pt4<T>* qsorted; const long long* corr; int n; int nb; };      // qsorted == nullptr: d / corr are in the caller's ROW order
+struct ArgmaxSide { const T* d; const long long* corr; int n; int nb; };      // d / corr are in the caller's ROW order
 
 template <typename T>
 __device__ __forceinline__ void block_argmax(T& v, long long& idx) {
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(kBlock) void k_argmax_pair(const ArgmaxSide<T> s0, 
     const int bid = second ? (int)blockIdx.x - s0.nb : (int)blockIdx.x;
     T v = -Limits<T>::max_v; long long idx = 0x7fffffffffffffffll;
     for (int i = bid * kBlock + threadIdx.x; i < sd.n; i += sd.nb * kBlock)
-        argmax_combine(v, idx, sd.d[i], ((long long)(sd.qsorted ? (int)sd.qsorted[i].idx : i) << 32) | (long long)i);
+        argmax_combine(v, idx, sd.d[i], ((long long)i << 32) | (long long)i);
     block_argmax(v, idx);
     __shared__ bool s_last;
     if (threadIdx.x == 0) {
@@ -118,7 +118,7 @@ __device__ __forceinline__ double exact_term(const unsigned long long* limbs, co
     const unsigned long long v = __hip_atomic_load(&limbs[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return v ? ldexp((double)v, 32 * l - 1074) : 0.0;
 }
-enum { FUSE_NONE = 0, FUSE_SUM = 1, FUSE_ARGMAX = 2, FUSE_MAXVAL = 3 };      // (MAXVAL: a variant of the lane kernel only -- see FuseTail::maxval; everything else says ARGMAX)
+enum { FUSE_NONE = 0, FUSE_SUM = 1, FUSE_ARGMAX = 2, FUSE_MAXVAL = 3 };      // (MAXVAL: the lane kernel's program for ARGMAX calls -- see FuseTail; everything else says ARGMAX)
 constexpr long long kKeyUnresolved = 1ll << 30;      // FUSE_MAXVAL keys: low word = this bit | the query's position in its cloud's cell order (clouds hold < 2^27 rows)
 constexpr int kTailThreads = 1024;
 // Arguments of k_fuse_tail, the one-block launch that ends a fused call.
@@ -131,12 +131,12 @@ struct FuseTail {
     unsigned long long* limbs[2]; double* special[2];                                          // the wave pass's exact sums
     const int* result_block; int* host_block; unsigned seq;
     int w_sums, w_vals, w_ij, w_tie;             // word offsets of sums[2] / vals / ij[4] / tie[2] inside the result block
-    // Round 6, Hausdorff (FUSE_ARGMAX with maxval != 0): the lane pass ran its VALUE-ONLY program (search.h: FUSE_MAXVAL -- the fused sum's scan with
+    // Round 6, Hausdorff (FUSE_ARGMAX): the lane pass ran its VALUE-ONLY program (search.h: FUSE_MAXVAL -- the fused sum's scan with
     // adoption, about half the cost of the winner-tracking one) and its partials name the arg-max QUERY, not its neighbour: key = source row << 32 |
     // kKeyUnresolved | query position. The one query that wins is resolved here, by this block: it scans the 5 x 5 x 5 cells around the query (the lane
     // pass certified its value inside the 27, or inside these by its radius-2 rescue) in the distance's own arithmetic, takes the minimum, and
     // reports the dataset row -- or, if two records share the minimum, the tie flag, which sends the call to the row-based path as before.
-    int maxval, squared;
+    int squared;
     long long* prof;                             // diagnostics (PCU_HIP_PROF_TAIL): stage times of thread 0, summed over calls; 100 MHz ticks; [7] = calls
     const GridParams<T>* r_gp[2]; const unsigned* r_cs[2]; const T* r_xyz[2]; const int* r_idx[2]; const T* q_xyz[2];
 };
@@ -345,7 +345,7 @@ __device__ __forceinline__ void fuse_tail_body(const FuseTail<T>& ft) {
 #pragma unroll
         for (int jb = 0; jb < 2; ++jb) { win[jb].v = s_fv[jb]; win[jb].k = s_fk[jb]; }
         TAIL_PROF(1);                               // block winners
-        if (ft.maxval) {            // the winners named by a value-only lane pass: their neighbours, both directions side by side
+        {                           // the winners named by the value-only lane pass: their neighbours, both directions side by side
             bool need[2]; unsigned qp[2]; long long j[2]; int tie[2]; T d2[2];
 #pragma unroll
             for (int jb = 0; jb < 2; ++jb) { need[jb] = jb < ft.njobs && (win[jb].k & kKeyUnresolved) && win[jb].v > -(double)Limits<T>::max_v; qp[jb] = (unsigned)(win[jb].k & 0x07ffffffll); }

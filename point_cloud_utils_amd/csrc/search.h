@@ -61,10 +61,8 @@ struct SearchArgs {
                                     // 2 = a one-pass build overflowed a bucket slot (the host rebuilds with the two-pass pipeline)
     int kreq;                       // neighbours requested (<= K)
     int squared;                    // write d2 instead of sqrt(d2)
-    int row_out;                    // 1: result row of a query goes to its ORIGINAL row (k >= 4: rows are >= 48 B, scattering whole
-                                    // rows costs less than a row-order restore pass); 0: to its slot in the queries' cell order
-    T* out_d;                       // (nq_total, kreq) in the queries' CELL order: row qpos belongs to qsorted[qpos]
-    long long* out_i;               // (nq_total, kreq)  (k_unpermute restores the caller's row order when needed)
+    T* out_d;                       // (nq_total, kreq) in the caller's ROW order: a query's result row is its original row (qsorted[qpos].idx)
+    long long* out_i;               // (nq_total, kreq)
     int* unresolved; int* n_unresolved;
     T* ubound;                      // nullable, lane passes: ubound[i] = the k-th best d2 the lane found for unresolved[i] (max_v: fewer than k points) --
                                     // an upper bound of the true one, which lets the wave-per-query pass start with the ball round
@@ -81,9 +79,6 @@ struct SearchArgs {
     int f_accum;                    // FUSE_ARGMAX, later wave-per-query launches of the same call (pcu_hip.hip: fused_continue): combine with the
                                     // slots instead of overwriting them
     int escalate;                   // wave-per-query passes: finish every query inside the launch (box round, then the ball round: k_search_wave)
-    int maxval;                     // fused arg-max: the lane pass runs its value-only variant (FUSE_MAXVAL; k_fuse_tail resolves the winner's neighbour)
-    int brick;                      // 1: query cloud and dataset share ONE grid and the call takes search_brick.h's staged pass (fused sum, float)
-    int* n_fallback;                // ... whose blocks that did not fit their stage count themselves here (pcu_hip.hip: brick feedback)
     const unsigned* cancel_word; unsigned cancel_gen;      // pcu_types.h: cancel_seen (the wave-per-query pass looks between its work items)
     int bad_r, bad_q;               // GridParams::nonfinite flags (grid.h: kNf*) of the dataset / of the query cloud that this operator rejects:
                                     // the passes give up at once and raise bit 2 of the large-bucket flag word (-> ValueError on the host)
@@ -332,9 +327,7 @@ __device__ __forceinline__ double kill_if(double d, bool dead) {
 }
 // Certification, output and list appends of one lane (shared by the gather and the LDS-tile main passes).
 // `valid` is false for padding lanes of a partial wave (they only take part in the wave-wide list appends).
-// POS: the ids in bi[] are record positions in the dataset's cell order (k_search_runs reads the coordinates-only stream, which has no row ids);
-// the rows are looked up here, once, for the kreq best.
-template <typename T, int K, bool POS = false>
+template <typename T, int K>
 __device__ __forceinline__ void finish_lane(const SearchArgs<T>& a, const GridParams<T>& g, const Pt4<T>& q, int qpos,
                                             int x0, int x1, int y0, int y1, int z0, int z1, T (&bd)[K], int (&bi)[K], bool tie, bool valid,
                                             bool defer = false) {
@@ -351,12 +344,12 @@ __device__ __forceinline__ void finish_lane(const SearchArgs<T>& a, const GridPa
     const bool certified = valid && kth < lb;
 
     if (certified) {
-        const size_t o = (size_t)(a.row_out ? (int)q.idx : qpos) * (size_t)kreq;       // cell order (coalesced rows; see k_unpermute) unless row_out
+        const size_t o = (size_t)(int)q.idx * (size_t)kreq;       // the query's own row
 #pragma unroll
         for (int i = 0; i < K; ++i) {
             if (i < kreq) {
                 const bool found = bi[i] != 0x7fffffff;
-                a.out_i[o + i] = found ? (long long)(POS ? a.ref_idx[bi[i]] : bi[i]) : -1ll;
+                a.out_i[o + i] = found ? (long long)bi[i] : -1ll;
                 a.out_d[o + i] = found ? (a.squared ? bd[i] : sqrt(bd[i])) : (T)-1;
             }
         }
@@ -377,9 +370,6 @@ __device__ __forceinline__ void finish_lane(const SearchArgs<T>& a, const GridPa
 // together, so a lane exposes ~20 dependent memory latencies instead of ~70.
 #ifndef PCU_KBUF
 #define PCU_KBUF 12
-#endif
-#ifndef PCU_KSEARCH_PIPE
-#define PCU_KSEARCH_PIPE 1
 #endif
 
 // Measured on config 3 (k = 16, 4M-vs-4M; profiles/r03_c3_*): 14.6k VALU + 4.9k SALU + 384 vector-memory instructions per wave at 44 % active
@@ -472,7 +462,7 @@ __global__ __launch_bounds__(kBlock) void k_search(const SearchArgs<T> a) {
         const unsigned e = (defer || bd[K - 1] < rlb[j]) ? rs[j] : re[j];
         // The groups of a row are software-pipelined: the next group's four loads are requested before the current group is evaluated
         // (straight-line, a lane past its row's end re-reads the sentinel), so a wait on memory covers the evaluation and the parking of
-        // a whole group. Before (one group requested and waited for per trip, PCU_KSEARCH_PIPE=0) k_search<float,16> spent 49 % of its
+        // a whole group. With one group requested and waited for per trip, k_search<float,16> spent 49 % of its
         // wave-cycles waiting on memory at 4 waves per SIMD (profiles/r03_c3_*.txt).
         auto load_group = [&](unsigned p, Pt4<T> (&c)[kGroup]) {
 #pragma unroll
@@ -495,7 +485,7 @@ __global__ __launch_bounds__(kBlock) void k_search(const SearchArgs<T> a) {
                 if (__any(cnt > kBuf - kGroup)) flush();
             }
         };
-        if (PCU_KSEARCH_PIPE && K > 1) {
+        if (K > 1) {
             unsigned p = rs[j];
             if (p < e) {
                 Pt4<T> ca[kGroup], cb[kGroup];
@@ -562,14 +552,6 @@ __device__ __forceinline__ int cell_of_query(const GridParams<double>& g, const 
 template <typename T> struct K1Group { static constexpr int n = 4; };     // records per group (8 measured slower: more bytes gathered past the row ends)
 struct __attribute__((packed, aligned(4))) CellStart4 { unsigned v[4]; };
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float dist2_k1(const Pt4<float>& q, const Pt4<float>& c) {
-    const f32x2 qxy = {q.x, q.y}, cxy = {c.x, c.y};
-    const f32x2 d = qxy - cxy;
-    const f32x2 dd = d * d;
-    const float dz = q.z - c.z;
-    return (dd.x + dd.y) + (dz * dz);
-}
-__device__ __forceinline__ double dist2_k1(const Pt4<double>& q, const Pt4<double>& c) { return dist2(q, c); }
 __device__ __forceinline__ float min4(float a, float b, float c, float d) { return __builtin_fminf(__builtin_fminf(__builtin_fminf(a, b), c), d); }
 __device__ __forceinline__ double min4(double a, double b, double c, double d) { return __builtin_fmin(__builtin_fmin(a, b), __builtin_fmin(c, d)); }
 
@@ -577,20 +559,15 @@ __device__ __forceinline__ unsigned lb_pack(float lb) { return __float_as_uint(l
 __device__ __forceinline__ unsigned lb_pack(double lb) { const double v = lb * (1.0 - 1e-6); return __float_as_uint((float)(v < 1e38 ? v : 1e38)) >> 16; }
 template <typename T> __device__ __forceinline__ T lb_unpack(unsigned b) { return (T)__uint_as_float(b << 16); }
 
-// Variants of the k = 1 main pass (compile-time, A/B-measured on the GPU; profiles/r03_*):
-//   PCU_FLAT_XYZ   candidates are read from a coordinates-only copy of the cell-ordered cloud (GridIndex::xyz: 3 T per record, no
-//                  row id): a group of 4 records is 12 consecutive scalars = THREE 16-byte loads instead of four, and the six
-//                  (x,y) / (z,x) / (y,z) pairs of the group go through the packed-fp32 pipe. A per-lane gather instruction costs
-//                  the CU's L1 / texture-address path ~17-21 cycles whatever its width (profiles/r02_ubench.txt), and that path is
-//                  the kernel's tightest resource, so a quarter fewer instructions in the loops is a quarter less of it. The row id
-//                  of the winner is fetched once, at the end, from the Pt4 records (not at all by the fused Chamfer sum).
+// The k = 1 main pass reads its candidates from a coordinates-only copy of the cell-ordered cloud (pcu_types.h: xyz_of, 3 T per record, no
+// row id; A/B-measured on the GPU, profiles/r03_*): a group of 4 records is 12 consecutive scalars = THREE 16-byte loads instead of four, and
+// the six (x,y) / (z,x) / (y,z) pairs of the group go through the packed-fp32 pipe. A per-lane gather instruction costs the CU's L1 /
+// texture-address path ~17-21 cycles whatever its width (profiles/r02_ubench.txt), and that path is the kernel's tightest resource, so a
+// quarter fewer instructions in the loops is a quarter less of it. The row id of the winner is fetched once, at the end, from the row-id
+// stream (not at all by the fused Chamfer sum).
 // Measured and rejected in round 3 (profiles/r03_flat_ab.txt): re-dealing the block's 256 queries to its lanes by remaining work after
 // the centre row (LDS counting sort + hand-over of the query state, wave 0 = the 64 heaviest ...): fewer loop trips, but four block
 // barriers in a latency-bound kernel, 80 instead of 72 VGPRs and 25 KB of LDS: 85.9 vs 83.9 us alone, 81.0 vs 78.0 us on top of XYZ.
-#ifndef PCU_FLAT_XYZ
-#define PCU_FLAT_XYZ 1
-#endif
-constexpr bool kFlatXyz = PCU_FLAT_XYZ != 0;
 
 template <typename T> struct __attribute__((packed, aligned(4))) Group12 { T v[12]; };      // 4 records of a coordinates-only stream
 // record index -> byte offset in the candidate stream: shifts and one add (v_mul_lo_u32 is a quarter-rate instruction, and a 24-bit multiply
@@ -607,21 +584,10 @@ template <unsigned REC> __device__ __forceinline__ unsigned rec_bytes(unsigned i
 // a * b + c with 24-bit unsigned factors, one full-rate instruction (the compiler widens the C expression to a 64-bit multiply-add when it cannot prove the ranges)
 __device__ __forceinline__ unsigned mad24(unsigned a, unsigned b, unsigned c) { unsigned r; asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 
-// One group = 4 consecutive records of the candidate stream: `load` requests it (straight-line loads), `dists` gives the 4 squared
+// One group = 4 consecutive records of the coordinates-only stream: `load` requests it (straight-line loads), `dists` gives the 4 squared
 // distances (bit-identical to 4 x dist2: IEEE subtract, multiply, add in the reference's order).
-template <typename T, bool XYZ> struct GroupEval;
-template <typename T> struct GroupEval<T, false> {           // Pt4 records
-    static constexpr unsigned kRec = (unsigned)sizeof(Pt4<T>);
-    struct Raw { Pt4<T> c[4]; };
-    static __device__ __forceinline__ Raw load(const char* base, unsigned off) {
-        const Pt4<T>* c = reinterpret_cast<const Pt4<T>*>(base + (size_t)off);
-        Raw r; r.c[0] = c[0]; r.c[1] = c[1]; r.c[2] = c[2]; r.c[3] = c[3]; return r;
-    }
-    static __device__ __forceinline__ void dists(const Raw& r, const Pt4<T>& q, T (&d)[4]) {
-        d[0] = dist2_k1(q, r.c[0]); d[1] = dist2_k1(q, r.c[1]); d[2] = dist2_k1(q, r.c[2]); d[3] = dist2_k1(q, r.c[3]);
-    }
-};
-template <> struct GroupEval<float, true> {
+template <typename T> struct GroupEval;
+template <> struct GroupEval<float> {
     static constexpr unsigned kRec = 12u;
     typedef Group12<float> Raw;
     static __device__ __forceinline__ Raw load(const char* base, unsigned off) { return *reinterpret_cast<const Raw*>(base + (size_t)off); }
@@ -633,7 +599,7 @@ template <> struct GroupEval<float, true> {
         d[0] = (p0.x + p0.y) + p1.x; d[1] = (p1.y + p2.x) + p2.y; d[2] = (p3.x + p3.y) + p4.x; d[3] = (p4.y + p5.x) + p5.y;
     }
 };
-template <> struct GroupEval<double, true> {
+template <> struct GroupEval<double> {
     static constexpr unsigned kRec = 24u;
     typedef Group12<double> Raw;
     static __device__ __forceinline__ Raw load(const char* base, unsigned off) { return *reinterpret_cast<const Raw*>(base + (size_t)off); }
@@ -651,8 +617,7 @@ template <> struct BitsOf<double> { typedef unsigned long long type; static __de
 // instead of 93, 7 waves per SIMD instead of 5). EARLY = true fetches them right away (79 VGPRs; measured equal).
 template <typename T, bool EARLY, int FUSE>
 __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const int nq_arg, const int bid, const int nblk, bool& f_ok, T& f_v, long long& f_key) {
-    constexpr bool XYZ = kFlatXyz;
-    typedef GroupEval<T, XYZ> GE;
+    typedef GroupEval<T> GE;
     __shared__ uint2 s_rng[8][kBlock];
     const int per = nblk >> 3;
     const int vb = (bid & 7) * per + (bid >> 3);       // XCD-aware block order, see k_search (nblk and the side's first block: multiples of 8)
@@ -677,13 +642,14 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
         q.idx = 0;
     }
     // (FUSE_MAXVAL, round 6: Hausdorff's lane pass on the fused sum's value-only program -- no winner, no tie flags, adoption -- whose partial names
-    // the arg-max QUERY; k_fuse_tail resolves that one query's neighbour, reduce.h: FuseTail::maxval)
+    // the arg-max QUERY; k_fuse_tail resolves that one query's neighbour, reduce.h: FuseTail)
+    static_assert(FUSE != FUSE_ARGMAX, "fused arg-max calls take the value-only program (FUSE_MAXVAL)");
     constexpr bool VALUE_ONLY = FUSE == FUSE_SUM || FUSE == FUSE_MAXVAL;
     const int Gx = g.G[0], Gy = g.G[1], Gz = g.G[2];
     const int ccx = cell_of_query(g, 0, q.x), ccy = cell_of_query(g, 1, q.y), ccz = cell_of_query(g, 2, q.z);
     constexpr unsigned kRec = GE::kRec;               // bytes per record of the candidate stream
     constexpr int kG = K1Group<T>::n;
-    const char* const base = XYZ ? reinterpret_cast<const char*>(a.ref_xyz) : reinterpret_cast<const char*>(a.ref);
+    const char* const base = reinterpret_cast<const char*>(a.ref_xyz);
     const unsigned cand_cap = a.lane_max_cand < 65535u ? a.lane_max_cand : 65535u;     // a run's record count is packed into 16 bits
     T best = Limits<T>::max_v;
     unsigned boff = 0xffffffffu, toff = 0xffffffffu;
@@ -802,9 +768,6 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
     // that has just run out of work fetches the +inf sentinel records once): loads issued under a branch would make the compiler wait
     // for them at the join, i.e. before the older group is evaluated.
     const unsigned sent_off = a.n_ref * kRec;
-#ifndef PCU_ADOPT
-#define PCU_ADOPT 1
-#endif
 #ifndef PCU_ADOPT_T
 #define PCU_ADOPT_T 3
 #endif
@@ -819,7 +782,7 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
     // candidates or a few more (what the owner's shrinking minimum would have skipped), all of them dataset points of the box -- the minimum is
     // the same. Only the fused sum needs no more than the minimum (no winner's row, no tie flags); a wave whose list would not fit, or with
     // exited lanes, goes on lane by lane.
-    if (PCU_ADOPT && VALUE_ONLY) {
+    if (VALUE_ONLY) {
         // (list capacity: with the run list, the block's fold and 8 blocks per CU -- the occupancy the kernel is tuned for -- 160 four-byte items
         // per wave are what fits the 160 KB of LDS; an item = record index of the group (26 bits: clouds of 2^26 records or more go on lane by
         // lane) | owner lane << 26. After three own groups a wave owes ~90 groups on a uniform cloud, 140 at most in the replay.)
@@ -928,9 +891,6 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
         const T hs = hq > (T)0 ? hq * shrink : (T)0;
         lb = hs * hs;
     }
-#ifndef PCU_NO_RESCUE
-#define PCU_NO_RESCUE 0
-#endif
     if (__ballot(valid && !defer && !(best < lb)) != 0ull) {
         const int cx0 = max(ccx - 1, 0), cx1 = min(ccx + 1, Gx - 1);
         const int cy0 = max(ccy - 1, 0), cy1 = min(ccy + 1, Gy - 1), cz0 = max(ccz - 1, 0), cz1 = min(ccz + 1, Gz - 1);
@@ -938,7 +898,7 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
         unsigned long long todo = __ballot(valid && !defer && !(best < lb));
         // (more than a few of them in one wave is not bad luck but the shape of the input -- a query cloud away from the dataset, every lane
         // uncertified: those go to the wave pass, whose rounds are built for it, without 64 futile box scans per wave first)
-        if (!PCU_NO_RESCUE && todo && __popcll(todo) <= 4 && __ballot(true) == ~0ull) {
+        if (todo && __popcll(todo) <= 4 && __ballot(true) == ~0ull) {
             const int lane_ = tid & 63;
             while (todo) {
                 const int l = __ffsll((long long)todo) - 1;
@@ -1002,10 +962,7 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
 #pragma unroll
         for (int u = kG - 1; u >= 0; --u) { const bool eq = d_[u] == best; hits += eq ? 1 : 0; rec_off = eq ? goff + (unsigned)u * kRec : rec_off; }
     };
-    auto row_id = [&](unsigned rec_off) -> int {
-        if (!XYZ) return (int)reinterpret_cast<const Pt4<T>*>(base + (size_t)rec_off)->idx;
-        return a.ref_idx[rec_off / kRec];
-    };
+    auto row_id = [&](unsigned rec_off) -> int { return a.ref_idx[rec_off / kRec]; };
     if (!VALUE_ONLY && boff != 0xffffffffu) {             // (the value-only programs need neither the row id nor the tie flags)
         int hits; unsigned ro;
         which(boff, hits, ro);
@@ -1022,7 +979,7 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
         if (defer) { wave_append(valid, qpos, a.ties, a.n_ties); return; }       // nothing was scanned: the wave-per-query pass at the same radius takes over
         const bool certified = valid && best < lb;
         if (certified) {
-            const size_t o = (size_t)(a.row_out ? a.q_idx[qpos] : qpos) * (size_t)a.kreq;
+            const size_t o = (size_t)a.q_idx[qpos] * (size_t)a.kreq;
             const bool found = bi[0] != 0x7fffffff;
             a.out_i[o] = found ? (long long)bi[0] : -1ll;
             a.out_d[o] = found ? (a.squared ? best : sqrt(best)) : (T)-1;
@@ -1042,9 +999,7 @@ __device__ __forceinline__ void search1_flat_body(const SearchArgs<T>& a, const 
     if (us >= 0 && a.ubound) a.ubound[us] = best;
     f_ok = certified;
     f_v = a.squared ? best : sqrt(best);
-    const long long qrow = FUSE == FUSE_SUM ? 0ll : (long long)a.q_idx[qpos];
-    f_key = FUSE == FUSE_MAXVAL ? ((qrow << 32) | kKeyUnresolved | (long long)qpos)
-                                : ((qrow << 32) | (long long)((unsigned)bi[0] | (tie ? 0x80000000u : 0u)));
+    if (FUSE == FUSE_MAXVAL) f_key = ((long long)a.q_idx[qpos] << 32) | kKeyUnresolved | (long long)qpos;
 }
 // -------------------------------------------------------------------------------------------------------
 // Main pass for k > 1 on an OPEN index (round 5): k_search's scan on the k = 1 kernel's plan. k_search walks the nine rows one after the
@@ -1089,10 +1044,6 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && K == 16) ? PCU_RUNS_MINW
     __shared__ uint2 s_rng[8][kBlock];
     int cnt = 0;
     auto flush = [&]() {
-#ifdef PCU_EXPERIMENT_NOINSERT          /* (scratch experiment: WRONG results; prices the insertion's share of the kernel) */
-        if (cnt > 0) { bd[K - 1] = s_bd[0][tid] < bd[K - 1] ? s_bd[0][tid] : bd[K - 1]; bi[K - 1] = s_bi[0][tid]; }
-        cnt = 0; return;
-#endif
         int mx = cnt;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
@@ -1101,35 +1052,24 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && K == 16) ? PCU_RUNS_MINW
         cnt = 0;
     };
     const unsigned sentinel = a.n_ref;
-#ifndef PCU_RUNS_XYZ
-#define PCU_RUNS_XYZ 0
-#endif
-    // Round 6 (PCU_RUNS_XYZ=1; measured equal to slightly slower on config 3, profiles/r06_c3_ab.txt -- off): candidates from the coordinates-only stream (12 / 24 bytes per record: a group of four = THREE 16-byte gathers instead of
-    // four, and 12 instead of 16 registers per group in flight), as the k = 1 kernel's do; an accepted candidate is parked with its POSITION in
-    // the stream, and the rows of the kreq best are looked up once, at the end (finish_lane<POS>). Slots at or past the run's end e are real
-    // records of the next cells (or the +inf sentinels): their distance is replaced by +inf -- a record offered twice would sit twice in the list.
-    constexpr bool XYZ = PCU_RUNS_XYZ != 0;
-    typedef GroupEval<T, true> GE;
-    struct Grp { typename GE::Raw raw; Pt4<T> c[XYZ ? 1 : kGroup]; unsigned p, e; };
+    // (Candidates from the coordinates-only stream, as the k = 1 kernel reads them -- three 16-byte gathers per group of four instead of four --
+    // measured equal to slightly slower on config 3 in round 6, profiles/r06_c3_ab.txt: the Pt4 records, which carry the row ids.)
+    struct Grp { Pt4<T> c[kGroup]; unsigned p, e; };
     const char* const base = reinterpret_cast<const char*>(a.ref);
-    const char* const xbase = reinterpret_cast<const char*>(a.ref_xyz);
     auto load_group = [&](unsigned p, unsigned e, Grp& gr) {
         gr.p = p; gr.e = e;
-        if (XYZ) { gr.raw = GE::load(xbase, rec_bytes<GE::kRec>(p)); return; }
 #pragma unroll
-        for (int u = 0; u < (XYZ ? 1 : kGroup); ++u) {
+        for (int u = 0; u < kGroup; ++u) {
             const unsigned idx = (p + u < e) ? p + u : sentinel;
             gr.c[u] = *reinterpret_cast<const Pt4<T>*>(base + (size_t)(idx * (unsigned)sizeof(Pt4<T>)));
         }
     };
     auto eval_group = [&](const Grp& gr) {
-        T dd[kGroup];
-        if (XYZ) GE::dists(gr.raw, q, dd);
 #pragma unroll
         for (int u = 0; u < kGroup; ++u) {
-            const T d = XYZ ? kill_if(dd[u], gr.p + (unsigned)u >= gr.e) : dist2(q, gr.c[XYZ ? 0 : u]);
+            const T d = dist2(q, gr.c[u]);
             tie = tie || (d == bd[K - 1]);            // as offer() would flag it (the k-th best may be stale: conservative)
-            if (d < bd[K - 1]) { s_bd[cnt][tid] = d; s_bi[cnt][tid] = XYZ ? (int)(gr.p + (unsigned)u) : (int)gr.c[XYZ ? 0 : u].idx; ++cnt; }
+            if (d < bd[K - 1]) { s_bd[cnt][tid] = d; s_bi[cnt][tid] = (int)gr.c[u].idx; ++cnt; }
         }
         if (__any(cnt > kBuf - kGroup)) flush();
     };
@@ -1247,7 +1187,7 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && K == 16) ? PCU_RUNS_MINW
         }
     }
     if (__any(cnt > 0)) flush();
-    finish_lane<T, K, XYZ>(a, g, q, qpos, max(ccx - 1, 0), min(ccx + 1, Gx - 1), max(ccy - 1, 0), min(ccy + 1, Gy - 1), max(ccz - 1, 0), min(ccz + 1, Gz - 1),
+    finish_lane<T, K>(a, g, q, qpos, max(ccx - 1, 0), min(ccx + 1, Gx - 1), max(ccy - 1, 0), min(ccy + 1, Gy - 1), max(ccz - 1, 0), min(ccz + 1, Gz - 1),
                            bd, bi, tie, true, defer);
 }
 
@@ -1267,7 +1207,7 @@ __global__ __launch_bounds__(kBlock, MINW) void k_search1_flat(const SearchArgs2
     if (FUSE == FUSE_SUM) {                     // one fp64 partial per block; lanes in a fixed order: reproducible
         const double r = block_sum(ok ? (double)v : 0.0);
         if (threadIdx.x == 0) p.a[side].f_sum[bid] = r;
-    } else if (FUSE == FUSE_ARGMAX || FUSE == FUSE_MAXVAL) {           // first maximum by source row (Eigen's maxCoeff visits rows in order, strict '>')
+    } else if (FUSE == FUSE_MAXVAL) {           // first maximum by source row (Eigen's maxCoeff visits rows in order, strict '>')
         T bv = ok ? v : -Limits<T>::max_v; long long bk = ok ? key : 0x7fffffffffffffffll;
         block_argmax(bv, bk);
         if (threadIdx.x == 0) { p.a[side].f_max_v[bid] = bv; p.a[side].f_max_k[bid] = bk; }
@@ -1288,13 +1228,6 @@ __device__ __forceinline__ bool lex_less(T d, int id, T d2, int id2) { return d 
 // (Measured and rejected, rounds 2 and 3: letting the block that finishes last also fold the fused call -- ticket, fuse_tail_body with
 // the block's 256 threads, hand-off to the host -- instead of the separate one-block k_fuse_tail launch: 21.4 us against 9.3 + 7.0 us.
 // The fold then runs strictly after the slowest block on a quarter of the threads; a launch boundary costs less.)
-// (scratch experiments: the wave pass without the subsample bound / without dropping candidates beyond the batch bound)
-#ifndef PCU_NO_SEED
-#define PCU_NO_SEED 0
-#endif
-#ifndef PCU_NO_BOUND_KILL
-#define PCU_NO_BOUND_KILL 0
-#endif
 template <typename T, int K>
 __global__ __launch_bounds__(kBlock) void k_search_wave(const SearchArgs<T> a0, const SearchArgs<T> a1, int njobs, const int n_blocks) {
     const int lane = threadIdx.x & 63;
@@ -1495,7 +1428,7 @@ __global__ __launch_bounds__(kBlock) void k_search_wave(const SearchArgs<T> a0, 
                         const Pt4<T>& c = cc[u];
                         const T dx = q.x - c.x, dy = q.y - c.y, dz = q.z - c.z;
                         const T d = ((dx * dx) + (dy * dy)) + (dz * dz);
-                        take(kill_if(d, (u > 0 && p + (unsigned)u >= le) || (!PCU_NO_BOUND_KILL && d > bound)), (int)c.idx);      // (beyond the bound: never among the k best, see above)
+                        take(kill_if(d, (u > 0 && p + (unsigned)u >= le) || d > bound), (int)c.idx);      // (beyond the bound: never among the k best, see above)
                     }
                 }
                 // heavy rows (a dense cluster next to the query): all 64 lanes stride over the row together, coalesced; every
@@ -1520,7 +1453,7 @@ __global__ __launch_bounds__(kBlock) void k_search_wave(const SearchArgs<T> a0, 
                             const Pt4<T>& c = hc[u];
                             const T dx = q.x - c.x, dy = q.y - c.y, dz = q.z - c.z;
                             const T d = ((dx * dx) + (dy * dy)) + (dz * dz);
-                            take(kill_if(d, (u > 0 && p + 64u * (unsigned)u >= he) || (!PCU_NO_BOUND_KILL && d > bound)), (int)c.idx);
+                            take(kill_if(d, (u > 0 && p + 64u * (unsigned)u >= he) || d > bound), (int)c.idx);
                         }
                     }
                 }
@@ -1571,7 +1504,7 @@ __global__ __launch_bounds__(kBlock) void k_search_wave(const SearchArgs<T> a0, 
             if (certified || !esc) break;
             if (kth < Limits<T>::max_v) ball = kth;                // k points seen: the ball round finishes the query
             else if (x0 == 0 && y0 == 0 && z0 == 0 && x1 == Gx - 1 && y1 == Gy - 1 && z1 == Gz - 1) break;      // (cannot happen on an open grid: its whole box certifies)
-            else if (!seeded && !PCU_NO_SEED) { seed_next = true; seeded = true; }  // fewer than k points in the box: a bound from the subsample first
+            else if (!seeded) { seed_next = true; seeded = true; }  // fewer than k points in the box: a bound from the subsample first
             else R = min(4 * R, 4096);                             // ... then a wider box (whole grid: certified)
         }
         if (certified && a.fuse != FUSE_NONE) {
@@ -1585,13 +1518,13 @@ __global__ __launch_bounds__(kBlock) void k_search_wave(const SearchArgs<T> a0, 
             }
         } else if (certified) {
             if (lane < kreq) {
-                const size_t o = (size_t)(a.row_out ? (int)q.idx : qpos) * (size_t)kreq + lane;
+                const size_t o = (size_t)(int)q.idx * (size_t)kreq + lane;
                 const bool found = my_i != 0x7fffffff;
                 a.out_i[o] = found ? (long long)my_i : -1ll;
                 a.out_d[o] = found ? (a.squared ? my_d : sqrt(my_d)) : (T)-1;
             }
             if (K > 64 && lane + 64 < kreq) {
-                const size_t o = (size_t)(a.row_out ? (int)q.idx : qpos) * (size_t)kreq + lane + 64;
+                const size_t o = (size_t)(int)q.idx * (size_t)kreq + lane + 64;
                 const bool found = my_i2 != 0x7fffffff;
                 a.out_i[o] = found ? (long long)my_i2 : -1ll;
                 a.out_d[o] = found ? (a.squared ? my_d2 : sqrt(my_d2)) : (T)-1;
@@ -1621,52 +1554,11 @@ __global__ __launch_bounds__(kBlock) void k_search_wave(const SearchArgs<T> a0, 
     }
 }
 
-// Restores the caller's row order: out[i, :] = res[pos_of[i], :], pos_of[i] = the slot the index build gave row i. One
-// thread per output element: reads of pos_of and writes of out are coalesced; the cell-ordered result rows are gathered
-// (they were just written and are L2/MALL resident). The main pass therefore writes full coalesced rows instead of
-// scattering 4/8-byte values over the row-ordered arrays (which cost ~5x the algorithmic write traffic,
-// profiles/r01_pmc.txt).
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_unpermute(const unsigned* __restrict__ pos_of, const T* __restrict__ res_d,
-                                                      const long long* __restrict__ res_i, T* __restrict__ out_d,
-                                                      long long* __restrict__ out_i, long long n_elems, int k,
-                                                      const int* __restrict__ result_block, int* host_block, unsigned seq, const int* __restrict__ giveup) {
-    // (block 0's first wave also hands the call's result block -- the search counters, final by now -- to pinned host
-    // memory, sequence word last: see k_pnorm_pair)
-    if (host_block && blockIdx.x == 0 && threadIdx.x < 64) {
-        if (threadIdx.x < 63) host_block[threadIdx.x] = result_block[threadIdx.x];
-        __threadfence_system();
-        if (threadIdx.x == 63) __hip_atomic_store(&host_block[63], (int)seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n_elems) return;
-    // (giveup: the search's skew / unplaced-buckets flags. When the passes gave up there are no rows yet, and pos_of may be
-    // incomplete -- the restore is repeated after the host has dealt with it)
-    if (giveup && (giveup[0] | giveup[kLargeFlag])) return;
-    const long long i = t / k; const int j = (int)(t - i * k);
-    const size_t src = (size_t)pos_of[i] * (size_t)k + j;
-    if (out_d) out_d[t] = res_d[src];
-    if (out_i) out_i[t] = res_i[src];
-}
-
-// The call's result block to pinned host memory (sequence word last), for call shapes without an unpermute launch.
+// The call's result block to pinned host memory (sequence word last), for call shapes without an epilogue launch that does it.
 static __global__ void k_result_block_to_host(const int* __restrict__ result_block, int* host_block, unsigned seq) {
     if (threadIdx.x < 63) host_block[threadIdx.x] = result_block[threadIdx.x];
     __threadfence_system();
     if (threadIdx.x == 63) __hip_atomic_store(&host_block[63], (int)seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// Same for the rows of a list of query slots only (after the tie-order resolver rewrote a handful of rows).
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_unpermute_rows(const int* __restrict__ slots, int n_slots, const Pt4<T>* __restrict__ qsorted,
-                                                           const T* __restrict__ res_d, const long long* __restrict__ res_i,
-                                                           T* __restrict__ out_d, long long* __restrict__ out_i, int k) {
-    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= (long long)n_slots * k) return;
-    const int s = slots[t / k]; const int j = (int)(t % k);
-    const size_t src = (size_t)s * (size_t)k + j, dst = (size_t)qsorted[s].idx * (size_t)k + j;
-    if (out_d) out_d[dst] = res_d[src];
-    if (out_i) out_i[dst] = res_i[src];
 }
 
 }  // namespace pcu

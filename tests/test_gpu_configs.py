@@ -155,19 +155,15 @@ SWITCHES = ["PCU_HIP_TWO_PASS=1", "PCU_HIP_NO_FUSE=1", "PCU_HIP_NO_FUSED_CONTINU
             "PCU_HIP_NO_KD_SPEC=1", "PCU_HIP_NO_RESCALE=1", "PCU_HIP_KD_FULL=1", "PCU_HIP_NO_K1=1", "PCU_HIP_INDEX=atomic",
             "PCU_HIP_SINK_TWO_PASS=1", "PCU_HIP_DEBUG_SKEW=1", "PCU_HIP_NO_ESCALATE=1", "PCU_HIP_GRID_KERNEL=1", "PCU_HIP_REFIT_BASE=1",
             "PCU_HIP_PROF_BUILD=1", "PCU_HIP_PROF_KD=1",
-            # round 4: first form of the one-pass build, Pt4 records for k = 1, cell-order rows + restore for k < 4, wave pass up front in
-            # fused calls, level passes all the way down / one workgroup for the whole tie-order tree, refits one direction at a time
-            "PCU_HIP_BUILD_V1=1", "PCU_HIP_NO_LEAN=1", "PCU_HIP_ROW_OUT_MIN_K=4", "PCU_HIP_FUSED_WAVE=1", "PCU_HIP_KD_FINISH_MAX=0",
-            "PCU_HIP_KD_FINISH_MAX=1000000000", "PCU_HIP_NO_SKEW_OVERLAP=1", "PCU_HIP_SPEC_PRIORITY=1", "PCU_HIP_PROF_BUILD2=1",
-            "PCU_HIP_HOST_PROF=1", "PCU_HIP_DEBUG_POISON=255", "PCU_HIP_NO_WAVE_MERGE=1",
-            # round 5: k > 1 lane pass without the run list (k_search everywhere), the round-4 small-cloud thresholds (wave-per-query below
-            # 16384 queries, atomic build below 32768 points), no SIGINT watch
-            "PCU_HIP_KSEARCH_V1=1", "PCU_HIP_WAVE_ONLY_BELOW=16384", "PCU_HIP_BUCKET_MIN=32768", "PCU_HIP_NO_SIGINT=1",
-            # round 6: every cloud of a two-sided call on its own grid again; the LDS-staged k = 1 pass over the shared grid (search_brick.h)
-            # ... every fused call laid out from its own sample; 2048-point scatter blocks
-            "PCU_HIP_NO_SHARED_GRID=1", "PCU_HIP_BRICK=1", "PCU_HIP_NO_GEO_CACHE=1", "PCU_HIP_BUILD_PTS=2",
-            # ... Hausdorff's lane pass tracking every query's winner (round 5) instead of the value-only program + one resolution in the tail
-            "PCU_HIP_NO_MAXVAL=1"]
+            # round 4: first form of the one-pass build, Pt4 records for k = 1, level passes all the way down / one workgroup for the whole
+            # tie-order tree, refits one direction at a time
+            "PCU_HIP_BUILD_V1=1", "PCU_HIP_NO_LEAN=1", "PCU_HIP_KD_FINISH_MAX=0",
+            "PCU_HIP_KD_FINISH_MAX=1000000000", "PCU_HIP_NO_SKEW_OVERLAP=1", "PCU_HIP_PROF_BUILD2=1",
+            "PCU_HIP_HOST_PROF=1", "PCU_HIP_DEBUG_POISON=255",
+            # round 5: the round-4 small-cloud thresholds (wave-per-query below 16384 queries, atomic build below 32768 points), no SIGINT watch
+            "PCU_HIP_WAVE_ONLY_BELOW=16384", "PCU_HIP_BUCKET_MIN=32768", "PCU_HIP_NO_SIGINT=1",
+            # round 6: every cloud of a two-sided call on its own grid again; every fused call laid out from its own sample
+            "PCU_HIP_NO_SHARED_GRID=1", "PCU_HIP_NO_GEO_CACHE=1"]
 
 
 @pytest.mark.gpu

@@ -11,6 +11,11 @@ from test_disasm import LLVM, _code_object
 FLAT = "_ZN3pcu14k_search1_flatI"
 FUSED_F32 = ["_ZN3pcu14k_search1_flatIfLb0ELi8ELi1EEEvNS_11SearchArgs2IT_EEi",     # <float, false, 8, FUSE_SUM>
              "_ZN3pcu14k_search1_flatIfLb0ELi8ELi3EEEvNS_11SearchArgs2IT_EEi"]     # <float, false, 8, FUSE_MAXVAL>
+# every instantiation the host launches (pcu_hip.hip: launch_search_fast): float and double, rows / fused sum / value-only arg-max
+LAUNCHED = FUSED_F32 + ["_ZN3pcu14k_search1_flatIfLb0ELi4ELi0EEEvNS_11SearchArgs2IT_EEi",     # <float, false, 4, FUSE_NONE>
+                        "_ZN3pcu14k_search1_flatIdLb0ELi4ELi0EEEvNS_11SearchArgs2IT_EEi",     # <double, false, 4, FUSE_NONE>
+                        "_ZN3pcu14k_search1_flatIdLb0ELi4ELi1EEEvNS_11SearchArgs2IT_EEi",     # <double, false, 4, FUSE_SUM>
+                        "_ZN3pcu14k_search1_flatIdLb0ELi4ELi3EEEvNS_11SearchArgs2IT_EEi"]     # <double, false, 4, FUSE_MAXVAL>
 
 
 def _kernel_resources(tmp_path):
@@ -33,9 +38,10 @@ def test_fused_k1_float_kernels_fit_eight_waves_without_scratch(tmp_path):
         assert r["agpr"] == 0 and r["vgpr"] <= 64, (name, r)
 
 
-def test_no_k1_lane_pass_uses_scratch(tmp_path):
+def test_every_launched_k1_lane_pass_is_built_without_scratch(tmp_path):
     res = _kernel_resources(tmp_path)
     flat = {n: r for n, r in res.items() if n.startswith(FLAT)}
-    assert len(flat) >= 8, sorted(flat)                # float and double, every fuse mode the host launches
+    for name in LAUNCHED:
+        assert name in flat, (name, sorted(flat))
     for name, r in flat.items():
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (name, r)
