@@ -189,18 +189,25 @@ def chamfer_distance(x, y, return_index=False, p_norm=2, max_points_per_leaf=10,
 
 # ---- normals: numpy restatement of src/point_cloud_normals.cpp:48-173 on top of a KNN checker ----------
 
-def _orient_filter(normals, dirs, drop_angle_threshold):
-    """:161-169: normal *= sign(normal . dir); drop if acos(normal . dir) > threshold. Returns (normals, keep)."""
+def _orient_filter(normals, dirs, drop_angle_threshold, with_angle=False):
+    """:161-169: normal *= sign(normal . dir); drop if acos(normal . dir) > threshold. Returns (normals, keep[, angle]).
+    (A direction longer than 1 can give a cosine above 1: acos is NaN in the reference and `NaN > threshold` keeps the point; the
+    clip keeps it as well, with angle 0.)"""
     d = np.einsum("ij,ij->i", normals, dirs)
     normals = normals * np.sign(d)[:, None]
-    ang = np.arccos(np.clip(np.einsum("ij,ij->i", normals, dirs), -1.0, 1.0))
+    cos = np.einsum("ij,ij->i", normals, dirs)
+    ang = np.arccos(np.clip(cos, -1.0, 1.0))
+    if with_angle:
+        return normals, ~(ang > drop_angle_threshold), np.where(cos > 1.0 + 1e-12, np.nan, ang)       # (NaN: kept whatever the threshold)
     return normals, ~(ang > drop_angle_threshold)
 
 
-def normals_knn(points, num_neighbors, view_directions=None, drop_angle_threshold=np.pi / 2, max_points_per_leaf=10, kind="port"):
+def normals_knn(points, num_neighbors, view_directions=None, drop_angle_threshold=np.pi / 2, max_points_per_leaf=10, kind="port", fits=False):
     """estimate_local_normal_knn for every point (:115-173): neighbour offsets in the input dtype, widened to double, thin SVD,
     V[:, 2]. Returns (idx, normals (float64, sign as numpy's SVD gives it), gap) where gap = (s1 - s2) / s0 of the kept points'
-    singular values (how well the smallest direction is separated: tests skip ill-conditioned fits)."""
+    singular values (how well the smallest direction is separated: tests skip ill-conditioned fits). With fewer than three
+    neighbours the reference reads V(:, 2) of a thin V out of bounds: there is no reference direction, normals and gap are zero.
+    fits=True appends `info` (see _fit_info): every row that has a fit BEFORE the view filter, its offset matrix A and its angle."""
     p = _prep(points)
     n = p.shape[0]
     _, c = knn(p, p, num_neighbors, True, max_points_per_leaf, kind=kind)
@@ -209,23 +216,36 @@ def normals_knn(points, num_neighbors, view_directions=None, drop_angle_threshol
     _, s, vt = np.linalg.svd(a, full_matrices=False)
     normals = vt[:, 2, :] if vt.shape[1] >= 3 else np.zeros((n, 3))
     gap = (s[:, 1] - s[:, 2]) / np.maximum(s[:, 0], 1e-300) if s.shape[1] >= 3 else np.zeros(n)
+    info = None
+    if fits:
+        rows = np.flatnonzero(ok)
+        info = _fit_info(rows, a[rows], normals[rows], gap[rows])
+    ang = None
     if view_directions is not None and len(view_directions):
-        normals, keep = _orient_filter(normals, np.asarray(view_directions, dtype=np.float64), drop_angle_threshold)
+        normals, keep, ang = _orient_filter(normals, np.asarray(view_directions, dtype=np.float64), drop_angle_threshold, True)
         ok &= keep
     idx = np.flatnonzero(ok)
+    if fits:
+        if ang is not None:
+            info["normals"], info["ang"] = normals[info["rows"]], ang[info["rows"]]
+        return idx, normals[idx], gap[idx], info
     return idx, normals[idx], gap[idx]
 
 
-def normals_ball(points, ball_radius, view_directions=None, drop_angle_threshold=np.pi / 2, min_pts_per_ball=3, weight_function="constant"):
+def normals_ball(points, ball_radius, view_directions=None, drop_angle_threshold=np.pi / 2, min_pts_per_ball=3, weight_function="constant",
+                 rows=None, fits=False):
     """estimate_local_normal_rbf for every point (:48-113), brute force (small clouds only). Members: d2 < T(ball_radius) with
-    d2 = ((dx*dx)+(dy*dy))+(dz*dz) in the input dtype -- nanoflann's RadiusResultSet compares SQUARED distances (:278-283)."""
+    d2 = ((dx*dx)+(dy*dy))+(dz*dz) in the input dtype -- nanoflann's RadiusResultSet compares SQUARED distances (:278-283).
+    rows: only these rows are fitted (a sample of a large cloud); idx then lists the kept ones among them. fits=True: as normals_knn."""
     p = _prep(points)
     n = p.shape[0]
     rad = p.dtype.type(ball_radius)
     normals = np.zeros((n, 3)); gap = np.zeros(n); ok = np.zeros(n, bool)
-    for i in range(n):
-        d = p[i] - p
-        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    mats = []
+    x, y, z = np.ascontiguousarray(p.T)          # (contiguous columns: the brute force is the cost of the tests that use this)
+    for i in (range(n) if rows is None else np.asarray(rows, dtype=np.int64)):
+        dx = x[i] - x; dy = y[i] - y; dz = z[i] - z
+        d2 = (dx * dx + dy * dy) + dz * dz
         m = np.flatnonzero(d2 < rad)
         if len(m) < min_pts_per_ball:
             continue
@@ -237,11 +257,84 @@ def normals_ball(points, ball_radius, view_directions=None, drop_angle_threshold
         a = (p[m] - p[i]).astype(np.float64) * w[:, None]
         _, s, vt = np.linalg.svd(a, full_matrices=False)
         normals[i] = vt[2]; gap[i] = (s[1] - s[2]) / max(s[0], 1e-300); ok[i] = True
+        if fits:
+            mats.append(a)
+    info = None
+    if fits:
+        fr = np.flatnonzero(ok)
+        info = _fit_info(fr, mats, normals[fr], gap[fr])
+    ang = None
     if view_directions is not None and len(view_directions):
-        normals, keep = _orient_filter(normals, np.asarray(view_directions, dtype=np.float64), drop_angle_threshold)
+        normals, keep, ang = _orient_filter(normals, np.asarray(view_directions, dtype=np.float64), drop_angle_threshold, True)
         ok &= keep
     idx = np.flatnonzero(ok)
+    if fits:
+        if ang is not None:
+            info["normals"], info["ang"] = normals[info["rows"]], ang[info["rows"]]
+        return idx, normals[idx], gap[idx], info
     return idx, normals[idx], gap[idx]
+
+
+def _fit_info(rows, mats, normals, gap):
+    """What a test needs to judge EVERY fit, not only the kept, well-separated ones: `rows` = the rows that have a fit before the view
+    filter (ascending), and aligned with them `A` (the weighted offset matrices: an (r, k, 3) array or a list of (m, 3) arrays), the
+    checker's own `normals` (oriented once view directions are given), `gap`, and `ang` (the angle the filter compares, NaN where the cosine is
+    above 1 by more than rounding; None without view directions)."""
+    return {"rows": rows, "A": mats, "normals": normals, "gap": gap, "ang": None}
+
+
+# The residual contract of a plane fit (DESIGN.md section 2): with s0 >= s1 >= s2 the singular values of A (zero-padded when A has
+# fewer than three rows) and n the returned normal,
+#     |A n|^2 <= s2^2 + C 2^-53 s0^2                        float64 clouds,  C = 4 m + 64
+#     |A n|   <= sqrt(s2^2 + C 2^-53 s0^2) + 2^-24 s0       float32 clouds (the double normal rounded to float)
+# and | |n| - 1 | <= 8 2^-53 / 2^-23. A^T A summed in double over m rows carries <= ~3 m 2^-53 s0^2 of error (trace <= 3 s0^2), a
+# backward-stable symmetric eigen-solver adds a small multiple of 2^-53 |A^T A|, the Rayleigh quotient of the computed vector is
+# within twice that of the smallest eigenvalue; rounding n to float moves it by <= 2^-24 in norm. Derived, not tuned to any kernel.
+def fit_residual(A, n):
+    """(|A n|^2, (s0, s1, s2), |n|) of one fit or of a batch (A (..., m, 3), n (..., 3)): the products and sums in np.longdouble,
+    the singular values from numpy's SVD of A itself (not of A^T A), in longdouble for what follows."""
+    A = np.asarray(A, dtype=np.float64)
+    s = np.linalg.svd(A, compute_uv=False)
+    if s.shape[-1] < 3:
+        s = np.concatenate([s, np.zeros(s.shape[:-1] + (3 - s.shape[-1],))], axis=-1)
+    nl = np.asarray(n).astype(np.longdouble)
+    an = (A.astype(np.longdouble) * nl[..., None, :]).sum(-1)
+    return (an * an).sum(-1), s[..., :3].astype(np.longdouble), np.sqrt((nl * nl).sum(-1))
+
+
+def fit_excess(A, n, dtype):
+    """The contract above for the normals n (in the cloud's dtype) of the fits A (an array (r, m, 3) or a list of (m, 3)).
+    Returns (ok, excess, zero, norm_err): ok -- residual and length within the contract (for fits without any spread, `zero`: finite, and
+    (0, 0, +-1) exactly, what a V = I SVD of a zero matrix gives); excess -- (|A n|^2 - s2^2) / (2^-53 s0^2) for float64 (contract:
+    <= C = 4 m + 64), (|A n| - sqrt(s2^2 + C 2^-53 s0^2)) / (2^-24 s0) for float32 (contract: <= 1); 0 for `zero` fits; norm_err -- | |n| - 1 |."""
+    f64 = np.dtype(dtype) == np.float64
+    n = np.asarray(n)
+    if isinstance(A, np.ndarray) and A.ndim == 3:
+        r2, s, nn = fit_residual(A, n)
+        m = np.full(len(A), A.shape[1])
+    elif len(A) == 0:
+        r2 = nn = np.zeros(0, np.longdouble); s = np.zeros((0, 3), np.longdouble); m = np.zeros(0, int)
+    else:
+        parts = [fit_residual(a, v) for a, v in zip(A, n)]
+        r2 = np.array([q[0] for q in parts]); s = np.stack([q[1] for q in parts]); nn = np.array([q[2] for q in parts])
+        m = np.array([len(a) for a in A])
+    u53, u24 = np.longdouble(2.0) ** -53, np.longdouble(2.0) ** -24
+    s0, s2 = s[:, 0], s[:, 2]
+    zero = np.asarray(s0 == 0)
+    C = (4 * m + 64).astype(np.longdouble)
+    safe = np.where(zero, np.longdouble(1), s0)
+    if f64:
+        excess = (r2 - s2 * s2) / (u53 * safe * safe)
+        ok = excess <= C
+    else:
+        excess = (np.sqrt(r2) - np.sqrt(s2 * s2 + C * u53 * s0 * s0)) / (u24 * safe)
+        ok = excess <= 1
+    ok = ok & (np.abs(nn - 1) <= (8 * u53 if f64 else 2 * u24))
+    if zero.any():
+        nz = n[zero].astype(np.float64)
+        ok = np.where(zero, False, ok)
+        ok[zero] = (nz[:, 0] == 0) & (nz[:, 1] == 0) & (np.abs(nz[:, 2]) == 1)
+    return np.asarray(ok, dtype=bool), np.where(zero, 0, excess).astype(np.float64), zero, np.abs(nn - 1).astype(np.float64)
 
 
 # ---- SURVEY.md 8f-4: Morton codes, voxel-grid downsampling, duplicate removal ------------------------------------------------

@@ -130,9 +130,27 @@ struct NormalsBallArgs {
     T* out_n; unsigned char* keep;
 };
 
+// The grid build places the records of a cell in the order its atomics were served, which differs from run to run; k_normals_ball adds its members
+// up in scan order, so two equal calls differed in the last bits of their normals, and with max_pts_per_ball (every (count / max_pts)-th member in
+// scan order) in the subset itself. This pass copies the records with every cell in ascending row order: the scan order, hence every bit of the
+// result, is then a function of the input alone. One lane per record: its rank among the records of its cell.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_cells_by_row(const GridParams<T>* __restrict__ gp, const Pt4<T>* __restrict__ sorted, const unsigned* __restrict__ cell_start,
+                                                         int n, Pt4<T>* __restrict__ out) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const Pt4<T> q = sorted[t];
+    const unsigned c = cell_linear(*gp, q.x, q.y, q.z);                  // (the build's own arithmetic: 0 <= c < ncells for any value, cell_coord clamps)
+    const unsigned s = min(cell_start[c], (unsigned)n), e = min(cell_start[c + 1], (unsigned)n);
+    unsigned r = s;
+    for (unsigned p = s; p < e; ++p) r += sorted[p].idx < q.idx ? 1u : 0u;
+    if (r < (unsigned)n) out[r] = q;                                     // (r < e: the record itself lies in [s, e) and is not counted)
+}
+
 // One lane per point (in cell order): every point of the cells within reach is tested with the reference's arithmetic
 // (d2 = ((dx*dx)+(dy*dy))+(dz*dz) in T, `d2 < radius`), members are accumulated straight into A^T A. The reference sorts a
-// neighbourhood by distance before the SVD; the order only changes the rounding of the sums (documented tolerance).
+// neighbourhood by distance before the SVD; the order only changes the rounding of the sums (documented tolerance). `sorted` is the
+// copy k_cells_by_row made: cells in grid order, rows ascending inside a cell.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_normals_ball(const NormalsBallArgs<T> a) {
     const int t = blockIdx.x * kBlock + threadIdx.x;

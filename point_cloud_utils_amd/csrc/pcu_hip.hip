@@ -2516,13 +2516,15 @@ static int normals_ball_impl(pcu_hip_ctx* c, const T* points, int64_t n, const T
     if (st) memset(st, 0, sizeof *st);
     c->time_phases = false; c->time_kernels = false;
     const double occ = 8.0;
-    size_t need = index_bytes<T>(n, occ) + 8192;
+    size_t need = index_bytes<T>(n, occ) + align_up((size_t)n * sizeof(Pt4<T>), 256) + 8192;
     if (!on_dev) need += 3 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n, 256);
     if (ctx_begin(c, need)) return PCU_HIP_ERR_RUNTIME;
     Arena ar{c};
     int rc = 0;
     do {
         const T *d_pts, *d_dirs = dirs;
+        Pt4<T>* by_row = nullptr;
+        if ((rc = aalloc(ar, &by_row, (size_t)n))) break;
         if ((rc = stage_in(ar, points, n, on_dev, s, &d_pts))) break;
         if (dirs && (rc = stage_in(ar, dirs, n, on_dev, s, &d_dirs))) break;
         T* d_out = out_n; uint8_t* d_keep = out_keep;
@@ -2532,8 +2534,13 @@ static int normals_ball_impl(pcu_hip_ctx* c, const T* points, int64_t n, const T
         const T radius_t = (T)ball_radius;                          // RadiusResultSet<DistanceType = T>(radius, ...)
         gi.h_want = sqrt((double)radius_t) / 1.98;                  // cells of about half the true search radius: 5^3 cells per point
         if ((rc = index_build(gi, d_pts, occ, s))) break;
+        // the rule of every searched cloud (nonfinite_error): NaN, or +inf and -inf along one axis, is refused -- the reference's tree over such a cloud
+        // has no stable answer. A row with single-signed infinities stays: its d2 is +inf or NaN against every row (itself included), so it is nobody's
+        // member, it has no members and is dropped, and it sits in a border cell of a grid laid over the finite values (grid.h).
+        if ((rc = check_nonfinite<T>(gi.gp, kNfNaN | kNfBothInf, s))) break;
         if (st) { st->n_grid_builds = 1; st->n_queries = n; st->n_passes = 1; }
-        const NormalsBallArgs<T> a{gi.gp, gi.sorted, gi.cell_start, d_dirs, (int)n, radius_t, ball_radius, min_pts, max_pts, weight_rbf, drop, d_out, d_keep};
+        hipLaunchKernelGGL(k_cells_by_row<T>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, gi.gp, gi.sorted, gi.cell_start, (int)n, by_row);
+        const NormalsBallArgs<T> a{gi.gp, by_row, gi.cell_start, d_dirs, (int)n, radius_t, ball_radius, min_pts, max_pts, weight_rbf, drop, d_out, d_keep};
         hipLaunchKernelGGL(k_normals_ball<T>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
         HIP_TRY(hipGetLastError());
         if (!on_dev) {

@@ -224,3 +224,195 @@ def test_oracle_norm_order_pinned_to_numpy():
     assert not np.array_equal(np.sqrt(seq), np.linalg.norm(x, axis=-1))
     a, b = rng.random((2, 5, 9)), rng.random((2, 6, 9))
     assert oracle.pairwise_distances_numpy_order(a, b).tobytes() == oracle.pairwise_distances(a, b).tobytes()
+
+
+# ---- normals: the inputs of tests/test_gpu_normals_fits.py and the rule that judges them, held to what they claim without a GPU -------------------
+from oracle import normals_cases as nc
+
+_KNN = nc.knn_cases()
+_BALL = nc.ball_cases()
+
+
+def _knn_kind():
+    oracle.build()
+    return "ref" if oracle.have_ref() else "port"
+
+
+@pytest.mark.parametrize("dtype", nc.DTYPES, ids=["f32", "f64"])
+@pytest.mark.parametrize("case", _KNN, ids=[c[0] for c in _KNN])
+def test_normals_knn_cases_checker_passes_its_own_rule(case, dtype):
+    """The checker's own SVD normal, rounded to the cloud's dtype, meets the residual contract on every fit of every _knn case, and the
+    'separated' cases leave at most 10 % of their fits out of the direction comparison. With fewer than three neighbours there is no
+    checker normal (V(:, 2) of a thin V): the smallest right singular vector of the zero-padded A is used, which is what the contract asks."""
+    _, make, k, leaf, separated = case
+    p = make(dtype)
+    idx0, nrm0, gap, info = oracle.normals_knn(p, k, max_points_per_leaf=leaf, kind=_knn_kind(), fits=True)
+    if k < 3:
+        a = info["A"]
+        nrm0 = np.linalg.svd(np.concatenate([a, np.zeros((len(a), 3 - k, 3))], 1))[2][:, 2, :]
+    if case[0] == "k=n+1":
+        assert len(idx0) == 0
+    elif case[0] != "k=n":
+        assert len(idx0) == len(p)
+    else:
+        assert len(idx0) == 300
+    zero = np.flatnonzero(~np.any(info["A"] != 0, axis=(1, 2)))
+    nrm0[zero] = (0.0, 0.0, 1.0)                   # no spread at all: the V = I answer
+    if case[0] == "duplicates-k4" or case[0] == "duplicates-k8":
+        assert len(zero) == len(p)                 # the tr == 0 early-out is all this case reaches
+    if case[0] == "duplicates-k12":
+        assert len(zero) == 0
+    nc.judge(idx0, nc.unit(nrm0, dtype), idx0, info, dtype, separated=separated)
+
+
+@pytest.mark.parametrize("dtype", nc.DTYPES, ids=["f32", "f64"])
+def test_normals_rule_rejects_wrong_variants(dtype):
+    """The residual contract fails (i) a neighbour swapped for the (k+1)-th, (iv) a Jacobi loop cut to two sweeps, and an index mix-up of the
+    normals; modelled on the CPU: A^T A in neighbour order and the cyclic Jacobi of csrc/normals.h restated in numpy."""
+    p = nc.sheet(2000, dtype)
+    k = 12
+    kind = _knn_kind()
+    idx0, nrm0, gap, info = oracle.normals_knn(p, k, kind=kind, fits=True)
+    _, c = oracle.knn(p, p, k + 1, True, kind=kind)
+    swapped = c[:, list(range(k - 1)) + [k]]
+    a_wrong = (p[swapped] - p[:, None, :]).astype(np.float64)
+    n_wrong = np.linalg.svd(a_wrong)[2][:, 2, :]
+    ok, _, _, _ = oracle.fit_excess(info["A"], nc.unit(n_wrong, dtype), dtype)
+    assert (~ok).mean() > 0.9, (~ok).mean()
+    with pytest.raises(AssertionError, match="residual contract"):
+        nc.judge(idx0, nc.unit(n_wrong, dtype), idx0, info, dtype)
+
+    def jacobi(S, sweeps):
+        a = S / np.trace(S); v = np.eye(3)
+        for _ in range(sweeps):
+            for pi, qi in ((0, 1), (0, 2), (1, 2)):
+                apq = a[pi, qi]
+                if abs(apq) < 1e-300:
+                    continue
+                theta = (a[qi, qi] - a[pi, pi]) / (2.0 * apq)
+                with np.errstate(over="ignore"):
+                    t = (1.0 if theta >= 0 else -1.0) / (abs(theta) + np.sqrt(theta * theta + 1.0))
+                cth = 1.0 / np.sqrt(t * t + 1.0); sth = t * cth
+                J = np.eye(3); J[pi, pi] = cth; J[qi, qi] = cth; J[pi, qi] = sth; J[qi, pi] = -sth
+                a = J.T @ a @ J; v = v @ J
+        return v[:, int(np.argmin(np.diag(a)))]
+
+    A = info["A"][:400]
+    S = np.einsum("nki,nkj->nij", A, A)
+    for sweeps, expect_fail in ((2, True), (8, False)):
+        nj = nc.unit(np.stack([jacobi(s, sweeps) for s in S]), dtype)
+        ok, _, _, _ = oracle.fit_excess(A, nj, dtype)
+        assert (not ok.all()) == expect_fail, (sweeps, int((~ok).sum()))
+    with pytest.raises(AssertionError, match="residual contract"):       # normals written at the wrong rows
+        nc.judge(idx0, nc.unit(np.roll(nrm0, 1, axis=0), dtype), idx0, info, dtype)
+    with pytest.raises(AssertionError, match="kept rows differ"):
+        nc.judge(idx0[1:], nc.unit(nrm0[1:], dtype), idx0, info, dtype)
+
+
+@pytest.mark.parametrize("dtype", nc.DTYPES, ids=["f32", "f64"])
+@pytest.mark.parametrize("k", [4, 5])
+def test_normals_lattice_tells_leaf_sizes_apart(dtype, k):
+    """(v) max_points_per_leaf not forwarded: on the displaced lattice the leaf-33 answer breaks the contract against the leaf-1 matrices on at
+    least 100 rows, while each answer passes against its own (test_normals_knn_cases_checker_passes_its_own_rule)."""
+    p = nc.lattice(dtype, displaced=True)
+    kind = _knn_kind()
+    _, _, _, i1 = oracle.normals_knn(p, k, max_points_per_leaf=1, kind=kind, fits=True)
+    _, n33, _, _ = oracle.normals_knn(p, k, max_points_per_leaf=33, kind=kind, fits=True)
+    ok, _, _, _ = oracle.fit_excess(i1["A"], nc.unit(n33, dtype), dtype)
+    assert (~ok).sum() >= 100, int((~ok).sum())
+
+
+@pytest.mark.parametrize("dtype", nc.DTYPES, ids=["f32", "f64"])
+def test_normals_scaling_case_is_exact(dtype):
+    """The scaled clouds of the bit-identity case: scaling by 2^+-e is exact, no non-zero squared coordinate difference leaves the normal
+    range, and the checker's own neighbour rows do not change."""
+    p = nc.sheet_on_lattice(5000, dtype)
+    e = nc.SCALE_EXP[dtype]
+    tiny = np.finfo(dtype).tiny
+    _, c0 = oracle.knn(p, p, 12, True, kind=_knn_kind())
+    for sgn in (1, -1):
+        q = (p * dtype(2.0) ** (sgn * e)).astype(dtype)
+        assert np.array_equal(q.astype(np.longdouble), p.astype(np.longdouble) * np.longdouble(2.0) ** (sgn * e))
+        for j in range(3):
+            d = np.diff(np.sort(q[:, j])); d = d[d > 0]
+            assert d.min() * d.min() >= tiny and np.isfinite((q[:, j].max() - q[:, j].min()) ** 2 * 3)
+        _, c1 = oracle.knn(q, q, 12, True, kind=_knn_kind())
+        assert np.array_equal(c0, c1)
+    idx0, _, gap, _ = oracle.normals_knn(p, 12, kind=_knn_kind(), fits=True)
+    assert nc.unseparated_share(gap) <= 0.10
+
+
+@pytest.mark.parametrize("dtype", nc.DTYPES, ids=["f32", "f64"])
+def test_normals_view_direction_cases(dtype):
+    """Per-row view directions: at most 1e-3 of the rows lie within 1e-6 rad of a threshold (judged by the checker alone), every threshold keeps
+    and drops rows of every kind the case claims, and an answer computed with the directions of the wrong rows is refused."""
+    p = nc.sheet(3000, dtype)
+    dirs = nc.view_directions(len(p), dtype)
+    for thr in nc.THRESHOLDS:
+        idx0, nrm0, gap, info = oracle.normals_knn(p, 12, view_directions=dirs, drop_angle_threshold=thr, kind=_knn_kind(), fits=True)
+        assert nc.ambiguous_share(info, thr, dirs) <= 1e-3
+        kept0 = np.isin(np.arange(0, len(p), 50), idx0)                       # zero directions: angle pi / 2
+        assert kept0.all() if thr == np.pi / 2 else not kept0.any()
+        assert np.isin(np.arange(2, len(p), 50), idx0).any()                  # length 2: cosines above 1 are kept
+        if thr > 0:
+            assert 0.05 < len(idx0) / len(p)
+        nc.judge(idx0, nc.unit(nrm0, dtype), idx0, info, dtype, dirs=dirs, thr=thr, separated=True)
+    thr = nc.THRESHOLDS[1]
+    idx0, nrm0, gap, info = oracle.normals_knn(p, 12, view_directions=dirs, drop_angle_threshold=thr, kind=_knn_kind(), fits=True)
+    idx1, nrm1, _ = oracle.normals_knn(p, 12, view_directions=np.roll(dirs, 1, axis=0), drop_angle_threshold=thr, kind=_knn_kind())     # (iii) dirs[t] for dirs[q.idx]
+    with pytest.raises(AssertionError):
+        nc.judge(idx1, nc.unit(nrm1, dtype), idx0, info, dtype, dirs=dirs, thr=thr, separated=True)
+
+
+@pytest.mark.parametrize("dtype", nc.DTYPES, ids=["f32", "f64"])
+def test_normals_ball_lattice_membership(dtype):
+    """Strict d2 < radius and count >= min_pts on the 12^3 lattice, ball_radius 4.0: the members of an inner point are its 3 x 3 x 3 block (27; the six
+    points at distance 2 are out), so 10^3 rows are kept at min_pts 27 and none at 28; (ii) `<=` would count 33 and keep rows at 28, (vi) `>` for `>=` none at 27.
+    The next radius above 4 in the cloud's dtype admits the six."""
+    p = nc.lattice(dtype, g=12)
+    inner = np.flatnonzero(np.all((p >= 1) & (p <= 10), axis=1))
+    idx27, _, _, info = oracle.normals_ball(p, 4.0, min_pts_per_ball=27, fits=True)
+    assert np.array_equal(idx27, inner) and len(inner) == 1000
+    assert max(len(a) for a in info["A"]) == 27
+    assert len(oracle.normals_ball(p, 4.0, min_pts_per_ball=28)[0]) == 0
+    up = float(np.nextafter(dtype(4), dtype(5)))
+    assert dtype(up) > dtype(4)
+    idx33, _, _, info = oracle.normals_ball(p, up, min_pts_per_ball=28, fits=True)
+    deep = np.flatnonzero(np.all((p >= 2) & (p <= 9), axis=1))
+    assert np.isin(deep, idx33).all() and max(len(a) for a in info["A"]) == 33
+    d2 = ((p[inner[0]] - p) ** 2).sum(1)
+    assert (d2 <= 4).sum() == 33 and (d2 < 4).sum() == 27 and (d2 < 3).sum() == 19
+    assert len(oracle.normals_ball(p, 3.0, min_pts_per_ball=19)[0]) == 1000 and len(oracle.normals_ball(p, 3.0, min_pts_per_ball=20)[0]) == 0
+    flat = nc.lattice(dtype, g=12, flat=True)
+    idx9, n9, _ = oracle.normals_ball(flat, 4.0, min_pts_per_ball=9)
+    assert len(idx9) == 100 and len(oracle.normals_ball(flat, 4.0, min_pts_per_ball=10)[0]) == 0
+    assert np.array_equal(np.abs(n9), np.tile([0.0, 0.0, 1.0], (100, 1)))
+
+
+# (the large sampled cloud once on this side -- float32, constant --; the GPU test runs every combination)
+_BALL_RUNS = [(c, w, t) for c in _BALL for w in ("constant", "rbf") for t in nc.DTYPES if not c[5] or (w == "constant" and t == np.float32)]
+
+
+@pytest.mark.parametrize("case,weight,dtype", _BALL_RUNS, ids=["%s-%s-%s" % (c[0], w, "f32" if t == np.float32 else "f64") for c, w, t in _BALL_RUNS])
+def test_normals_ball_cases_checker_passes_its_own_rule(case, weight, dtype):
+    """As test_normals_knn_cases_checker_passes_its_own_rule, for the _ball table; and rows= gives what the full run gives on those rows."""
+    name, make, radius, min_pts, separated, sample = case
+    p = make(dtype)
+    rows = nc.sample_rows(len(p), sample) if sample else None
+    idx0, nrm0, gap, info = oracle.normals_ball(p, radius, min_pts_per_ball=min_pts, weight_function=weight, rows=rows, fits=True)
+    assert len(idx0) > 0
+    if name == "identical":
+        assert len(idx0) == 50
+        nrm0[:] = (0.0, 0.0, 1.0)
+    if name == "sees-all":
+        assert all(len(a) == len(p) for a in info["A"])
+    if name.endswith("outliers") or name == "one-outlier":
+        assert idx0.max() < 1200 and len(idx0) > 1150              # the far points are dropped
+    nc.judge(idx0, nc.unit(nrm0, dtype), idx0, info, dtype, separated=separated)
+    if sample:                                                     # rows= equals the full run on those rows (a smaller cloud: the full run is the cost)
+        q = nc.sheet(1500, dtype, 5)
+        r = nc.sample_rows(len(q), 200)
+        full = oracle.normals_ball(q, 0.02, min_pts_per_ball=5, weight_function=weight)
+        part = oracle.normals_ball(q, 0.02, min_pts_per_ball=5, weight_function=weight, rows=r)
+        pick = np.isin(full[0], r)
+        assert np.array_equal(part[0], full[0][pick]) and np.array_equal(part[1], full[1][pick]) and np.array_equal(part[2], full[2][pick])
