@@ -163,6 +163,34 @@ def test_oracle_voxel_and_dedup_restatements():
                           np.array([[0.5, 1.5, -0.5], [2.5, -1.5, 0.49999997]], np.float32)[[0, 1]])
 
 
+def test_oracle_voxel_downsample_fast_pinned_to_dict_restatement():
+    """oracle.voxel_downsample_fast (lexsort + np.add.at, for the size sweeps of tests/test_gpu_voxel_edges.py) is bit-equal to the
+    dict restatement of the reference loop: both point dtypes with the other dtype's attributes, signed coordinates, anisotropic
+    voxels, min_points_per_voxel, one voxel holding every point, an empty result."""
+    rng = np.random.default_rng(11)
+
+    def same(p, a, vs, mb, mp=1):
+        v0, a0 = oracle.voxel_downsample(p, a, vs, mb, mp)
+        v1, a1 = oracle.voxel_downsample_fast(p, a, vs, mb, mp)
+        assert v1.dtype == v0.dtype and v1.shape == v0.shape and np.array_equal(v0, v1)
+        if a is None:
+            assert a0 is None and a1 is None
+        else:
+            assert a1.dtype == a0.dtype and a1.shape == a0.shape and np.array_equal(a0, a1)
+        return len(v0)
+
+    for dt, adt in ((np.float32, np.float64), (np.float64, np.float32)):
+        p = ((rng.random((30000, 3)) - 0.5) * 3).astype(dt)                      # signed: negative voxel indices on every axis
+        a = rng.normal(size=(30000, 2)).astype(adt)
+        assert same(p, a, [0.125] * 3, [-0.4, 0.1, -1.0]) > 5000
+        assert same(p, a, (0.3, 0.07, 0.9), [-1.6, -1.6, -1.6]) > 500           # anisotropic
+        assert 0 < same(p, a, [0.125] * 3, [-1.5] * 3, 3) < same(p, a, [0.125] * 3, [-1.5] * 3, 1)
+        assert same(p, None, [0.25] * 3, [-1.5] * 3, 0) == same(p, None, [0.25] * 3, [-1.5] * 3, -4)
+        assert same(p, a, [10.0] * 3, [-2.0] * 3) == 1                           # one voxel holds all 30 000 points
+        assert same(p, a, [0.25] * 3, [-1.5] * 3, 10 ** 6) == 0                  # nothing kept: (0, 3) and (0, 2)
+        assert same(p[:1], a[:1], [0.25] * 3, [-1.5] * 3) == 1
+
+
 def test_oracle_sinkhorn_pinned_to_reference_module_and_golden():
     """The numpy restatement of point_cloud_utils/_sinkhorn.py against tests/golden/sinkhorn.npz (generated from the reference's
     own module) and, where /root/reference exists, against that module itself on fresh inputs: bit-equal (same numpy calls)."""
