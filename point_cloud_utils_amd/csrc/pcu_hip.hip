@@ -54,6 +54,9 @@ static int abi_rc(int rc);
 #define HIP_TRY(x)                                                                              \
     do { hipError_t e_ = (x); if (e_ != hipSuccess)                                             \
         return fail(PCU_HIP_ERR_RUNTIME, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+// PCU_HIP_DEBUG_SKEW=1 (diagnostics), read once like every switch; a macro, so that a site's arguments cost nothing when it is off (two are on every fused call's path)
+static const bool g_debug_skew = getenv("PCU_HIP_DEBUG_SKEW") != nullptr;
+#define DEBUG_SKEW(...) do { if (g_debug_skew) fprintf(stderr, __VA_ARGS__); } while (0)
 
 // ------------------------------------------------------------------------------------------------ cancellation
 // The reference polls PyErr_CheckSignals() per query and per kd-tree node and turns Ctrl-C into KeyboardInterrupt
@@ -542,7 +545,7 @@ static int index_build_pair(GridIndex<T>& a, const T* pa, double occa, GridIndex
             GridGeo<T>* const g0 = reinterpret_cast<GridGeo<T>*>(gc.dev), *const g1 = reinterpret_cast<GridGeo<T>*>(gc.dev + 256);
             s0.geo_out = g0; s1.geo_out = g1;
             if (hit) { s0.geo_in = g0; s1.geo_in = g1; }
-            if (getenv("PCU_HIP_DEBUG_SKEW")) fprintf(stderr, "[layout] handed down: %d (n %d %d, shared %d)\n", (int)hit, a.n, b->n, (int)shared);
+            DEBUG_SKEW("[layout] handed down: %d (n %d %d, shared %d)\n", (int)hit, a.n, b->n, (int)shared);
             // (valid again only when both launches are enqueued, below: a build that fails on the way leaves no claim on memory nobody wrote)
             gc.valid[0] = gc.valid[1] = false;
             geo_arm = occa == occb && a.h_want == b->h_want && a.max_cells == b->max_cells;
@@ -742,7 +745,6 @@ constexpr double kSkewFactor = 32.0;    // dataset grid considered unbalanced wh
 // restarts with the default. Ratios above kSkewFactor still take the refit path. Off when the caller fixes the occupancy
 // (pcu_hip_ctx_set_cell_occupancy), for persistent indexes, and with PCU_HIP_NO_RESCALE.
 constexpr double kRescaleAbove = 6.0, kRescaleBelow = 3.0, kRescaleMax = 8.0;
-constexpr int PCU_RETRY = 1000;         // internal: restart the call (the context's occ_scale changed)
 static bool rescale_enabled(const pcu_hip_ctx* c) { static const bool off = getenv("PCU_HIP_NO_RESCALE") != nullptr; return !off && !(c->occupancy > 0); }
 static double call_occupancy(const pcu_hip_ctx* c, int k, int role) { return c->occupancy > 0 ? c->occupancy : default_occupancy(k) * c->occ_scale[role]; }
 #ifndef PCU_WAVE_BLOCKS
@@ -1397,7 +1399,7 @@ static bool rescale_wanted(pcu_hip_ctx* c, const SearchJob<T>& j, hipStream_t s,
     if (hipMemcpyAsync(&hg, j.ridx.gp, sizeof hg, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
     const double r = (double)hg.sumsq / (double)j.ridx.n / (j.occ + 1.0);
     double& scale = c->occ_scale[j.role];
-    if (getenv("PCU_HIP_DEBUG_SKEW")) fprintf(stderr, "[rescale] cloud %d n=%d occ=%.3f scale=%.3f ratio=%.2f\n", j.role, j.ridx.n, j.occ, scale, r);
+    DEBUG_SKEW("[rescale] cloud %d n=%d occ=%.3f scale=%.3f ratio=%.2f\n", j.role, j.ridx.n, j.occ, scale, r);
     if (scale >= 1.0) {
         if (r > kRescaleAbove && r <= kSkewFactor) { scale = 1.0 / std::min(kRescaleMax, sqrt(r)); return true; }
         return false;
@@ -1415,7 +1417,21 @@ static bool rescale_wanted(pcu_hip_ctx* c, const SearchJob<T>& j, hipStream_t s,
 // DATASET / TARGET cloud with infinities of one sign per axis are never anybody's neighbour. Only a cloud that is searched IN and
 // holds a NaN, or +inf and -inf along one axis, has no stable answer in the reference (its kd-tree bounds become NaN).
 constexpr int kNfHard = kNfNaN | kNfBothInf;
-constexpr int PCU_NONFINITE = -1000;    // internal: a search met non-finite input its operator rejects (the caller words the error)
+// What the finish half of a call did, for its caller to act on. Failures do not travel here: they are the int every function returns
+// (fail(): 0 or < 0), and an outcome means something only next to a 0.
+enum class Outcome {
+    Clean,          // nothing was re-run: what the caller has read back or enqueued stands
+    Redone,         // result rows changed (passes re-run after a rebuild, a refit, on coarser grids; tied rows reordered): dependent reductions are redone
+    Restart,        // nothing was delivered, begin the call again: the context holds another grid resolution (rescale_wanted) or dropped a stale layout (kGeoStale)
+    Refused,        // a search met non-finite input its operator rejects (the caller words the error, or knows a stable answer)
+};
+enum class Fused { Done, Rows, RowsGiven, Restart, Refused };       // where a fused two-sided attempt stands: see fused_ladder
+static int attempt_exit(pcu_hip_ctx* c, int rc) { ctx_end(c); return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0; }      // the foot of every attempt: overflow blocks go, an internal failure becomes an ABI code
+// A call is attempted until an attempt does not end in Outcome::Restart. attempt(restarts, out) returns the call's code.
+template <typename Attempt>
+static int with_restarts(Attempt attempt) {
+    for (int restarts = 0;; ++restarts) { Outcome out = Outcome::Clean; const int rc = attempt(restarts, out); if (out != Outcome::Restart) return rc; }
+}
 static int nonfinite_error(bool metric) {
     if (metric) return fail(PCU_HIP_ERR_INVALID, "Invalid input: a point cloud that is searched in (the target; both clouds of hausdorff_distance / chamfer_distance) "
                             "contains non-finite coordinates: NaN, or both +inf and -inf along one axis. The reference builds its kd-tree over NaN bounds for such data "
@@ -1424,10 +1440,6 @@ static int nonfinite_error(bool metric) {
                 "NaN bounds for such data and returns rows that depend on the traversal; not supported (non-finite query points and single-signed "
                 "infinities in the dataset are handled as the reference handles them).");
 }
-// After the call's single read-back + stream sync: look at the counters; finish whatever is still unresolved with coarser dataset grids
-// (host-driven, one sync per pass; only far-away / isolated queries ever get here).
-// Returns 1 if extra passes ran (callers then redo dependent reductions), 0 if not, 3 if the call is to be restarted (rescale_wanted),
-// <0 on error.
 // Two sub-box levels over the heavy cells (more than 8x the wanted occupancy) of `from`, and once more over what is still heavy in the
 // first (tight clusters inside blobs); the passes then run finest level first.
 template <typename T>
@@ -1448,14 +1460,18 @@ struct SkewPre {
     int hc_redo[C_N]; double hs[2] = {0, 0}; const double* hs_dev = nullptr;
     int d_passes = 0, d_builds = 0;             // what the attempt added to the call's statistics (taken back if it is dropped)
 };
+// After the call's single read-back + stream sync: look at the counters; finish whatever is still unresolved with coarser dataset grids
+// (host-driven, one sync per pass; only far-away / isolated queries ever get here).
+// Returns 0 or the failure; `out` then says what was done: Clean (nothing ran), Redone (extra passes ran or tied rows were rewritten: callers
+// redo dependent reductions), Restart (rescale_wanted: the call is to be begun again), Refused (non-finite input).
 template <typename T>
-static int search_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob<T>& j, pcu_hip_stats* st, const int* hc, SkewPre* pre = nullptr) {
+static int search_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob<T>& j, pcu_hip_stats* st, const int* hc, Outcome& out, SkewPre* pre = nullptr) {
     // hc: host copy of j.sc.counters, read back by the caller together with the call's scalar results
     // (one D2H copy + one stream sync for the whole call in the common case)
     int hc_redo[C_N], hc_large[C_N];
     bool redone = false;
-    if (hc[C_LARGE] & 4) return PCU_NONFINITE;
-    if (getenv("PCU_HIP_DEBUG_SKEW")) fprintf(stderr, "[finish] role=%d n=%d occ=%.3f may=%d skew=%d large=%d u1=%d u2=%d t1=%d\n", j.role, j.ridx.n, j.occ, (int)j.may_rescale, hc[C_SKEW], hc[C_LARGE], hc[C_U1], hc[C_U2], hc[C_T1]);
+    if (hc[C_LARGE] & 4) { out = Outcome::Refused; return 0; }
+    DEBUG_SKEW("[finish] role=%d n=%d occ=%.3f may=%d skew=%d large=%d u1=%d u2=%d t1=%d\n", j.role, j.ridx.n, j.occ, (int)j.may_rescale, hc[C_SKEW], hc[C_LARGE], hc[C_U1], hc[C_U2], hc[C_T1]);
     if (hc[C_LARGE]) {
         // Every pass gave up at once because an index was not ready (GridParams::has_large).
         if (hc[C_LARGE] & 2) {
@@ -1475,7 +1491,7 @@ static int search_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob<T>&
         HIP_WAIT(s);
         hc = hc_large; redone = true;
     }
-    if (hc[C_SKEW] && rescale_wanted(c, j, s, hc[C_SKEW])) return 3;          // 3: restart the call at another grid resolution
+    if (hc[C_SKEW] && rescale_wanted(c, j, s, hc[C_SKEW])) { out = Outcome::Restart; return 0; }          // at another grid resolution
     if (hc[C_SKEW]) {
         // The dataset grid is badly unbalanced (clusters, blobs, a far outlier inflating the bbox): every pass gave up
         // at once. Refit: same cell count over the core range of the cloud (replaces `ridx`), then up to two finer
@@ -1500,7 +1516,7 @@ static int search_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob<T>&
             memcpy(hc_redo, pre->hc_redo, sizeof hc_redo);
             keep_base = pre->hs[1] <= 0.5 * (double)j.ridx.n;
             if (!keep_base && st) { st->n_passes -= pre->d_passes; st->n_grid_builds -= pre->d_builds; }
-            if (getenv("PCU_HIP_DEBUG_SKEW")) fprintf(stderr, "[skew] n=%d heavy points %.0f, level cells %.0f: %s (both directions enqueued together)\n", j.ridx.n, pre->hs[1], pre->hs[0], keep_base ? "grid kept" : "base refit");
+            DEBUG_SKEW("[skew] n=%d heavy points %.0f, level cells %.0f: %s (both directions enqueued together)\n", j.ridx.n, pre->hs[1], pre->hs[0], keep_base ? "grid kept" : "base refit");
         } else if (keep_base) {
             // everything enqueued at once -- both sub-box levels, the passes, the read-back of the heavy-cell statistics next to the counters:
             // ONE host round trip for the direction (the balance metric that brought us here, > 32 x the even value, already says that
@@ -1514,7 +1530,7 @@ static int search_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob<T>&
             HIP_WAIT(s);
             keep_base = hs[1] <= 0.5 * (double)j.ridx.n;
             if (!keep_base && st) *st = before;          // (the attempt is dropped: its builds and passes are not the call's)
-            if (getenv("PCU_HIP_DEBUG_SKEW")) fprintf(stderr, "[skew] n=%d heavy points %.0f, level cells %.0f: %s\n", j.ridx.n, hs[1], hs[0], keep_base ? "grid kept" : "base refit");
+            DEBUG_SKEW("[skew] n=%d heavy points %.0f, level cells %.0f: %s\n", j.ridx.n, hs[1], hs[0], keep_base ? "grid kept" : "base refit");
         }
         if (!keep_base) {
             QuantState<T>* qs = nullptr;
@@ -1532,15 +1548,16 @@ static int search_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob<T>&
             HIP_WAIT(s);
         }
         hc = hc_redo; redone = true;
-        if (getenv("PCU_HIP_DEBUG_SKEW")) fprintf(stderr, "[skew] n=%d lists: after finest %d, after mid %d, after base %d; ties %d\n", j.qidx.n, hc[C_X0], hc[C_X1], hc[C_U1], hc[C_T1]);
+        DEBUG_SKEW("[skew] n=%d lists: after finest %d, after mid %d, after base %d; ties %d\n", j.qidx.n, hc[C_X0], hc[C_X1], hc[C_U1], hc[C_T1]);
     }
     if (st) { st->n_escalated += hc[C_U1]; st->n_tie_flagged += hc[C_T1] + hc[C_TF0] + hc[C_TF1]; }
     int n_left = hc[C_U2];
     if (n_left == 0) {
         if (st) st->n_tie_true += hc[C_TT];
         j.n_tt = hc[C_TT];
-        if (hc[C_TT] > 0 && j.tie_order) { if (tie_order_resolve(c, ar, s, j, hc[C_TT], st)) return -1; return redone ? 1 : 2; }   // 2: only the rows in the tie list changed
-        return redone ? 1 : 0;
+        if (hc[C_TT] > 0 && j.tie_order) { if (tie_order_resolve(c, ar, s, j, hc[C_TT], st)) return -1; redone = true; }     // (only the rows in the tie list changed)
+        out = redone ? Outcome::Redone : Outcome::Clean;
+        return 0;
     }
     const int KL = std::max(2, pow2_at_least(j.k + 1));
     int* cur = j.sc.u2; int* nxt = j.sc.u1;
@@ -1585,7 +1602,8 @@ static int search_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob<T>&
     if (st) st->n_tie_true += tt;
     j.n_tt = tt;
     if (tt > 0 && j.tie_order && tie_order_resolve(c, ar, s, j, tt, st)) return -1;
-    return 1;
+    out = Outcome::Redone;
+    return 0;
 }
 
 // One 256-byte device block per call holds everything the host must read back: both directions' counters and
@@ -1598,6 +1616,9 @@ struct ResultBlock {
     int pad[24];
 };
 static_assert(sizeof(ResultBlock) == 256, "ResultBlock layout");
+// The kernel that copies the block to c->h_pinned stores the call's sequence number (c->seq) into its last word afterwards.
+constexpr int kSeqWord = (int)(sizeof(ResultBlock) / sizeof(int)) - 1;
+static bool result_block_arrived(const pcu_hip_ctx* c) { return (unsigned)*(volatile int*)(c->h_pinned + kSeqWord) == c->seq; }
 
 // ------------------------------------------------------------------------------------------------ validation
 static int validate_sizes(int64_t nq, int64_t nr, const char* qname, const char* rname) {
@@ -1710,14 +1731,32 @@ static int knn_big_k(pcu_hip_ctx* c, const T* query, int64_t nq, const T* datase
         if (herr) { rc = fail(PCU_HIP_ERR_RUNTIME, "internal: kd traversal exceeded the tree depth (%d)", levels); break; }
         if (st) { st->n_queries = nq; st->n_passes = 1; }
     } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+    return attempt_exit(c, rc);
 }
 
-template <typename T> static int job_unlean(hipStream_t s, SearchJob<T>& j);
+// The Pt4 records of two lean indexes (grid2.h), for everything that is not a lean fast path: a k = 1 job's two clouds, or a pair's.
+template <typename T>
+static int unlean(hipStream_t s, GridIndex<T>& ix, GridIndex<T>& iy) {
+    if (!ix.lean && !iy.lean) return 0;
+    const Pt4Side<T> a{ix.sorted, ix.n}, b{iy.sorted, iy.n};
+    const int nb0 = ix.lean ? std::min((ix.n + 8 + kBlock - 1) / kBlock, 2048) : 0, nb1 = iy.lean ? std::min((iy.n + 8 + kBlock - 1) / kBlock, 2048) : 0;
+    hipLaunchKernelGGL(k_make_pt4<T>, dim3(nb0 + nb1), dim3(kBlock), 0, s, a, b, nb0);
+    HIP_TRY(hipGetLastError());
+    ix.lean = iy.lean = false;
+    return 0;
+}
+// k_nearest_neighbors' read-back: the block copied by a kernel, the STREAM waited for (the per-row outputs must be complete, so not for the word
+// alone), the sequence word checked. mark2: the Timer whose mark 2 follows the launch.
+static int result_block_fetch(pcu_hip_ctx* c, hipStream_t s, const ResultBlock* rb, Timer* mark2 = nullptr) {
+    hipLaunchKernelGGL(k_result_block_to_host, dim3(1), dim3(64), 0, s, reinterpret_cast<const int*>(rb), c->h_pinned, ++c->seq); HIP_TRY(hipGetLastError());
+    if (mark2) mark2->mark(2);
+    HIP_WAIT(s);
+    if (!result_block_arrived(c)) return fail(PCU_HIP_ERR_RUNTIME, "internal: the result block did not arrive");
+    return 0;
+}
 template <typename T>
 static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* dataset, int64_t nr, int k, int max_leaf,
-                       T* out_d, int64_t* out_i, unsigned flags, void* stream, pcu_hip_stats* st, const pcu_hip_index* pidx, int restarts) {
+                       T* out_d, int64_t* out_i, unsigned flags, void* stream, pcu_hip_stats* st, const pcu_hip_index* pidx, int restarts, Outcome& out) {
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
     if (pidx) {
         if (pidx->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the index was built for the other floating-point type");
@@ -1770,7 +1809,7 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         job.out_d = dd; job.out_i = di;
         job.leaf_max = max_leaf > 0 ? max_leaf : 10; job.tie_order = !(flags & PCU_HIP_NO_TIE_ORDER);
         {   // k = 1 on a fresh pair of indexes: the lane kernel reads the coordinate and row-id streams only, so the Pt4 records are not
-            // written (grid2.h; 16 MB less per million points); whatever runs after the first read-back fills them in first (job_unlean)
+            // written (grid2.h; 16 MB less per million points); whatever runs after the first read-back fills them in first (unlean)
             static const bool no_lean = getenv("PCU_HIP_NO_LEAN") != nullptr;
             const bool lean = !pidx && !no_lean && lane_k1_job(job) && job.ridx.bucketed && job.qidx.bucketed && job.ridx.one_pass && job.qidx.one_pass;
             job.ridx.lean = job.qidx.lean = lean;
@@ -1784,29 +1823,24 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         const bool lazy_wave = lane_k1_job(job);            // (k = 1: the wave pass only if the lane launch leaves something, see below)
         if ((rc = search_enqueue(c, s, job, st, /*zero_counters=*/false, lazy_wave ? 1 : 3))) break;
         if (spec && (rc = kd_speculate(c, ar, s, job))) break;
-        hipLaunchKernelGGL(k_result_block_to_host, dim3(1), dim3(64), 0, s, reinterpret_cast<const int*>(rb), c->h_pinned, ++c->seq); HIP_TRY(hipGetLastError());
-        tm.mark(2);
-        HIP_WAIT(s);         // the per-row outputs must be complete, so this call waits for the stream, not for the word
-        if ((unsigned)*(volatile int*)(c->h_pinned + 63) != c->seq) { rc = fail(PCU_HIP_ERR_RUNTIME, "internal: the result block did not arrive"); break; }
+        if ((rc = result_block_fetch(c, s, rb, &tm))) break;
         if (job.ridx.lean || job.qidx.lean) {
             const int* hc0 = ((ResultBlock*)c->h_pinned)->counters[0];
             bool clean = true;
             for (int i = 0; i < C_N; ++i) clean = clean && hc0[i] == 0;
-            if (!clean && (rc = job_unlean(s, job))) break;      // stragglers, ties, give-ups: everything from here on may read Pt4 records
+            if (!clean && (rc = unlean(s, job.qidx, job.ridx))) break;      // stragglers, ties, give-ups: everything from here on may read Pt4 records
         }
         if (lazy_wave) {
             const int* hc0 = ((ResultBlock*)c->h_pinned)->counters[0];
             if ((hc0[C_U1] > 0 || hc0[C_T1] > 0) && !hc0[C_SKEW] && !hc0[C_LARGE]) {       // stragglers beyond radius 2, possible ties, deferred lanes: the wave pass now
                 if ((rc = search_enqueue(c, s, job, st, false, 2))) break;
-                hipLaunchKernelGGL(k_result_block_to_host, dim3(1), dim3(64), 0, s, reinterpret_cast<const int*>(rb), c->h_pinned, ++c->seq); HIP_TRY(hipGetLastError());
-                HIP_WAIT(s);
-                if ((unsigned)*(volatile int*)(c->h_pinned + 63) != c->seq) { rc = fail(PCU_HIP_ERR_RUNTIME, "internal: the result block did not arrive"); break; }
+                if ((rc = result_block_fetch(c, s, rb))) break;
             }
         }
-        if ((rc = search_finish(c, ar, s, job, st, ((ResultBlock*)c->h_pinned)->counters[0])) < 0) { if (rc == PCU_NONFINITE) rc = nonfinite_error(false); break; }
-        if (rc == 3) { rc = PCU_RETRY; break; }
-        if (rc > 0) tm.mark(2);
-        rc = 0;
+        if ((rc = search_finish(c, ar, s, job, st, ((ResultBlock*)c->h_pinned)->counters[0], out))) break;
+        if (out == Outcome::Refused) { rc = nonfinite_error(false); break; }
+        if (out == Outcome::Restart) break;
+        if (out != Outcome::Clean) tm.mark(2);
         if (!on_dev) {
             HIP_TRY(hipMemcpyAsync(out_d, dd, (size_t)nq * k * sizeof(T), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipMemcpyAsync(out_i, di, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
@@ -1814,18 +1848,15 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         HIP_WAIT(s);
         if (st) { st->n_queries = nq; st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_total = tm.span(0, 2); collect_kernel_times(c, st); }
     } while (0);
-    kd_speculate_end(c, rc != PCU_RETRY);
-    ctx_end(c);
-    if (rc == PCU_RETRY) return PCU_RETRY;
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+    kd_speculate_end(c, out != Outcome::Restart);
+    return attempt_exit(c, rc);
 }
 template <typename T>
 static int knn_impl(pcu_hip_ctx* c, const T* query, int64_t nq, const T* dataset, int64_t nr, int k, int max_leaf,
                     T* out_d, int64_t* out_i, unsigned flags, void* stream, pcu_hip_stats* st, const pcu_hip_index* pidx = nullptr) {
-    for (int restarts = 0;; ++restarts) {          // (restarts: occupancy rescale, see kRescaleAbove)
-        const int rc = knn_attempt<T>(c, query, nq, dataset, nr, k, max_leaf, out_d, out_i, flags, stream, st, pidx, restarts);
-        if (rc != PCU_RETRY) return rc;
-    }
+    return with_restarts([&](int restarts, Outcome& out) {          // (restarts: occupancy rescale, see kRescaleAbove)
+        return knn_attempt<T>(c, query, nq, dataset, nr, k, max_leaf, out_d, out_i, flags, stream, st, pidx, restarts, out);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ two-sided ops
@@ -1855,6 +1886,19 @@ struct PairState {
     int fuse = FUSE_NONE; FuseTail<T> tail;             // fused attempt (tail: arguments of the launch that ends the call)
     bool wave_pending = false;                          // the fused attempt's wave-per-query pass has not been launched (pair_search_enqueue)
     int* tie_hit = nullptr;
+};
+// A two-sided (or one-sided) k = 1 call between its enqueue half and its finish half. The batch entry points keep one of
+// these in flight per lane (pcu_hip_ctx) so that the short kernels of independent pairs overlap on the GPU.
+template <typename T>
+struct PendingPair {
+    PairState<T> P;
+    Arena ar; Timer tm; hipStream_t s = nullptr;
+    const T *x = nullptr, *y = nullptr; int64_t nx = 0, ny = 0;
+    bool on_dev = false; unsigned flags = 0; pcu_hip_stats* st = nullptr;
+    int restarts = 0;                       // how often this call has been restarted (Outcome::Restart)
+    bool squared = false, two_sided = true; int max_leaf = 10;            // from here on: set by the operator's begin, before pair_begin
+    bool tie_xy = false, tie_yx = false; int fuse_mode = FUSE_NONE;      // tie order resolved for every row of a direction; the fused epilogue to attempt
+    double p_norm = 2.0; int64_t *out_cxy = nullptr, *out_cyx = nullptr;      // chamfer
 };
 template <typename T>
 static size_t pair_bytes(int64_t nx, int64_t ny, double occ_x, double occ_y, bool on_dev) {
@@ -1887,11 +1931,11 @@ static int pair_search_enqueue(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, p
     return 0;
 }
 // The first fold of a lazy fused attempt has arrived: do some queries still need the wave-per-query pass (stragglers beyond radius 2, lanes that
-// deferred next to a heavy cell)? Then run it now, fold again, and wait for that result block.
+// deferred next to a heavy cell)? Then run it now, fold again, and wait for that result block. out: touched only for Fused::Restart.
 template <typename T>
-static int fused_wave_if_needed(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, pcu_hip_stats* st, ResultBlock& host) {
+static int fused_wave_if_needed(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, pcu_hip_stats* st, ResultBlock& host, Fused& out) {
     // The layout handed down from the previous call no longer fits these clouds (grid2.h: kGeoStale; every pass gave up): once more, laid out afresh.
-    if ((host.counters[0][C_LARGE] | (P.two ? host.counters[1][C_LARGE] : 0)) & kGeoStale) { c->geo.valid[0] = c->geo.valid[1] = false; return PCU_RETRY; }
+    if ((host.counters[0][C_LARGE] | (P.two ? host.counters[1][C_LARGE] : 0)) & kGeoStale) { c->geo.valid[0] = c->geo.valid[1] = false; out = Fused::Restart; return 0; }
     if (!P.wave_pending) return 0;
     P.wave_pending = false;
     bool need = false, broken = false;
@@ -1909,15 +1953,16 @@ static int fused_wave_if_needed(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, 
     return 0;
 }
 template <typename T>
-static int pair_setup(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const T* x, int64_t nx, const T* y, int64_t ny, bool on_dev,
-                      bool squared, double occ_x, double occ_y, long long* ext_ixy, long long* ext_iyx, PairState<T>& P, Timer& tm,
-                      pcu_hip_stats* st, bool two_sided, int max_leaf, bool tie_order_xy, bool tie_order_yx, int fuse_mode = FUSE_NONE) {
-    // (ext_ixy / ext_iyx: device arrays of the caller that take the correspondences directly. Result rows of the row-based path are in the
-    // caller's ROW order -- the search kernels write them there, see knn_attempt -- so no row -> slot table is built and no restore pass runs.)
+static int pair_setup(pcu_hip_ctx* c, PendingPair<T>& pp, double occ_x, double occ_y) {
+    PairState<T>& P = pp.P; Arena& ar = pp.ar; Timer& tm = pp.tm; hipStream_t s = pp.s; pcu_hip_stats* st = pp.st;
+    const int64_t nx = pp.nx, ny = pp.ny; const bool two_sided = pp.two_sided, squared = pp.squared; const int fuse_mode = pp.fuse_mode;
+    // (device arrays of the caller take the correspondences directly. Result rows of the row-based path are in the caller's ROW order -- the
+    // search kernels write them there, see knn_attempt -- so no row -> slot table is built and no restore pass runs.)
+    long long* const ext_ixy = pp.on_dev ? (long long*)pp.out_cxy : nullptr; long long* const ext_iyx = pp.on_dev ? (long long*)pp.out_cyx : nullptr;
     P.two = two_sided;
-    P.xy.leaf_max = P.yx.leaf_max = max_leaf > 0 ? max_leaf : 10; P.xy.tie_order = tie_order_xy; P.yx.tie_order = tie_order_yx;
-    if (stage_in(ar, x, nx, on_dev, s, &P.dx)) return -1;
-    if (stage_in(ar, y, ny, on_dev, s, &P.dy)) return -1;
+    P.xy.leaf_max = P.yx.leaf_max = pp.max_leaf > 0 ? pp.max_leaf : 10; P.xy.tie_order = pp.tie_xy; P.yx.tie_order = pp.tie_yx;
+    if (stage_in(ar, pp.x, nx, pp.on_dev, s, &P.dx)) return -1;
+    if (stage_in(ar, pp.y, ny, pp.on_dev, s, &P.dy)) return -1;
     GridIndex<T> ix, iy;
     const bool share = two_sided && shared_grid_wanted(c, nx, ny, occ_x, occ_y);
     const int64_t n_plan = share ? std::max(nx, ny) : 0;
@@ -2011,10 +2056,9 @@ static int pair_setup(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const T* x, int6
 static int wait_result_block(pcu_hip_ctx* c, hipStream_t s) {
     static const bool no_spin = getenv("PCU_HIP_NO_SPIN") != nullptr;
     if (!no_spin && !c->time_phases && !c->time_kernels) {
-        volatile int* flag = c->h_pinned + 63;
         const auto t0 = std::chrono::steady_clock::now();
         for (unsigned it = 0;; ++it) {
-            if ((unsigned)*flag == c->seq) { std::atomic_thread_fence(std::memory_order_acquire); return cancel_requested() ? cancelled(s) : 0; }
+            if (result_block_arrived(c)) { std::atomic_thread_fence(std::memory_order_acquire); return cancel_requested() ? cancelled(s) : 0; }
             if ((it & 0x3ff) == 0x3ff) {
                 if (cancel_requested()) return cancelled(s);
                 if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;   // long call or fault: poll the stream instead
@@ -2022,7 +2066,7 @@ static int wait_result_block(pcu_hip_ctx* c, hipStream_t s) {
         }
     }
     HIP_WAIT(s);
-    if ((unsigned)*(volatile int*)(c->h_pinned + 63) != c->seq) return fail(PCU_HIP_ERR_RUNTIME, "internal: the epilogue kernel did not deliver its result block");
+    if (!result_block_arrived(c)) return fail(PCU_HIP_ERR_RUNTIME, "internal: the epilogue kernel did not deliver its result block");
     return 0;
 }
 // A fused attempt stands when nothing needs the row-based machinery (see the head of this section).
@@ -2044,12 +2088,12 @@ static bool fused_rescale(pcu_hip_ctx* c, hipStream_t s, const PairState<T>& P, 
 }
 // A fused attempt whose only flaw is that some queries are still uncertified after radius 2 (sparse tails, outliers): finish
 // those with the host-driven passes of search_finish -- in fused mode the wave-per-query kernel adds every query it certifies to
-// the direction's exact sum / arg-max slots -- and fold again. Returns 1 if the call is complete (host block refreshed), 0 if
-// the row-based path has to take over, < 0 on error.
+// the direction's exact sum / arg-max slots -- and fold again. out: Fused::Done if the call is complete (host block refreshed),
+// Fused::Rows if the row-based path has to take over.
 template <typename T>
-static int fused_continue(pcu_hip_ctx* c, Arena& ar, hipStream_t s, PairState<T>& P, pcu_hip_stats* st, ResultBlock& host, bool tie_matters) {
+static int fused_continue(pcu_hip_ctx* c, Arena& ar, hipStream_t s, PairState<T>& P, pcu_hip_stats* st, ResultBlock& host, bool tie_matters, Fused& out) {
     static const bool off = getenv("PCU_HIP_NO_FUSED_CONTINUE") != nullptr;
-    if (off) return 0;
+    out = Fused::Rows; if (off) return 0;
     const int nd = P.two ? 2 : 1;
     bool any = false;
     for (int d = 0; d < nd; ++d) {
@@ -2059,38 +2103,22 @@ static int fused_continue(pcu_hip_ctx* c, Arena& ar, hipStream_t s, PairState<T>
     if (!any) return 0;                         // (a tied arg-max row: rows are needed)
     for (int d = 0; d < nd; ++d) {
         if (host.counters[d][C_U2] <= 0) { if (st) { st->n_escalated += host.counters[d][C_U1]; st->n_tie_flagged += host.counters[d][C_T1]; } continue; }
-        const int r = search_finish(c, ar, s, d ? P.yx : P.xy, st, host.counters[d]);
-        if (r < 0) return r;
+        Outcome fin;          // (neither Restart nor Refused can come back: no direction gave up)
+        if (int r = search_finish(c, ar, s, d ? P.yx : P.xy, st, host.counters[d], fin)) return r;
     }
     P.tail.seq = ++c->seq;
     hipLaunchKernelGGL(k_fuse_tail<T>, dim3(1), dim3(kTailThreads), 0, s, P.tail);
     HIP_TRY(hipGetLastError());
     if (wait_result_block(c, s)) return -1;
     memcpy(&host, c->h_pinned, sizeof host);
-    return fused_ok(P, host, tie_matters, /*stragglers_done=*/true) ? 1 : 0;
-}
-// The Pt4 records of a pair's lean indexes (grid2.h), for everything that is not the fused fast path.
-template <typename T>
-static int pair_unlean(hipStream_t s, PairState<T>& P) {
-    GridIndex<T>& ix = P.xy.qidx; GridIndex<T>& iy = P.xy.ridx;
-    if (!ix.lean && !iy.lean) return 0;
-    const Pt4Side<T> a{ix.sorted, ix.n}, b{iy.sorted, iy.n};
-    const int nb0 = ix.lean ? std::min((ix.n + 8 + kBlock - 1) / kBlock, 2048) : 0, nb1 = iy.lean ? std::min((iy.n + 8 + kBlock - 1) / kBlock, 2048) : 0;
-    hipLaunchKernelGGL(k_make_pt4<T>, dim3(nb0 + nb1), dim3(kBlock), 0, s, a, b, nb0);
-    HIP_TRY(hipGetLastError());
-    P.xy.qidx.lean = P.xy.ridx.lean = P.yx.qidx.lean = P.yx.ridx.lean = false;
+    if (fused_ok(P, host, tie_matters, /*stragglers_done=*/true)) out = Fused::Done;
     return 0;
 }
-// The same for a single job (k_nearest_neighbors, k = 1).
+// The Pt4 records of a pair's lean indexes, for everything that is not the fused fast path (both jobs hold copies of the same two indexes).
 template <typename T>
-static int job_unlean(hipStream_t s, SearchJob<T>& j) {
-    GridIndex<T>& ix = j.qidx; GridIndex<T>& iy = j.ridx;
-    if (!ix.lean && !iy.lean) return 0;
-    const Pt4Side<T> a{ix.sorted, ix.n}, b{iy.sorted, iy.n};
-    const int nb0 = ix.lean ? std::min((ix.n + 8 + kBlock - 1) / kBlock, 2048) : 0, nb1 = iy.lean ? std::min((iy.n + 8 + kBlock - 1) / kBlock, 2048) : 0;
-    hipLaunchKernelGGL(k_make_pt4<T>, dim3(nb0 + nb1), dim3(kBlock), 0, s, a, b, nb0);
-    HIP_TRY(hipGetLastError());
-    ix.lean = iy.lean = false;
+static int pair_unlean(hipStream_t s, PairState<T>& P) {
+    if (int rc = unlean(s, P.xy.qidx, P.xy.ridx)) return rc;
+    P.yx.qidx.lean = P.yx.ridx.lean = false;
     return 0;
 }
 // A pass refused non-finite input (counter bit 4): the classification of both clouds (GridParams::nonfinite; [0] = x / source, [1] = y / target).
@@ -2102,15 +2130,6 @@ static int pair_nonfinite_flags(hipStream_t s, const PairState<T>& P, int (&nf)[
     HIP_WAIT(s);
     return 0;
 }
-// ... and is it input the reference answers stably (see nonfinite_error)? Then the jobs take it from here on (row-based path).
-template <typename T>
-static bool pair_nonfinite_ok(PairState<T>& P, const int (&nf)[2]) {
-    if ((nf[1] & kNfHard) || (P.two && (nf[0] & kNfHard))) return false;
-    P.xy.bad_r = P.yx.bad_r = kNfHard; P.xy.bad_q = P.yx.bad_q = 0;
-    return true;
-}
-template <typename T>
-static bool pair_refused_nonfinite(const PairState<T>& P, const ResultBlock& h) { return ((h.counters[0][C_LARGE] | (P.two ? h.counters[1][C_LARGE] : 0)) & 4) != 0; }
 // Redo a fused call's searches through the row-based path (everything the fused attempt left behind is reset).
 template <typename T>
 static int unfuse_and_research(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, pcu_hip_stats* st, bool skip_search = false) {
@@ -2149,18 +2168,16 @@ static int skew_prelaunch(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob<T>
     return 0;
 }
 
-// Sync + finish stragglers. Returns 1 if the epilogue must be re-enqueued, 0 if not, 3 if the call is to be restarted, <0 on error.
+// Wait for the epilogue's result block + finish stragglers. out: Redone if the epilogue must be re-enqueued, Clean if not, Restart / Refused as the
+// first direction that says so. host_given: *host holds the counters to act on (nothing was enqueued since they were read).
 template <typename T>
-static int pair_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, PairState<T>& P, pcu_hip_stats* st, ResultBlock* host, bool copied_by_kernel = false,
-                       bool host_given = false) {
-    if (host_given) {}                          // (*host holds the counters to act on: nothing was enqueued since they were read)
-    else if (!copied_by_kernel) { HIP_TRY(hipMemcpyAsync(c->h_pinned, P.rb, sizeof(ResultBlock), hipMemcpyDeviceToHost, s)); HIP_WAIT(s); }
-    else if (wait_result_block(c, s)) return -1;
+static int pair_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, PairState<T>& P, pcu_hip_stats* st, ResultBlock* host, bool host_given, Outcome& out) {
+    if (!host_given && wait_result_block(c, s)) return -1;
     if (!host_given) memcpy(host, c->h_pinned, sizeof(ResultBlock));
     // Both directions unbalanced (clustered clouds): their refits -- dozens of short launches each -- are enqueued side by side on the
     // context's two streams and share ONE host round trip, instead of one direction after the other (round 3: 2 x 0.8 ms).
     SkewPre pre[2];
-    if (getenv("PCU_HIP_DEBUG_SKEW")) fprintf(stderr, "[pair_finish] two=%d wanted=%d,%d (skew %d,%d large %d,%d may %d,%d scale %.2f,%.2f time %d%d)\n", (int)P.two, (int)skew_prelaunch_wanted(c, P.xy, host->counters[0]), (int)skew_prelaunch_wanted(c, P.yx, host->counters[1]), host->counters[0][C_SKEW], host->counters[1][C_SKEW], host->counters[0][C_LARGE], host->counters[1][C_LARGE], (int)P.xy.may_rescale, (int)P.yx.may_rescale, c->occ_scale[0], c->occ_scale[1], (int)c->time_phases, (int)c->time_kernels);
+    DEBUG_SKEW("[pair_finish] two=%d wanted=%d,%d (skew %d,%d large %d,%d may %d,%d scale %.2f,%.2f time %d%d)\n", (int)P.two, (int)skew_prelaunch_wanted(c, P.xy, host->counters[0]), (int)skew_prelaunch_wanted(c, P.yx, host->counters[1]), host->counters[0][C_SKEW], host->counters[1][C_SKEW], host->counters[0][C_LARGE], host->counters[1][C_LARGE], (int)P.xy.may_rescale, (int)P.yx.may_rescale, c->occ_scale[0], c->occ_scale[1], (int)c->time_phases, (int)c->time_kernels);
     if (P.two && skew_prelaunch_wanted(c, P.xy, host->counters[0]) && skew_prelaunch_wanted(c, P.yx, host->counters[1])) {
         HIP_TRY(hipEventRecord(c->jev[0], s));
         HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->jev[0], 0));
@@ -2177,11 +2194,14 @@ static int pair_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, PairState<T>& P
         HIP_WAIT(s);
         for (int d = 0; d < 2; ++d) { memcpy(pre[d].hs, hp + 16 * d, 16); memcpy(pre[d].hc_redo, hp + 32 + sizeof(int) * C_N * d, sizeof(int) * C_N); }
     }
-    int r1 = search_finish(c, ar, s, P.xy, st, host->counters[0], &pre[0]);
-    if (r1 < 0 || r1 == 3) return r1;
-    int r2 = P.two ? search_finish(c, ar, s, P.yx, st, host->counters[1], &pre[1]) : 0;
-    if (r2 < 0 || r2 == 3) return r2;
-    return (r1 | r2) ? 1 : 0;       // (2 = "only tied rows changed" matters to k_nearest_neighbors only)
+    out = Outcome::Clean;
+    for (int d = 0; d < (P.two ? 2 : 1); ++d) {
+        Outcome dir;
+        if (int rc = search_finish(c, ar, s, d ? P.yx : P.xy, st, host->counters[d], dir, &pre[d])) return rc;
+        if (dir != Outcome::Clean) out = dir;
+        if (out == Outcome::Restart || out == Outcome::Refused) break;
+    }
+    return 0;
 }
 
 // Arg-max epilogue of one or both directions (+ copy of the result block to pinned host memory): one launch.
@@ -2200,75 +2220,93 @@ static int argmax_enqueue(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, bool t
     return 0;
 }
 
-// A two-sided (or one-sided) k = 1 call between its enqueue half and its finish half. The batch entry points keep one of
-// these in flight per lane (pcu_hip_ctx) so that the short kernels of independent pairs overlap on the GPU.
+// The begin half of a two-sided call, the same for every operator (xname / yname: what its Python signature calls the two clouds).
 template <typename T>
-struct PendingPair {
-    PairState<T> P;
-    Arena ar; Timer tm; hipStream_t s = nullptr;
-    const T *x = nullptr, *y = nullptr; int64_t nx = 0, ny = 0;
-    bool on_dev = false, squared = false, two_sided = true;
-    unsigned flags = 0; int max_leaf = 10; pcu_hip_stats* st = nullptr;
-    double p_norm = 2.0; int64_t *out_cxy = nullptr, *out_cyx = nullptr;      // chamfer
-    int restarts = 0;                       // how often this call has been restarted at another grid resolution (PCU_RETRY)
-};
-
-template <typename T>
-static int hausdorff_begin(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int64_t ny, bool two_sided, int max_leaf,
-                           unsigned flags, void* stream, pcu_hip_stats* st, PendingPair<T>& pp) {
+static int pair_begin(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int64_t ny, const char* xname, const char* yname,
+                      unsigned flags, void* stream, pcu_hip_stats* st, PendingPair<T>& pp) {
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
-    if (validate_sizes(nx, ny, "source", "targets")) return PCU_HIP_ERR_INVALID;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE, squared = flags & PCU_HIP_SQUARED;
+    if (validate_sizes(nx, ny, xname, yname)) return PCU_HIP_ERR_INVALID;
+    if (isnan(pp.p_norm)) return fail(PCU_HIP_ERR_INVALID, "p_norm is NaN");          // (Chamfer's exponent; the default elsewhere)
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
     hipStream_t s = (stream || (flags & PCU_HIP_STREAM_GIVEN)) ? (hipStream_t)stream : c->own_stream;
     if (st) { const int builds = pp.restarts ? st->n_grid_builds : 0; memset(st, 0, sizeof *st); st->n_grid_builds = builds; }      // (a restarted call reports the builds of its abandoned attempts too)
     c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = flags & PCU_HIP_TIME_KERNELS;
     const double occ_x = call_occupancy(c, 1, 0), occ_y = call_occupancy(c, 1, 1);
     if (ctx_begin(c, pair_bytes<T>(nx, ny, occ_x, occ_y, on_dev))) return PCU_HIP_ERR_RUNTIME;
     pp.P.allow_rescale = pp.restarts < 2;
-    if (getenv("PCU_HIP_DEBUG_SKEW")) fprintf(stderr, "[pair begin] restarts=%d nx=%lld ny=%lld occ_x=%.3f occ_y=%.3f\n", pp.restarts, (long long)nx, (long long)ny, occ_x, occ_y);
+    DEBUG_SKEW("[pair begin] restarts=%d nx=%lld ny=%lld occ_x=%.3f occ_y=%.3f\n", pp.restarts, (long long)nx, (long long)ny, occ_x, occ_y);
     pp.ar = Arena{c}; pp.tm = Timer{c, s, st}; pp.s = s; pp.x = x; pp.y = y; pp.nx = nx; pp.ny = ny;
-    pp.on_dev = on_dev; pp.squared = squared; pp.two_sided = two_sided; pp.flags = flags; pp.max_leaf = max_leaf; pp.st = st;
-    int rc = pair_setup(c, pp.ar, s, x, nx, y, ny, on_dev, squared, occ_x, occ_y, nullptr, nullptr, pp.P, pp.tm, st, two_sided, max_leaf, false, false, FUSE_ARGMAX);
-    if (rc) { ctx_end(c); return rc < 0 ? rc : PCU_HIP_ERR_RUNTIME; }
+    pp.on_dev = on_dev; pp.flags = flags; pp.st = st;
+    const int rc = pair_setup(c, pp, occ_x, occ_y);
+    g_hprof.mark(2);
+    return rc ? attempt_exit(c, rc) : 0;
+}
+// The finish half of a fused attempt, rung by rung from the wait for its result block to where the call stands: Done (host holds the results), Rows
+// (the row-based path takes over, its searches are enqueued), RowsGiven (... and they are not: rows_finish acts on the counters in host), Restart,
+// Refused (with both clouds' classification flags in nf). tie_matters: a fused arg-max whose winning row has exactly tied neighbours does not stand.
+template <typename T>
+static int fused_ladder(pcu_hip_ctx* c, PendingPair<T>& pp, ResultBlock& host, bool tie_matters, Fused& out, int (&nf)[2]) {
+    PairState<T>& P = pp.P; hipStream_t s = pp.s; pcu_hip_stats* st = pp.st;
+    pp.tm.mark(3);
+    if (int rc = wait_result_block(c, s)) return rc;
+    g_hprof.mark(3);
+    memcpy(&host, c->h_pinned, sizeof host);
+    out = Fused::Rows;
+    if (int rc = fused_wave_if_needed(c, s, P, st, host, out)) return rc;
+    if (out == Fused::Restart) return 0;          // the handed-down layout was stale
+    if ((host.counters[0][C_LARGE] | (P.two ? host.counters[1][C_LARGE] : 0)) & 4) {          // a pass refused non-finite coordinates: row-based, if
+        if (int rc = pair_nonfinite_flags(s, P, nf)) return rc;                                  // the reference answers such input stably (nonfinite_error)
+        if ((nf[1] & kNfHard) || (P.two && (nf[0] & kNfHard))) { out = Fused::Refused; return 0; }
+        P.xy.bad_r = P.yx.bad_r = kNfHard; P.xy.bad_q = P.yx.bad_q = 0;          // (the jobs take it from here on)
+    } else if (fused_ok(P, host, tie_matters)) {           // nothing needs the row-based machinery
+        for (int d = 0; d < (P.two ? 2 : 1); ++d) if (st) { st->n_escalated += host.counters[d][C_U1]; st->n_tie_flagged += host.counters[d][C_T1]; }
+        out = Fused::Done;
+        return 0;
+    } else if (fused_rescale(c, s, P, host)) { out = Fused::Restart; return 0; }        // the balance check failed and another grid resolution is the answer
+    if (int rc = pair_unlean(s, P)) return rc;
+    if (int rc = fused_continue(c, pp.ar, s, P, st, host, tie_matters, out)) return rc;       // only stragglers left: Done (a pass that gave up or refused: Rows at once)
+    if (out == Fused::Done) return 0;
+    const bool skewed = skewed_everywhere(P, host);          // (the same passes would stop at the balance check again: straight to the refit path)
+    out = skewed ? Fused::RowsGiven : Fused::Rows;
+    return unfuse_and_research(c, s, P, st, skewed);
+}
+// The finish half of a row-based call: the operator's epilogue (one launch: its reduction over the result rows + the copy of the result block to
+// pinned host memory), pair_finish, and if that changed rows the epilogue once more, read back the plain way. given (Fused::RowsGiven): no searches
+// were re-run, so a first epilogue has nothing to reduce -- pair_finish acts on the counters in `host` and the epilogue follows in any case.
+template <typename T, typename Epilogue>
+static int rows_finish(pcu_hip_ctx* c, PendingPair<T>& pp, ResultBlock& host, bool given, Epilogue epilogue, Outcome& out) {
+    if (!given) { if (int rc = epilogue()) return rc; pp.tm.mark(3); }
+    if (int rc = pair_finish(c, pp.ar, pp.s, pp.P, pp.st, &host, given, out)) return rc;
+    if (out == Outcome::Restart || out == Outcome::Refused || (out == Outcome::Clean && !given)) return 0;
+    if (int rc = epilogue()) return rc;
+    pp.tm.mark(3);
+    HIP_TRY(hipMemcpyAsync(c->h_pinned, pp.P.rb, sizeof(ResultBlock), hipMemcpyDeviceToHost, pp.s)); HIP_WAIT(pp.s);
+    memcpy(&host, c->h_pinned, sizeof host);
+    out = Outcome::Redone;
     return 0;
 }
+
 template <typename T>
-static int hausdorff_end(pcu_hip_ctx* c, PendingPair<T>& pp, T* out_d, int64_t* out_i, int64_t* out_j) {
+static int hausdorff_begin(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int64_t ny, bool two_sided, int max_leaf,
+                           unsigned flags, void* stream, pcu_hip_stats* st, PendingPair<T>& pp) {
+    pp.squared = flags & PCU_HIP_SQUARED; pp.two_sided = two_sided; pp.max_leaf = max_leaf; pp.fuse_mode = FUSE_ARGMAX;
+    return pair_begin(c, x, nx, y, ny, "source", "targets", flags, stream, st, pp);
+}
+// out (here and in chamfer_end): Restart = nothing was delivered, begin again; anything else = the call is over, with the code returned.
+template <typename T>
+static int hausdorff_end(pcu_hip_ctx* c, PendingPair<T>& pp, T* out_d, int64_t* out_i, int64_t* out_j, Outcome& out) {
     PairState<T>& P = pp.P; Arena& ar = pp.ar; Timer& tm = pp.tm; hipStream_t s = pp.s; pcu_hip_stats* st = pp.st;
-    const bool two_sided = pp.two_sided; const unsigned flags = pp.flags;
-    const bool tie_matters = !(flags & PCU_HIP_NO_TIE_ORDER);
-    int rc = 0;
+    const bool two_sided = pp.two_sided, tie_matters = !(pp.flags & PCU_HIP_NO_TIE_ORDER);
+    auto epilogue = [&] { return argmax_enqueue(c, s, P, two_sided); };
+    int rc = 0; out = Outcome::Clean;
     do {
         ResultBlock host;
-        bool done = false, skewed = false;
-        if (P.fuse) {
-            tm.mark(3);
-            if ((rc = wait_result_block(c, s))) break;
-            memcpy(&host, c->h_pinned, sizeof host);
-            if ((rc = fused_wave_if_needed(c, s, P, st, host))) break;
-            if (pair_refused_nonfinite(P, host)) {          // non-finite coordinates: row-based, if the reference has a stable answer
-                int nf[2];
-                if ((rc = pair_nonfinite_flags(s, P, nf))) break;
-                if (!pair_nonfinite_ok(P, nf)) { rc = nonfinite_error(true); break; }
-                if ((rc = pair_unlean(s, P)) || (rc = unfuse_and_research(c, s, P, st))) break;
-            }
-            else if (fused_ok(P, host, tie_matters)) {
-                for (int d = 0; d < (two_sided ? 2 : 1); ++d) if (st) { st->n_escalated += host.counters[d][C_U1]; st->n_tie_flagged += host.counters[d][C_T1]; }
-                done = true;
-            } else if (fused_rescale(c, s, P, host)) { rc = PCU_RETRY; break; }
-            else if ((rc = pair_unlean(s, P))) break;
-            else if ((rc = fused_continue(c, ar, s, P, st, host, tie_matters)) != 0) { if (rc < 0) break; rc = 0; done = true; }
-            else { skewed = skewed_everywhere(P, host); if ((rc = unfuse_and_research(c, s, P, st, skewed))) break; }
-        }
-        if (!done) {
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                const bool given = attempt == 0 && skewed;       // no searches were re-run: no epilogue to run either, straight to the refit path
-                if (!given && (rc = argmax_enqueue(c, s, P, two_sided))) break;
-                tm.mark(3);
-                if (attempt == 0) { rc = pair_finish(c, ar, s, P, st, &host, /*copied_by_kernel=*/true, given); if (rc == PCU_NONFINITE) rc = nonfinite_error(true); if (given && rc == 0) rc = 1; if (rc == 3) rc = PCU_RETRY; if (rc <= 0 || rc == PCU_RETRY) break; rc = 0; }   // syncs; 1 => redo epilogue
-                else { HIP_TRY(hipMemcpyAsync(c->h_pinned, P.rb, sizeof(ResultBlock), hipMemcpyDeviceToHost, s)); HIP_WAIT(s); memcpy(&host, c->h_pinned, sizeof host); }
-            }
-            if (rc) break;
+        Fused f = Fused::Rows; Outcome fin = Outcome::Clean; int nf[2];          // (a call without a fused attempt is row-based from its begin)
+        if (P.fuse && (rc = fused_ladder(c, pp, host, tie_matters, f, nf))) break;
+        if ((f == Fused::Rows || f == Fused::RowsGiven) && (rc = rows_finish(c, pp, host, f == Fused::RowsGiven, epilogue, fin))) break;
+        if (f == Fused::Restart || fin == Outcome::Restart) { out = Outcome::Restart; break; }
+        if (f == Fused::Refused || fin == Outcome::Refused) { rc = nonfinite_error(true); break; }
+        if (f != Fused::Done) {
             // The value never depends on the order of exact ties, and (i, j) only does if the arg-max source row i itself
             // has tied nearest neighbours: only then is that direction's tie order resolved (kd_order.h) and j re-read.
             // Whether row i is in a direction's true-tie list is checked on the device (one launch, one 4-byte read-back).
@@ -2293,7 +2331,7 @@ static int hausdorff_end(pcu_hip_ctx* c, PendingPair<T>& pp, T* out_d, int64_t* 
                 }
                 if (rc) break;
                 if (redo) {
-                    if ((rc = argmax_enqueue(c, s, P, two_sided))) break;
+                    if ((rc = epilogue())) break;
                     HIP_TRY(hipMemcpyAsync(c->h_pinned, P.rb, sizeof(ResultBlock), hipMemcpyDeviceToHost, s));
                     HIP_WAIT(s);
                     memcpy(&host, c->h_pinned, sizeof host);
@@ -2305,19 +2343,16 @@ static int hausdorff_end(pcu_hip_ctx* c, PendingPair<T>& pp, T* out_d, int64_t* 
         for (int r = 0; r < nres; ++r) { out_d[r] = hv[r]; out_i[r] = hij[2 * r]; out_j[r] = hij[2 * r + 1]; }
         if (st) { st->n_queries = two_sided ? pp.nx + pp.ny : pp.nx; st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_total = tm.span(0, 3); collect_kernel_times(c, st); }
     } while (0);
-    ctx_end(c);
-    if (rc == PCU_RETRY) return PCU_RETRY;
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+    return attempt_exit(c, rc);
 }
 template <typename T>
 static int hausdorff_impl(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int64_t ny, bool two_sided, int max_leaf,
                           T* out_d, int64_t* out_i, int64_t* out_j, unsigned flags, void* stream, pcu_hip_stats* st) {
-    for (int restarts = 0;; ++restarts) {          // (restarts: occupancy rescale, see kRescaleAbove)
+    return with_restarts([&](int restarts, Outcome& out) {
         PendingPair<T> pp; pp.restarts = restarts;
         if (int rc = hausdorff_begin(c, x, nx, y, ny, two_sided, max_leaf, flags, stream, st, pp)) return rc;
-        const int rc = hausdorff_end(c, pp, out_d, out_i, out_j);
-        if (rc != PCU_RETRY) return rc;
-    }
+        return hausdorff_end(c, pp, out_d, out_i, out_j, out);
+    });
 }
 
 static int pcode_of(double p) {
@@ -2332,97 +2367,57 @@ template <typename T>
 static int chamfer_begin(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int64_t ny, double p_norm, int max_leaf,
                          int64_t* out_cxy, int64_t* out_cyx, unsigned flags, void* stream, pcu_hip_stats* st, PendingPair<T>& pp) {
     g_hprof.mark(0);
-    if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
-    if (validate_sizes(nx, ny, "query_points", "dataset_points")) return PCU_HIP_ERR_INVALID;
-    if (isnan(p_norm)) return fail(PCU_HIP_ERR_INVALID, "p_norm is NaN");
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = (stream || (flags & PCU_HIP_STREAM_GIVEN)) ? (hipStream_t)stream : c->own_stream;
-    if (st) { const int builds = pp.restarts ? st->n_grid_builds : 0; memset(st, 0, sizeof *st); st->n_grid_builds = builds; }      // (a restarted call reports the builds of its abandoned attempts too)
-    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = flags & PCU_HIP_TIME_KERNELS;
-    const double occ_x = call_occupancy(c, 1, 0), occ_y = call_occupancy(c, 1, 1);
-    if (ctx_begin(c, pair_bytes<T>(nx, ny, occ_x, occ_y, on_dev))) return PCU_HIP_ERR_RUNTIME;
-    pp.P.allow_rescale = pp.restarts < 2;
-    if (getenv("PCU_HIP_DEBUG_SKEW")) fprintf(stderr, "[pair begin] restarts=%d nx=%lld ny=%lld occ_x=%.3f occ_y=%.3f\n", pp.restarts, (long long)nx, (long long)ny, occ_x, occ_y);
-    pp.ar = Arena{c}; pp.tm = Timer{c, s, st}; pp.s = s; pp.x = x; pp.y = y; pp.nx = nx; pp.ny = ny;
-    pp.on_dev = on_dev; pp.two_sided = true; pp.flags = flags; pp.max_leaf = max_leaf; pp.st = st;
-    pp.p_norm = p_norm; pp.out_cxy = out_cxy; pp.out_cyx = out_cyx;
+    pp.two_sided = true; pp.max_leaf = max_leaf; pp.p_norm = p_norm; pp.out_cxy = out_cxy; pp.out_cyx = out_cyx;
     // Which of two exactly tied neighbours is picked changes a direction's contribution only through the returned
     // indices, or through a p != 2 norm of the difference vector; the p = 2 value is the tied distance itself.
     const bool tie_any = !(flags & PCU_HIP_NO_TIE_ORDER);
-    const bool tie_xy = tie_any && (out_cxy != nullptr || p_norm != 2.0), tie_yx = tie_any && (out_cyx != nullptr || p_norm != 2.0);
+    pp.tie_xy = tie_any && (out_cxy != nullptr || p_norm != 2.0); pp.tie_yx = tie_any && (out_cyx != nullptr || p_norm != 2.0);
     // p = 2 without indices: the value is the sum of the nearest-neighbour distances -> fused epilogue, no result rows
-    const int fuse = (p_norm == 2.0 && !out_cxy && !out_cyx) ? FUSE_SUM : FUSE_NONE;
-    int rc = pair_setup(c, pp.ar, s, x, nx, y, ny, on_dev, /*squared=*/false, occ_x, occ_y, on_dev ? (long long*)out_cxy : nullptr, on_dev ? (long long*)out_cyx : nullptr,
-                        pp.P, pp.tm, st, true, max_leaf, tie_xy, tie_yx, fuse);
-    g_hprof.mark(2);
-    if (rc) { ctx_end(c); return rc < 0 ? rc : PCU_HIP_ERR_RUNTIME; }
-    return 0;
+    pp.fuse_mode = (p_norm == 2.0 && !out_cxy && !out_cyx) ? FUSE_SUM : FUSE_NONE;
+    return pair_begin(c, x, nx, y, ny, "query_points", "dataset_points", flags, stream, st, pp);
 }
 template <typename T>
-static int chamfer_end(pcu_hip_ctx* c, PendingPair<T>& pp, double* out_mean2) {
-    PairState<T>& P = pp.P; Arena& ar = pp.ar; Timer& tm = pp.tm; hipStream_t s = pp.s; pcu_hip_stats* st = pp.st;
+static int chamfer_end(pcu_hip_ctx* c, PendingPair<T>& pp, double* out_mean2, Outcome& out) {
+    PairState<T>& P = pp.P; Timer& tm = pp.tm; hipStream_t s = pp.s; pcu_hip_stats* st = pp.st;
     const int64_t nx = pp.nx, ny = pp.ny; const bool on_dev = pp.on_dev;
     int64_t *out_cxy = pp.out_cxy, *out_cyx = pp.out_cyx; const double p_norm = pp.p_norm;
-    int rc = 0;
+    int rc = 0; out = Outcome::Clean;
     // A NaN coordinate in either cloud makes the reference's value NaN whatever its kd-tree does with it: the row's own term
     // norm(other[corr] - row) is NaN for every corr (__init__.py:112-113), and so are the mean and the sum (:114-115) -- for every ord but 0,
     // which counts NaN as a non-zero. So the VALUE is stable although the correspondences are not: returned as the reference returns it
     // (no indices asked for). Everything else a search refuses (nonfinite_error) has no stable answer.
     bool nan_result = false;
-    auto nan_rule = [&](const int (&nf)[2]) { return ((nf[0] | nf[1]) & kNfNaN) && !out_cxy && !out_cyx && p_norm != 0.0; };
-    auto refused = [&]() -> int {           // a row-based search refused its dataset: the NaN value, or the error
-        int nf[2];
-        if (int r = pair_nonfinite_flags(s, P, nf)) return r;
-        if (nan_rule(nf)) { nan_result = true; return 0; }
+    auto refused = [&](const int (&nf)[2]) -> int {           // a search refused a cloud with these flags: the NaN value, or the error
+        if (((nf[0] | nf[1]) & kNfNaN) && !out_cxy && !out_cyx && p_norm != 0.0) { nan_result = true; return 0; }
         return nonfinite_error(true);
     };
     do {
         ResultBlock host;
-        bool done = false, skewed = false;
-        if (P.fuse) {
-            tm.mark(3);
-            if ((rc = wait_result_block(c, s))) break;
-            g_hprof.mark(3);
-            memcpy(&host, c->h_pinned, sizeof host);
-            if ((rc = fused_wave_if_needed(c, s, P, st, host))) break;
-            if (pair_refused_nonfinite(P, host)) {          // non-finite coordinates: see below (nan_rule) and hausdorff_end
-                int nf[2];
-                if ((rc = pair_nonfinite_flags(s, P, nf))) break;
-                if (!pair_nonfinite_ok(P, nf)) { if (nan_rule(nf)) { rc = 0; nan_result = true; } else rc = nonfinite_error(true); break; }
-                if ((rc = pair_unlean(s, P)) || (rc = unfuse_and_research(c, s, P, st))) break;
-            }
-            else if (fused_ok(P, host, false)) {
-                for (int d = 0; d < 2; ++d) if (st) { st->n_escalated += host.counters[d][C_U1]; st->n_tie_flagged += host.counters[d][C_T1]; }
-                done = true;
-            } else if (fused_rescale(c, s, P, host)) { rc = PCU_RETRY; break; }
-            else if ((rc = pair_unlean(s, P))) break;
-            else if ((rc = fused_continue(c, ar, s, P, st, host, false)) != 0) { if (rc < 0) break; rc = 0; done = true; }
-            else { skewed = skewed_everywhere(P, host); if ((rc = unfuse_and_research(c, s, P, st, skewed))) break; }
-        }
-        if (!done) {
+        Fused f = Fused::Rows; Outcome fin = Outcome::Clean; int nf[2];          // (a call without a fused attempt is row-based from its begin)
+        if (P.fuse && (rc = fused_ladder(c, pp, host, /*tie_matters=*/false, f, nf))) break;
+        if (f == Fused::Rows || f == Fused::RowsGiven) {
             const int pc = pcode_of(p_norm);
             // __init__.py:112: norm(x[corrs_y_to_x] - y).mean() -> queries y, targets x ; :113 the other way round
             const int nbx = std::min((int)((nx + kBlock - 1) / kBlock), kRedBlocksFused), nby = std::min((int)((ny + kBlock - 1) / kBlock), kRedBlocksFused);
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                const bool given = attempt == 0 && skewed;       // no searches were re-run: no epilogue to run either, straight to the refit path
-                if (given) { rc = pair_finish(c, ar, s, P, st, &host, true, true); if (rc == PCU_NONFINITE) { rc = refused(); break; } if (rc == 0) rc = 1; if (rc == 3) rc = PCU_RETRY; if (rc <= 0 || rc == PCU_RETRY) break; rc = 0; continue; }
-                // both directions' norms + final sums + the copy of the result block to pinned host memory: one launch
-                // (the rows are in the caller's row order: the queries are the clouds themselves)
+            // both directions' norms + final sums + the copy of the result block to pinned host memory: one launch
+            // (the rows are in the caller's row order: the queries are the clouds themselves)
+            auto epilogue = [&]() -> int {
                 const PnormSide<T> sx{nullptr, P.dx, P.dy, P.xy.out_i, P.xy.out_d, (int)nx, nbx, P.xy.sc.counters + C_SKEW, (long long)ny},
                                    sy{nullptr, P.dy, P.dx, P.yx.out_i, P.yx.out_d, (int)ny, nby, P.yx.sc.counters + C_SKEW, (long long)nx};
                 hipLaunchKernelGGL(k_pnorm_pair<T>, dim3(nbx + nby), dim3(kBlock), 0, s, sx, sy, pc, p_norm, P.pd, P.res_s,
                                    reinterpret_cast<unsigned*>(P.rb->pad), reinterpret_cast<const int*>(P.rb), c->h_pinned, ++c->seq);
                 HIP_TRY(hipGetLastError());
-                tm.mark(3);
-                if (attempt == 0) { rc = pair_finish(c, ar, s, P, st, &host, /*copied_by_kernel=*/true); if (rc == PCU_NONFINITE) { rc = refused(); break; } if (rc == 3) rc = PCU_RETRY; if (rc <= 0 || rc == PCU_RETRY) break; rc = 0; }
-                else { HIP_TRY(hipMemcpyAsync(c->h_pinned, P.rb, sizeof(ResultBlock), hipMemcpyDeviceToHost, s)); HIP_WAIT(s); memcpy(&host, c->h_pinned, sizeof host); }
-            }
-            if (rc || nan_result) break;
-            if (!on_dev) {
-                if (out_cxy) HIP_TRY(hipMemcpyAsync(out_cxy, P.xy.out_i, (size_t)nx * 8, hipMemcpyDeviceToHost, s));
-                if (out_cyx) HIP_TRY(hipMemcpyAsync(out_cyx, P.yx.out_i, (size_t)ny * 8, hipMemcpyDeviceToHost, s));
-                HIP_WAIT(s);
-            }
+                return 0;
+            };
+            if ((rc = rows_finish(c, pp, host, f == Fused::RowsGiven, epilogue, fin))) break;
+            if (fin == Outcome::Refused && (rc = pair_nonfinite_flags(s, P, nf))) break;
+        }
+        if (f == Fused::Restart || fin == Outcome::Restart) { out = Outcome::Restart; break; }
+        if (f == Fused::Refused || fin == Outcome::Refused) { rc = refused(nf); break; }
+        if (f != Fused::Done && !on_dev) {
+            if (out_cxy) HIP_TRY(hipMemcpyAsync(out_cxy, P.xy.out_i, (size_t)nx * 8, hipMemcpyDeviceToHost, s));
+            if (out_cyx) HIP_TRY(hipMemcpyAsync(out_cyx, P.yx.out_i, (size_t)ny * 8, hipMemcpyDeviceToHost, s));
+            HIP_WAIT(s);
         }
         const double* hs = host.sums;
         out_mean2[0] = hs[0] / (double)nx;
@@ -2430,20 +2425,17 @@ static int chamfer_end(pcu_hip_ctx* c, PendingPair<T>& pp, double* out_mean2) {
         if (st) { st->n_queries = nx + ny; st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_total = tm.span(0, 3); collect_kernel_times(c, st); }
     } while (0);
     if (!rc && nan_result) { out_mean2[0] = out_mean2[1] = std::numeric_limits<double>::quiet_NaN(); if (st) st->n_queries = nx + ny; }
-    ctx_end(c);
-    g_hprof.mark(4); g_hprof.done();
-    if (rc == PCU_RETRY) return PCU_RETRY;
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+    rc = attempt_exit(c, rc); g_hprof.mark(4); g_hprof.done();
+    return rc;
 }
 template <typename T>
 static int chamfer_impl(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int64_t ny, double p_norm, int max_leaf, double* out_mean2,
                         int64_t* out_cxy, int64_t* out_cyx, unsigned flags, void* stream, pcu_hip_stats* st) {
-    for (int restarts = 0;; ++restarts) {
+    return with_restarts([&](int restarts, Outcome& out) {
         PendingPair<T> pp; pp.restarts = restarts;
         if (int rc = chamfer_begin(c, x, nx, y, ny, p_norm, max_leaf, out_cxy, out_cyx, flags, stream, st, pp)) return rc;
-        const int rc = chamfer_end(c, pp, out_mean2);
-        if (rc != PCU_RETRY) return rc;
-    }
+        return chamfer_end(c, pp, out_mean2, out);
+    });
 }
 
 
@@ -2599,12 +2591,14 @@ static int batch_run(pcu_hip_ctx* c, int n_pairs, unsigned flags, void* stream, 
     for (int it = 0; it < n_pairs + L; ++it) {
         const int lane = it % L;
         if (cur[lane] >= 0) {
-            int r = end(c->lanes[lane], pend[lane], cur[lane]);
-            for (int restarts = 1; r == PCU_RETRY; ++restarts) {         // occupancy rescale: the lane's context has a new scale
+            Outcome out = Outcome::Clean;
+            int r = end(c->lanes[lane], pend[lane], cur[lane], out);
+            for (int restarts = 1; out == Outcome::Restart; ++restarts) {         // occupancy rescale: the lane's context has a new scale
                 pend[lane] = PendingPair<T>(); pend[lane].restarts = restarts;
                 pcu_hip_stats again;
+                out = Outcome::Clean;
                 r = begin(c->lanes[lane], pend[lane], cur[lane], lflags, &again);
-                if (!r) r = end(c->lanes[lane], pend[lane], cur[lane]);
+                if (!r) r = end(c->lanes[lane], pend[lane], cur[lane], out);
             }
             if (r && !rc) { rc = r; err = g_err; }
             stats_add(st, lst[lane]);
@@ -2690,8 +2684,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
         for (int64_t i = 0; i < n; ++i) out_vacc[i] = (int64_t)h[(size_t)i].idx;
         *out_nnodes = nn;
     } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+    return attempt_exit(c, rc);
 }
 
 #include "voxel_host.h"
@@ -2810,7 +2803,7 @@ int pcu_hip_hausdorff_batch_##SUF(pcu_hip_ctx* c, int n_pairs, const T* const* x
     CallGuard dg(c);                                                                                                     \
     return abi_rc(batch_run<T>(c, n_pairs, flags, stream, st,                                                                                      \
         [&](pcu_hip_ctx* l, PendingPair<T>& pp, int p, unsigned lf, pcu_hip_stats* ls) { return hausdorff_begin<T>(l, xs[p], nxs[p], ys[p], nys[p], true, max_leaf, lf, nullptr, ls, pp); }, \
-        [&](pcu_hip_ctx* l, PendingPair<T>& pp, int p) { return hausdorff_end<T>(l, pp, out_d2 + 2 * (size_t)p, out_i2 + 2 * (size_t)p, out_j2 + 2 * (size_t)p); }));       \
+        [&](pcu_hip_ctx* l, PendingPair<T>& pp, int p, Outcome& out) { return hausdorff_end<T>(l, pp, out_d2 + 2 * (size_t)p, out_i2 + 2 * (size_t)p, out_j2 + 2 * (size_t)p, out); }));       \
 }
 PCU_BATCH_HAUSDORFF(f32, float)
 PCU_BATCH_HAUSDORFF(f64, double)
@@ -2821,7 +2814,7 @@ int pcu_hip_chamfer_batch_##SUF(pcu_hip_ctx* c, int n_pairs, const T* const* xs,
     CallGuard dg(c);                                                                                                     \
     return abi_rc(batch_run<T>(c, n_pairs, flags, stream, st,                                                                                      \
         [&](pcu_hip_ctx* l, PendingPair<T>& pp, int p, unsigned lf, pcu_hip_stats* ls) { return chamfer_begin<T>(l, xs[p], nxs[p], ys[p], nys[p], p_norm, max_leaf, nullptr, nullptr, lf, nullptr, ls, pp); }, \
-        [&](pcu_hip_ctx* l, PendingPair<T>& pp, int p) { return chamfer_end<T>(l, pp, out_mean2 + 2 * (size_t)p); }));                            \
+        [&](pcu_hip_ctx* l, PendingPair<T>& pp, int p, Outcome& out) { return chamfer_end<T>(l, pp, out_mean2 + 2 * (size_t)p, out); }));                            \
 }
 PCU_BATCH_CHAMFER(f32, float)
 PCU_BATCH_CHAMFER(f64, double)
