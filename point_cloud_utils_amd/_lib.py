@@ -37,7 +37,8 @@ CANCEL_BY_SIGINT = 2        # ... or the chained SIGINT handler
 
 _COMPUTE_ENTRY_POINTS = [f"pcu_hip_{op}_{suf}" for suf in ("f32", "f64") for op in (
     "knn", "one_sided_hausdorff", "hausdorff", "chamfer", "index_create", "index_knn", "hausdorff_batch", "chamfer_batch", "normals_knn",
-    "normals_ball", "dedup", "pairwise", "sinkhorn", "dot", "debug_kd_tree", "poisson_disk")] + [
+    "normals_ball", "dedup", "pairwise", "sinkhorn", "dot", "debug_kd_tree", "poisson_disk", "closest_points_on_mesh", "mesh_index_create",
+    "mesh_index_closest")] + [
     "pcu_hip_morton_encode", "pcu_hip_morton_decode", "pcu_hip_morton_addsub", "pcu_hip_morton_knn"] + [
     f"pcu_hip_voxel_downsample_{sp}_{sa}" for sp in ("f32", "f64") for sa in ("f32", "f64")]
 
@@ -116,6 +117,9 @@ def lib():
                 getattr(L, f"pcu_hip_voxel_downsample_{sp}_{sa}").argtypes = [vp, vp, i64, vp, i64, ci, vp, vp, vp, ci, vp, vp, vp, u, vp]
             getattr(L, "pcu_hip_dedup_" + sp).argtypes = [vp, vp, i64, ctypes.c_double, vp, vp, vp, vp, u, vp]
             getattr(L, "pcu_hip_poisson_disk_" + sp).argtypes = [vp, vp, i64, ctypes.c_double, i64, ctypes.c_uint32, ctypes.c_double, vp, vp, u, vp, vp]
+            getattr(L, "pcu_hip_closest_points_on_mesh_" + sp).argtypes = [vp, vp, i64, vp, i64, ci, vp, i64, vp, vp, vp, u, vp, vp]
+            getattr(L, "pcu_hip_mesh_index_create_" + sp).argtypes = [vp, vp, i64, vp, i64, ci, u, vp, ctypes.POINTER(ctypes.c_void_p)]
+            getattr(L, "pcu_hip_mesh_index_closest_" + sp).argtypes = [vp, vp, vp, i64, vp, vp, vp, u, vp, vp]
         for sp in ("f32", "f64"):
             getattr(L, "pcu_hip_pairwise_" + sp).argtypes = [vp, vp, vp, i64, i64, i64, i64, ctypes.c_double, vp, u, vp]
             getattr(L, "pcu_hip_sinkhorn_" + sp).argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_double, ci, ctypes.c_double, vp, vp, u, vp]
@@ -125,6 +129,10 @@ def lib():
         L.pcu_hip_index_size.argtypes = [vp]
         L.pcu_hip_index_destroy.argtypes = [vp]
         L.pcu_hip_index_destroy.restype = None
+        L.pcu_hip_mesh_index_size.restype = ctypes.c_int64
+        L.pcu_hip_mesh_index_size.argtypes = [vp]
+        L.pcu_hip_mesh_index_destroy.argtypes = [vp]
+        L.pcu_hip_mesh_index_destroy.restype = None
         L.pcu_hip_cancel.restype = None
         L.pcu_hip_watch_sigint.argtypes = [ci]
         L.pcu_hip_cancel_source.restype = ci

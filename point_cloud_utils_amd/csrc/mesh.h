@@ -1,0 +1,326 @@
+// csrc/mesh.h -- closest_points_on_mesh: exact point-to-triangle-mesh distance.
+//
+// Replaces npe_function(closest_points_on_mesh) (src/closest_point_on_mesh.cpp:9-50), which calls igl::point_mesh_squared_distance (libigl's AABB
+// tree). libigl's last bits cannot be reproduced, so the operator has a contract of its own that does not depend on the index:
+//
+//   per face   D2(q, a, b, c) -> (d2, v, w), all in the input type T, separate multiplies and adds, IEEE division:
+//                the seven-region closest-point classification (Ericson, Real-Time Collision Detection, 5.1.5) with
+//                dot(x, y) = (x0*y0 + x1*y1) + x2*y2, tested in the order vertex A, vertex B, edge AB, vertex C, edge AC, edge BC, interior;
+//                an EDGE region is entered only if its denominator is > 0 (a collapsed edge falls through to the next region) and the interior
+//                formula with a denominator that is not > 0 gives vertex A: a degenerate face behaves as the segment or point it is and no
+//                finite input whose products stay finite gives NaN;
+//                u = (1 - v) - w, closest = (u*a + v*b) + w*c, d2 = dot(q - closest, q - closest).
+//   per query  the LOWEST face index among the faces of minimal d2 (exact equality), d = sqrt(d2) and bc = (u, v, w) of that face:
+//                what a serial loop over all faces with a strict `<` returns.
+//
+// Index: a linear BVH. Faces are ordered by the 63-bit Morton code of their centroid in the bounding box of the referenced vertices (morton.h,
+// radix.h), cut into leaves of kMeshLeaf consecutive faces, and an implicit balanced binary tree is laid over the leaves padded to a power
+// of two P: node i has children 2i+1 and 2i+2, leaf j is node P-1+j, padding leaves have the empty box (+inf, -inf). The depth is log2 P <= 25
+// whatever the data (thousands of faces with one code are no special case), so the traversal stack has a compile-time size. Boxes are made
+// bottom-up, one launch per level: a level reads only what an earlier launch wrote, so no box crosses between workgroups inside a launch.
+//
+// Pruning that cannot change the result. Let e = eps(T), S = the largest absolute coordinate of a referenced vertex.
+//   (1) the computed closest point x~ = (u*a + v*b) + w*c lies within 7 e S of the triangle in every coordinate: three products (e/2 S each), two
+//       sums (e/2 * 2S, e/2 * 3S), u + v + w = 1 up to e (two roundings in u), u >= -e (tests/mesh_contract.py states and tests/test_mesh_contract.py
+//       checks both). Leaf boxes are padded outward by 16 e S (the rest covers the rounding of the padding itself), so x~ is inside the padded box
+//       of its leaf and of every ancestor, and |q - x~| >= D, the true distance from q to that box.
+//   (2) the computed d2 = fl(|q - x~|^2) >= D^2 (1 - 3e); the computed box bound lb = fl(D^2) <= D^2 (1 + 3e) (one subtraction, one square, two sums).
+//   So a node can hold the winner only if lb (1 - 16e) <= best (the factor 16 is generous against the 6e of (2) and the rounding of the product):
+//   a node is skipped only if lb (1 - 16e) > best, and nodes whose bound EQUALS the best are visited, because a face of equal d2 and lower index wins.
+#pragma once
+#include "pcu_types.h"
+#include "grid.h"
+#include "morton.h"
+
+namespace pcu {
+
+constexpr int kMeshLeaf = 4;            // faces per leaf
+constexpr int kMeshStack = 26;          // >= tree depth + 1 (P <= 2^25 leaves: 2^27 faces)
+constexpr int kMeshBlock = 256;
+constexpr int kMeshBadVertex = 1, kMeshBadFace = 2;
+
+template <typename T>
+struct MeshHead {
+    typename EncT<T>::type elo[3], ehi[3];      // bounding box of the referenced vertices, order-preserving encoding (atomics)
+    int bad;                                    // kMeshBad*
+    T lo[3], inv[3];                            // low corner; Morton cells (of 2^21) per unit length, 0 on a flat axis
+    T pad;                                      // outward padding of every leaf box: 16 eps S
+};
+template <typename T>
+struct MeshIdx {                                // device pointers of one index
+    MeshHead<T>* head = nullptr;
+    T* tri = nullptr;                           // (nf, 9): the faces' corners in Morton order
+    unsigned* face = nullptr;                   // (nf): face index of every sorted position
+    T* box = nullptr;                           // (2P - 1, 6): lo[3], hi[3] of every node
+    int nf = 0, P = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------- build
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_mesh_vcheck(const T* __restrict__ v, long long count, int* __restrict__ bad, int bit) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    bool nf = false;
+    if (i < count) { const T x = v[i]; nf = !(x - x == (T)0); }
+    if (__ballot(nf) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, bit);
+}
+template <typename T>
+__global__ void k_mesh_head_init(MeshHead<T>* h) {
+    using E = typename EncT<T>::type;
+    if (threadIdx.x < 3) { h->elo[threadIdx.x] = ~(E)0; h->ehi[threadIdx.x] = (E)0; }
+    if (threadIdx.x == 0) h->bad = 0;
+}
+// Face indices of any of the four integer types (kind 0 int32, 1 int64, 2 uint32, 3 uint64) -> the index's own int32 triples, range-checked;
+// and the bounding box of the vertices that faces refer to.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_mesh_faces(const void* __restrict__ f, int kind, int nf, int nv, const T* __restrict__ v,
+                                                       int* __restrict__ fidx, MeshHead<T>* __restrict__ h) {
+    using E = typename EncT<T>::type;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    E lo[3] = {~(E)0, ~(E)0, ~(E)0}, hi[3] = {(E)0, (E)0, (E)0};
+    bool bad = false;
+    if (i < nf) {
+        int id[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            unsigned long long u;               // (a negative index becomes a huge unsigned one)
+            if (kind == 0) u = (unsigned long long)(long long)static_cast<const int*>(f)[3 * (size_t)i + j];
+            else if (kind == 1) u = (unsigned long long)static_cast<const long long*>(f)[3 * (size_t)i + j];
+            else if (kind == 2) u = (unsigned long long)static_cast<const unsigned*>(f)[3 * (size_t)i + j];
+            else u = static_cast<const unsigned long long*>(f)[3 * (size_t)i + j];
+            bad |= u >= (unsigned long long)nv;
+            id[j] = (int)u;
+        }
+        if (bad) id[0] = id[1] = id[2] = 0;
+        fidx[3 * (size_t)i] = id[0]; fidx[3 * (size_t)i + 1] = id[1]; fidx[3 * (size_t)i + 2] = id[2];
+        if (!bad) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const E e = enc(v[3 * (size_t)id[j] + k]);
+                    lo[k] = e < lo[k] ? e : lo[k]; hi[k] = e > hi[k] ? e : hi[k];
+                }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const E a = (E)__shfl_xor(lo[k], o, 64), b = (E)__shfl_xor(hi[k], o, 64);
+            lo[k] = a < lo[k] ? a : lo[k]; hi[k] = b > hi[k] ? b : hi[k];
+        }
+    }
+    const bool any_bad = __ballot(bad) != 0ull;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { atomicMin(&h->elo[k], lo[k]); atomicMax(&h->ehi[k], hi[k]); }
+        if (any_bad) atomicOr(&h->bad, kMeshBadFace);
+    }
+}
+template <typename T>
+__global__ void k_mesh_frame(MeshHead<T>* h) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    T S = (T)0;
+    for (int k = 0; k < 3; ++k) {
+        const T lo = dec(h->elo[k]), hi = dec(h->ehi[k]);
+        const T ext = hi - lo;
+        h->lo[k] = lo;
+        h->inv[k] = (ext > (T)0 && ext < Limits<T>::max_v) ? (T)2097152 / ext : (T)0;
+        const T m = fabs(lo) > fabs(hi) ? fabs(lo) : fabs(hi);
+        S = m > S ? m : S;
+    }
+    h->pad = (T)16 * Limits<T>::eps * S;
+}
+__device__ __forceinline__ unsigned mesh_cell(double t, unsigned top) { return t >= 0.0 ? (t < (double)top ? (unsigned)t : top) : 0u; }     // (NaN -> 0)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_mesh_codes(const T* __restrict__ v, const int* __restrict__ fidx, int nf, const MeshHead<T>* __restrict__ h,
+                                                       unsigned long long* __restrict__ keys) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nf) return;
+    const int a = fidx[3 * (size_t)i], b = fidx[3 * (size_t)i + 1], c = fidx[3 * (size_t)i + 2];
+    unsigned cell[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double m = (((double)v[3 * (size_t)a + k] + (double)v[3 * (size_t)b + k]) + (double)v[3 * (size_t)c + k]) / 3.0;
+        cell[k] = mesh_cell((m - (double)h->lo[k]) * (double)h->inv[k], 2097151u);
+    }
+    keys[i] = morton_split21(cell[0]) | morton_split21(cell[1]) << 1 | morton_split21(cell[2]) << 2;
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_mesh_gather(const T* __restrict__ v, const int* __restrict__ fidx, const unsigned* __restrict__ order, int nf,
+                                                        T* __restrict__ tri, unsigned* __restrict__ face) {
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= nf) return;
+    const unsigned id = order[s];
+    face[s] = id;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int r = fidx[3 * (size_t)id + j];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tri[9 * (size_t)s + 3 * j + k] = v[3 * (size_t)r + k];
+    }
+}
+// leaf j = node P-1+j: the padded box of the sorted faces [kMeshLeaf j, kMeshLeaf (j + 1)); beyond the last face the empty box
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_mesh_leaves(const T* __restrict__ tri, int nf, int P, const MeshHead<T>* __restrict__ h, T* __restrict__ box) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= P) return;
+    T lo[3] = {(T)INFINITY, (T)INFINITY, (T)INFINITY}, hi[3] = {-(T)INFINITY, -(T)INFINITY, -(T)INFINITY};
+    const T pad = h->pad;
+    for (int t = 0; t < kMeshLeaf; ++t) {
+        const long long s = (long long)kMeshLeaf * j + t;
+        if (s >= nf) break;
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const T x = tri[9 * (size_t)s + 3 * c + k];
+                lo[k] = x - pad < lo[k] ? x - pad : lo[k]; hi[k] = x + pad > hi[k] ? x + pad : hi[k];
+            }
+    }
+    T* o = box + 6 * (size_t)(P - 1 + j);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { o[k] = lo[k]; o[3 + k] = hi[k]; }
+}
+// one level: the m nodes m-1 .. 2m-2 from their children (written by the launch before)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_mesh_refit(T* __restrict__ box, int m) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    const size_t node = (size_t)m - 1 + i;
+    const T* l = box + 6 * (2 * node + 1);
+    const T* r = l + 6;
+    T* o = box + 6 * node;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { o[k] = l[k] < r[k] ? l[k] : r[k]; o[3 + k] = l[3 + k] > r[3 + k] ? l[3 + k] : r[3 + k]; }
+}
+
+// ---------------------------------------------------------------------------------------------------- queries
+// 30-bit Morton key of every query in the mesh's frame (clamped to it), so that the lanes of a wave walk the same nodes; non-finite rows are flagged
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_mesh_qcodes(const T* __restrict__ p, int np, const MeshHead<T>* __restrict__ h, unsigned long long* __restrict__ keys,
+                                                        int* __restrict__ bad) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    bool nf = false;
+    if (i < np) {
+        unsigned cell[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const T x = p[3 * (size_t)i + k];
+            nf |= !(x - x == (T)0);
+            cell[k] = mesh_cell(((double)x - (double)h->lo[k]) * (double)h->inv[k] * (1.0 / 2048.0), 1023u);
+        }
+        keys[i] = morton_split21(cell[0]) | morton_split21(cell[1]) << 1 | morton_split21(cell[2]) << 2;
+    }
+    if (__ballot(nf) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
+}
+
+template <typename T>
+__device__ __forceinline__ T mesh_dot(const T x[3], const T y[3]) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
+
+// D2 of the contract (head of this file). Every test is a positive one, so that a NaN from overflowing products falls through to vertex A.
+template <typename T>
+__device__ __forceinline__ void mesh_face_d2(const T q[3], const T a[3], const T b[3], const T c[3], T& d2, T& v, T& w) {
+    T ab[3], ac[3], ap[3], bp[3], cp[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { ab[k] = b[k] - a[k]; ac[k] = c[k] - a[k]; ap[k] = q[k] - a[k]; bp[k] = q[k] - b[k]; cp[k] = q[k] - c[k]; }
+    const T d1 = mesh_dot(ab, ap), d2_ = mesh_dot(ac, ap), d3 = mesh_dot(ab, bp), d4 = mesh_dot(ac, bp), d5 = mesh_dot(ab, cp), d6 = mesh_dot(ac, cp);
+    const T vc = d1 * d4 - d3 * d2_, vb = d5 * d2_ - d1 * d6, va = d3 * d6 - d5 * d4;
+    const T e_ab = d1 - d3, e_ac = d2_ - d6, e_b = d4 - d3, e_c = d5 - d6, e_bc = e_b + e_c, den = (va + vb) + vc;
+    v = (T)0; w = (T)0;
+    if (d1 <= (T)0 && d2_ <= (T)0) { /* vertex A */ }
+    else if (d3 >= (T)0 && d4 <= d3) { v = (T)1; }                                                      // vertex B
+    else if (vc <= (T)0 && d1 >= (T)0 && d3 <= (T)0 && e_ab > (T)0) { v = d1 / e_ab; }                   // edge AB
+    else if (d6 >= (T)0 && d5 <= d6) { w = (T)1; }                                                      // vertex C
+    else if (vb <= (T)0 && d2_ >= (T)0 && d6 <= (T)0 && e_ac > (T)0) { w = d2_ / e_ac; }                 // edge AC
+    else if (va <= (T)0 && e_b >= (T)0 && e_c >= (T)0 && e_bc > (T)0) { w = e_b / e_bc; v = (T)1 - w; }  // edge BC
+    else if (den > (T)0) { v = vb / den; w = vc / den; }                                                // interior
+    const T u = ((T)1 - v) - w;
+    T r[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r[k] = q[k] - ((u * a[k] + v * b[k]) + w * c[k]);
+    d2 = mesh_dot(r, r);
+}
+
+// (1 - 16 eps) times the squared distance from q to a node's box, in T (see "Pruning" at the head of this file); +inf for the empty box
+template <typename T>
+__device__ __forceinline__ T mesh_bound(const T* __restrict__ bx, const T q[3]) {
+    T d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const T below = bx[k] - q[k], above = q[k] - bx[3 + k];
+        const T m = below > above ? below : above;
+        d[k] = m > (T)0 ? m : (T)0;
+    }
+    return mesh_dot(d, d) * ((T)1 - (T)16 * Limits<T>::eps);
+}
+
+template <typename T>
+struct MeshQuery {
+    const T* p; const unsigned* order; int np;
+    MeshIdx<T> ix;
+    T* out_d; long long* out_fi; T* out_bc;
+    const unsigned* cancel_word; unsigned cancel_gen;          // pcu_types.h: cancel_seen
+};
+
+// One lane per query, queries in Morton order. Near child first, the far child pushed if its bound allows: at most one entry per level, so the
+// stack (LDS, one column per lane: a runtime-indexed private array would live in scratch memory) holds kMeshStack node ids. A popped node's
+// bound is computed again, against the best of that moment.
+template <typename T>
+__global__ __launch_bounds__(kMeshBlock) void k_mesh_closest(const MeshQuery<T> a) {
+    __shared__ int s_stack[kMeshStack][kMeshBlock];
+    const int i = blockIdx.x * kMeshBlock + threadIdx.x;
+    if (i >= a.np) return;
+    const unsigned row = a.order[i];
+    const T q[3] = {a.p[3 * (size_t)row], a.p[3 * (size_t)row + 1], a.p[3 * (size_t)row + 2]};
+    const T* __restrict__ box = a.ix.box;
+    const T* __restrict__ tri = a.ix.tri;
+    const int first_leaf = a.ix.P - 1, nf = a.ix.nf;
+    T best = (T)INFINITY, bv = (T)0, bw = (T)0;
+    unsigned bf = 0xffffffffu;
+    int sp = 0, node = 0;
+    unsigned steps = 0;
+    long long t_poll = wall_clock64();
+    bool live = (q[0] - q[0] == (T)0) && (q[1] - q[1] == (T)0) && (q[2] - q[2] == (T)0);        // (a non-finite row is refused by the host after the launch)
+    while (live) {
+        if ((++steps & 63u) == 0u) { const long long t_now = wall_clock64(); if (t_now - t_poll > 20000ll) { t_poll = t_now; if (cancel_seen(a.cancel_word, a.cancel_gen)) return; } }
+        bool descend = false;
+        if (node >= first_leaf) {
+            const long long s0 = (long long)kMeshLeaf * (node - first_leaf);
+            for (int t = 0; t < kMeshLeaf; ++t) {
+                const long long s = s0 + t;
+                if (s >= nf) break;
+                const T* tr = tri + 9 * (size_t)s;
+                const T fa[3] = {tr[0], tr[1], tr[2]}, fb[3] = {tr[3], tr[4], tr[5]}, fc[3] = {tr[6], tr[7], tr[8]};
+                T d2, v, w;
+                mesh_face_d2(q, fa, fb, fc, d2, v, w);
+                const unsigned id = a.ix.face[s];
+                if (d2 < best || (d2 == best && id < bf)) { best = d2; bf = id; bv = v; bw = w; }
+            }
+        } else {
+            const int c0 = 2 * node + 1;
+            const T l0 = mesh_bound(box + 6 * (size_t)c0, q), l1 = mesh_bound(box + 6 * (size_t)c0 + 6, q);
+            const bool v0 = l0 <= best, v1 = l1 <= best;
+            if (v0 && v1) {
+                const bool left_first = l0 <= l1;
+                s_stack[sp++][threadIdx.x] = left_first ? c0 + 1 : c0;
+                node = left_first ? c0 : c0 + 1;
+                descend = true;
+            } else if (v0 || v1) {
+                node = v0 ? c0 : c0 + 1;
+                descend = true;
+            }
+        }
+        if (descend) continue;
+        live = false;
+        while (sp > 0) {
+            const int n = s_stack[--sp][threadIdx.x];
+            if (mesh_bound(box + 6 * (size_t)n, q) <= best) { node = n; live = true; break; }
+        }
+    }
+    const T u = ((T)1 - bv) - bw;
+    a.out_d[row] = sqrt(best);
+    a.out_fi[row] = bf == 0xffffffffu ? -1ll : (long long)bf;
+    a.out_bc[3 * (size_t)row] = u; a.out_bc[3 * (size_t)row + 1] = bv; a.out_bc[3 * (size_t)row + 2] = bw;
+}
+
+}  // namespace pcu

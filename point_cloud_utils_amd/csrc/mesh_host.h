@@ -1,0 +1,203 @@
+// csrc/mesh_host.h -- host orchestration of closest_points_on_mesh (kernels, contract and index layout: mesh.h). Included by pcu_hip.hip after
+// the arena, staging and radix-sort helpers.
+#pragma once
+
+// A mesh kept on the GPU as its search index (pcu_hip_mesh_index_*): one block owned by the object, not by a call's arena.
+struct pcu_hip_mesh_index {
+    int elem_size = 0;            // 4: float, 8: double
+    int device = 0;
+    int64_t nf = 0;
+    void* mem = nullptr;
+    MeshIdx<float> m32; MeshIdx<double> m64;
+};
+template <typename T> static MeshIdx<T>& mesh_idx(pcu_hip_mesh_index* p);
+template <> MeshIdx<float>& mesh_idx<float>(pcu_hip_mesh_index* p) { return p->m32; }
+template <> MeshIdx<double>& mesh_idx<double>(pcu_hip_mesh_index* p) { return p->m64; }
+
+static void mesh_index_free(pcu_hip_mesh_index* p) {
+    if (!p) return;
+    if (p->mem) (void)hipFree(p->mem);
+    delete p;
+}
+static int mesh_leaves_pow2(int64_t nf) {
+    const int64_t leaves = (nf + kMeshLeaf - 1) / kMeshLeaf;
+    int P = 1;
+    while (P < leaves) P <<= 1;
+    return P;
+}
+static size_t mesh_sort_bytes(int64_t n) {
+    const size_t N = (size_t)n, nwt = (N + kRsWaveTile - 1) / kRsWaveTile;
+    return 2 * align_up(N * 8, 256) + 2 * align_up(N * 4, 256) + align_up(256 * nwt * 4, 256) + 1024;
+}
+template <typename T>
+static size_t mesh_index_bytes(int64_t nf) {
+    const size_t N = (size_t)nf, P = (size_t)mesh_leaves_pow2(nf);
+    return align_up(sizeof(MeshHead<T>), 256) + align_up(N * 9 * sizeof(T), 256) + align_up(N * 4, 256) + align_up(2 * P * 6 * sizeof(T), 256) + 1024;
+}
+static int mesh_face_bytes(int f_kind) { return (f_kind == 0 || f_kind == 2) ? 4 : 8; }
+template <typename T>
+static size_t mesh_build_bytes(int64_t nv, int64_t nf, int f_kind, bool on_dev) {
+    size_t b = mesh_sort_bytes(nf) + align_up((size_t)nf * 12, 256) + 4096;
+    if (!on_dev) b += align_up((size_t)nv * 3 * sizeof(T), 256) + align_up((size_t)nf * 3 * mesh_face_bytes(f_kind), 256);
+    return b;
+}
+template <typename T>
+static size_t mesh_query_bytes(int64_t np, bool on_dev) {
+    size_t b = mesh_sort_bytes(np) + 4096;
+    if (!on_dev) b += 2 * align_up((size_t)np * 3 * sizeof(T), 256) + align_up((size_t)np * sizeof(T), 256) + align_up((size_t)np * 8, 256);
+    return b;
+}
+// validate_mesh (src/common/common.h:133-147) and this package's row limit
+static int mesh_validate(int64_t nv, int64_t nf, int64_t np, int f_kind) {
+    if (nv <= 0 || nf <= 0)
+        return fail(PCU_HIP_ERR_INVALID, "Invalid input mesh with zero elements: v and f must have shape (n, 3) and (m, 3) (n, m > 0). Got v.shape =(%lld, 3), f.shape = (%lld, 3).",
+                    (long long)nv, (long long)nf);
+    if (np < 0) return fail(PCU_HIP_ERR_INVALID, "negative number of query points");
+    if (f_kind < 0 || f_kind > 3) return fail(PCU_HIP_ERR_INVALID, "f_kind must be one of PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64");
+    if (nv > 0x07fffff0ll || nf > 0x07fffff0ll || np > 0x07fffff0ll) return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported");
+    return 0;
+}
+
+// Enqueues the build on s and waits once (the validity flags). `ari` gives the buffers of the index, `ar` the temporaries.
+template <typename T>
+static int mesh_build(Arena& ari, Arena& ar, hipStream_t s, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, bool on_dev, MeshIdx<T>& M) {
+    const T* dv = nullptr; const char* df = nullptr;
+    if (stage_in(ar, v, nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(f), (size_t)nf * 3 * mesh_face_bytes(f_kind), on_dev, s, &df)) return -1;
+    M.nf = (int)nf; M.P = mesh_leaves_pow2(nf);
+    int* fidx = nullptr;
+    if (aalloc(ari, &M.head, 1) || aalloc(ari, &M.tri, (size_t)nf * 9) || aalloc(ari, &M.face, (size_t)nf) || aalloc(ari, &M.box, (size_t)M.P * 12) ||
+        aalloc(ar, &fidx, (size_t)nf * 3)) return -1;
+    const int nbf = (int)((nf + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_mesh_head_init<T>, dim3(1), dim3(64), 0, s, M.head);
+    int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
+    hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3((unsigned)((nv * 3 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, dv, (long long)nv * 3, d_bad, kMeshBadVertex);
+    hipLaunchKernelGGL(k_mesh_faces<T>, dim3(nbf), dim3(kBlock), 0, s, (const void*)df, f_kind, (int)nf, (int)nv, dv, fidx, M.head);
+    hipLaunchKernelGGL(k_mesh_frame<T>, dim3(1), dim3(64), 0, s, M.head);
+    HIP_TRY(hipGetLastError());
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_WAIT(s);
+    if (bad & kMeshBadVertex) return fail(PCU_HIP_ERR_INVALID, "v must not contain NaN or infinite coordinates");
+    if (bad & kMeshBadFace) return fail(PCU_HIP_ERR_INVALID, "f must hold row indices of v: found a face index outside [0, %lld)", (long long)nv);
+    unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
+    if (aalloc(ar, &ka, (size_t)nf) || aalloc(ar, &kb, (size_t)nf) || aalloc(ar, &ia, (size_t)nf) || aalloc(ar, &ib, (size_t)nf)) return -1;
+    hipLaunchKernelGGL(k_mesh_codes<T>, dim3(nbf), dim3(kBlock), 0, s, dv, (const int*)fidx, (int)nf, (const MeshHead<T>*)M.head, ka);
+    if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)nf, 63)) return -1;
+    hipLaunchKernelGGL(k_mesh_gather<T>, dim3(nbf), dim3(kBlock), 0, s, dv, (const int*)fidx, (const unsigned*)ia, (int)nf, M.tri, M.face);
+    hipLaunchKernelGGL(k_mesh_leaves<T>, dim3((M.P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const T*)M.tri, (int)nf, M.P, (const MeshHead<T>*)M.head, M.box);
+    for (int m = M.P / 2; m >= 1; m /= 2) hipLaunchKernelGGL(k_mesh_refit<T>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, M.box, m);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Enqueues the queries and waits for them. Events 1 / 2 of the context bracket the query phase.
+template <typename T>
+static int mesh_query(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const MeshIdx<T>& M, const T* p, int64_t np, bool on_dev, T* out_d, int64_t* out_fi, T* out_bc,
+                      Timer& tm) {
+    tm.mark(1);
+    if (np == 0) { tm.mark(2); HIP_WAIT(s); return 0; }
+    const T* dp = nullptr;
+    if (stage_in(ar, p, np, on_dev, s, &dp)) return -1;
+    int* d_bad = nullptr;
+    unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
+    if (aalloc(ar, &d_bad, 1) || aalloc(ar, &ka, (size_t)np) || aalloc(ar, &kb, (size_t)np) || aalloc(ar, &ia, (size_t)np) || aalloc(ar, &ib, (size_t)np)) return -1;
+    T *d_d = out_d, *d_bc = out_bc; long long* d_fi = reinterpret_cast<long long*>(out_fi);
+    if (!on_dev && (aalloc(ar, &d_d, (size_t)np) || aalloc(ar, &d_fi, (size_t)np) || aalloc(ar, &d_bc, (size_t)np * 3))) return -1;
+    const int nb = (int)((np + kBlock - 1) / kBlock);
+    HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_mesh_qcodes<T>, dim3(nb), dim3(kBlock), 0, s, dp, (int)np, (const MeshHead<T>*)M.head, ka, d_bad);
+    if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)np, 30)) return -1;
+    MeshQuery<T> a;
+    a.p = dp; a.order = ia; a.np = (int)np; a.ix = M;
+    a.out_d = d_d; a.out_fi = d_fi; a.out_bc = d_bc;
+    a.cancel_word = g_cancel_mirror.load(std::memory_order_relaxed); a.cancel_gen = t_call_gen;
+    hipLaunchKernelGGL(k_mesh_closest<T>, dim3((unsigned)((np + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    tm.mark(2);
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (!on_dev) {
+        HIP_TRY(hipMemcpyAsync(out_d, d_d, (size_t)np * sizeof(T), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)np * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)np * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+    }
+    HIP_WAIT(s);
+    if (bad) return fail(PCU_HIP_ERR_INVALID, "p must not contain NaN or infinite coordinates");
+    return 0;
+}
+static void mesh_stats(pcu_hip_stats* st, Timer& tm, int64_t np, bool built) {
+    if (!st) return;
+    st->n_queries = np; st->n_passes = 1; st->n_grid_builds = built ? 1 : 0;
+    if (built) st->ms_index = tm.span(0, 1);
+    st->ms_search = tm.span(1, 2);
+    st->ms_total = built ? tm.span(0, 2) : st->ms_search;
+}
+
+// closest_points_on_mesh (src/closest_point_on_mesh.cpp:25-50): index, queries and temporaries in the call's arena
+template <typename T>
+static int mesh_oneshot_impl(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* p, int64_t np,
+                             T* out_d, int64_t* out_fi, T* out_bc, unsigned flags, void* stream, pcu_hip_stats* st) {
+    if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
+    if (st) memset(st, 0, sizeof *st);
+    if (int rc = mesh_validate(nv, nf, np, f_kind)) return rc;
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
+    hipStream_t s = pick_stream(c, flags, stream);
+    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
+    if (ctx_begin(c, mesh_index_bytes<T>(nf) + mesh_build_bytes<T>(nv, nf, f_kind, on_dev) + mesh_query_bytes<T>(np, on_dev))) return PCU_HIP_ERR_RUNTIME;
+    Arena ar{c};
+    Timer tm{c, s, st};
+    MeshIdx<T> M;
+    tm.mark(0);
+    int rc = mesh_build<T>(ar, ar, s, v, nv, f, nf, f_kind, on_dev, M);
+    if (!rc) rc = mesh_query<T>(c, ar, s, M, p, np, on_dev, out_d, out_fi, out_bc, tm);
+    if (!rc) mesh_stats(st, tm, np, true);
+    return attempt_exit(c, rc);
+}
+
+template <typename T>
+static int mesh_index_create_impl(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, unsigned flags, void* stream,
+                                  pcu_hip_mesh_index** out) {
+    if (!c || !out) return fail(PCU_HIP_ERR_INVALID, "null context / output");
+    *out = nullptr;
+    if (int rc = mesh_validate(nv, nf, 0, f_kind)) return rc;
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
+    hipStream_t s = pick_stream(c, flags, stream);
+    pcu_hip_mesh_index* p = new pcu_hip_mesh_index();
+    p->elem_size = (int)sizeof(T); p->device = c->device; p->nf = nf;
+    const size_t bytes = mesh_index_bytes<T>(nf);
+    if (hipMalloc(&p->mem, bytes) != hipSuccess) { p->mem = nullptr; mesh_index_free(p); return fail(PCU_HIP_ERR_RUNTIME, "out of device memory for the mesh index"); }
+    if (ctx_begin(c, mesh_build_bytes<T>(nv, nf, f_kind, on_dev))) { mesh_index_free(p); return PCU_HIP_ERR_RUNTIME; }
+    pcu_hip_ctx holder;                             // only its arena fields are used: a bump allocator over the index's own block
+    holder.device = c->device; holder.arena = static_cast<char*>(p->mem); holder.arena_cap = bytes; holder.arena_off = 0;
+    Arena ari{&holder}, ar{c};
+    int rc = mesh_build<T>(ari, ar, s, v, nv, f, nf, f_kind, on_dev, mesh_idx<T>(p));
+    if (!rc) rc = wait_stream(s);                   // (the temporaries go back to the context with this call)
+    if (!holder.extra.empty()) {
+        (void)hipDeviceSynchronize();
+        for (void* q : holder.extra) (void)hipFree(q);
+        if (!rc) rc = fail(PCU_HIP_ERR_RUNTIME, "internal: mesh index block too small");
+    }
+    rc = attempt_exit(c, rc);
+    if (rc) { (void)hipStreamSynchronize(s); mesh_index_free(p); return rc; }
+    *out = p;
+    return 0;
+}
+
+template <typename T>
+static int mesh_index_closest_impl(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* p, int64_t np, T* out_d, int64_t* out_fi, T* out_bc,
+                                   unsigned flags, void* stream, pcu_hip_stats* st) {
+    if (!c || !ix) return fail(PCU_HIP_ERR_INVALID, "null context / mesh index");
+    if (st) memset(st, 0, sizeof *st);
+    if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the mesh index was built for the other scalar type");
+    if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the mesh index lives on another device than the context");
+    if (np < 0 || np > 0x07fffff0ll) return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported");
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
+    hipStream_t s = pick_stream(c, flags, stream);
+    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
+    if (ctx_begin(c, mesh_query_bytes<T>(np, on_dev))) return PCU_HIP_ERR_RUNTIME;
+    Arena ar{c};
+    Timer tm{c, s, st};
+    int rc = mesh_query<T>(c, ar, s, mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)), p, np, on_dev, out_d, out_fi, out_bc, tm);
+    if (!rc) mesh_stats(st, tm, np, false);
+    return attempt_exit(c, rc);
+}

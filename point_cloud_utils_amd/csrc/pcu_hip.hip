@@ -36,6 +36,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "voxel.h"
 #include "sinkhorn.h"
 #include "poisson.h"
+#include "mesh.h"
 
 using namespace pcu;
 
@@ -2689,6 +2690,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 
 #include "voxel_host.h"
 #include "poisson_host.h"
+#include "mesh_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2900,6 +2902,31 @@ void pcu_hip_index_destroy(pcu_hip_index* ix) {
     DeviceGuard dg(ix->device);
     (void)hipDeviceSynchronize();
     index_free(ix);
+}
+
+// closest_points_on_mesh (mesh.h, mesh_host.h). A create that a late request turns into PCU_HIP_ERR_CANCELLED gives its index back: the caller sees an
+// error and would drop the handle.
+#define PCU_MESH(SUF, T)                                                                                                                              \
+int pcu_hip_closest_points_on_mesh_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* p, int64_t np,      \
+                                         T* out_d, int64_t* out_fi, T* out_bc, unsigned flags, void* stream, pcu_hip_stats* st) {                   \
+    CallGuard dg(c); return abi_rc(mesh_oneshot_impl<T>(c, v, nv, f, nf, f_kind, p, np, out_d, out_fi, out_bc, flags, stream, st)); }                \
+int pcu_hip_mesh_index_create_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, unsigned flags, void* stream,    \
+                                    pcu_hip_mesh_index** out) {                                                                                      \
+    CallGuard dg(c);                                                                                                                                 \
+    const int rc = abi_rc(mesh_index_create_impl<T>(c, v, nv, f, nf, f_kind, flags, stream, out));                                                   \
+    if (rc && out && *out) { DeviceGuard g(c->device); (void)hipDeviceSynchronize(); mesh_index_free(*out); *out = nullptr; }                        \
+    return rc; }                                                                                                                                     \
+int pcu_hip_mesh_index_closest_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* p, int64_t np, T* out_d, int64_t* out_fi, T* out_bc,     \
+                                     unsigned flags, void* stream, pcu_hip_stats* st) {                                                              \
+    CallGuard dg(c); return abi_rc(mesh_index_closest_impl<T>(c, ix, p, np, out_d, out_fi, out_bc, flags, stream, st)); }
+PCU_MESH(f32, float) PCU_MESH(f64, double)
+#undef PCU_MESH
+int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }
+void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) {
+    if (!ix) return;
+    DeviceGuard dg(ix->device);
+    (void)hipDeviceSynchronize();
+    mesh_index_free(ix);
 }
 
 }  // extern "C"
