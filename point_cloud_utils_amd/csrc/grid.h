@@ -530,7 +530,10 @@ constexpr int kBkBlockPts = kBkThreads * kBkPts;    // 8192 points per block (40
 constexpr int kBkMaxBuckets = 8192;                 // LDS: 32 KB (count) / 64 KB (scatter) of bucket counters per 1024-thread block
 constexpr int kBkMaxCellsPerBucket = 4096;
 constexpr int kSortThreads = PCU_SORT_THREADS;
-constexpr int kSortIters = 8;                       // (16 costs 8 more VGPRs: 3 instead of 4 resident blocks per CU)
+#ifndef PCU_SORT_ITERS
+#define PCU_SORT_ITERS 8          // (16 costs 8 more VGPRs: 3 instead of 4 resident blocks per CU)
+#endif
+constexpr int kSortIters = PCU_SORT_ITERS;          // trips over a full slot: kLargeBucket below (tuning knob, with PCU_BUCKET_PTS and PCU_STAGE_RECS)
 constexpr unsigned kLargeBucket = kSortThreads * kSortIters;      // 8192 points = twice the mean bucket
 #ifndef PCU_BUCKET_PTS
 #define PCU_BUCKET_PTS 4096

@@ -294,37 +294,52 @@ __global__ __launch_bounds__(kBkThreads) void k_bucket_onepass3(const Build2Args
         if (lane == 63) a.xpartial[(size_t)bid * kXPartStride + wave] = r;
     } else if (tid == 6 * 64) a.xpartial[(size_t)bid * kXPartStride + 6] = (T)s_nf;
     // per bucket: where the block's run starts in the stage (exclusive scan of the counts, two buckets per thread) and in the bucket's slot
+    unsigned long long at[2] = {0ull, 0ull}; unsigned rc0, rc1;
     {
         static_assert(kStagedMaxBuckets == 2 * kBkThreads, "two buckets per thread");
         const int i0 = 2 * tid;
         const unsigned c0 = i0 < NB ? s_cnt[i0] : 0u, c1 = i0 + 1 < NB ? s_cnt[i0 + 1] : 0u;
+        rc0 = c0; rc1 = c1;
         unsigned total;
         const unsigned ex = block_exclusive_scan_nt<kBkThreads>(c0 + c1, &total);
         if (i0 < NB) s_lbase[i0] = ex;
         if (i0 + 1 < NB) s_lbase[i0 + 1] = ex + c0;
+        // (the reservations are REQUESTED here and looked at after the staging loop, which needs s_lbase and rk only: the returning atomics'
+        // round trip through the L2 runs under it instead of in front of it)
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int i = i0 + q; const unsigned c = q ? c1 : c0;
-            if (i < NB && c) {
-                const unsigned pad = (c + 7u) & ~7u;
-                const unsigned at = (unsigned)atomicAdd(&a.fill[i], ((unsigned long long)c << 32) | (unsigned long long)pad);
-                if (at + pad > cap) { *a.ovf = 1ull; s_gbase[i] = 0xffffffffu; }
-                else s_gbase[i] = (unsigned)i * cap + at;
-            }
+            if (i < NB && c) at[q] = atomicAdd(&a.fill[i], ((unsigned long long)c << 32) | (unsigned long long)((c + 7u) & ~7u));
         }
     }
     __syncthreads();                // (the folds above have read the columns: the stage may be written)
-    P3_PROF(3);                                                      // partial folds, bucket scan, slot reservations (global atomics)
-    typedef typename RawRec<T>::type Raw;
+    P3_PROF(3);                                                      // partial folds, bucket scan, slot reservations requested (global atomics)
 #pragma unroll
     for (int j = 0; j < PTS; ++j) {
         const int i = base + j * kBkThreads + tid;
         if (i < n) { Pt4<T> p; p.x = px[j]; p.y = py[j]; p.z = pz[j]; p.idx = i; s_stage[s_lbase[bk[j]] + rk[j]] = p; }
     }
+    // (both words of the atomics' results stay claimed up to here: the unused high words are otherwise handed out as temporaries of the loop
+    // above, and a write to a register with a load in flight waits for the load)
+    asm volatile("" :: "v"(at[0]), "v"(at[1]));
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int i = 2 * tid + q; const unsigned c = q ? rc1 : rc0;
+        if (i < NB && c) {
+            const unsigned pad = (c + 7u) & ~7u, lo = (unsigned)at[q];
+            if (lo + pad > cap) { *a.ovf = 1ull; s_gbase[i] = 0xffffffffu; }
+            else s_gbase[i] = (unsigned)i * cap + lo;
+        }
+    }
     __syncthreads();
-    P3_PROF(4);                                                      // staging
+    P3_PROF(4);                                                      // staging, reservations arrived
     // run by run, a wave each: lane l of a wave holds the description of bucket wave + 16 (64 r + l) in round r and hands it out by shuffles
-    Pt4<T> hole; hole.x = hole.y = hole.z = (T)0; hole.idx = -1;
+    // (copied as 16-byte chunks, consecutive lanes consecutive chunks, so that every store instruction writes whole lines through -- also for the
+    // 32-byte float64 records; a HOLE record is zero coordinates and row id -1: all-zero chunks but for the words of the id)
+    constexpr unsigned CH = sizeof(Pt4<T>) / 16;
+    const Chunk16* const stage16 = reinterpret_cast<const Chunk16*>(s_stage);
+    Chunk16* const tmp16 = reinterpret_cast<Chunk16*>(a.tmp);
+    const Chunk16 zero16 = {0u, 0u, 0u, 0u}, hole_id16 = {0u, 0u, sizeof(T) == 8 ? 0xffffffffu : 0u, 0xffffffffu};
     for (int r0 = 0; r0 * 1024 + wave < NB; ++r0) {
         const int mine = wave + 16 * (64 * r0 + lane);
         const unsigned mc = mine < NB ? s_cnt[mine] : 0u, ml = mine < NB ? s_lbase[mine] : 0u, mg = mine < NB ? s_gbase[mine] : 0u;
@@ -335,10 +350,10 @@ __global__ __launch_bounds__(kBkThreads) void k_bucket_onepass3(const Build2Args
             const unsigned lb = (unsigned)__shfl((int)ml, k, 64), gb = (unsigned)__shfl((int)mg, k, 64);
             if (gb == 0xffffffffu) continue;
             const unsigned pad = (c + 7u) & ~7u;
-            for (unsigned l = (unsigned)lane; l < pad; l += 64u) {
-                Pt4<T> rec = hole;
-                if (l < c) rec = s_stage[lb + l];
-                a.tmp[gb + l] = rec;
+            for (unsigned l = (unsigned)lane; l < pad * CH; l += 64u) {
+                Chunk16 v = (l % CH) == CH - 1 ? hole_id16 : zero16;
+                if (l / CH < c) v = stage16[(size_t)lb * CH + l];
+                store16_wt(tmp16 + ((size_t)gb * CH + l), v);           // (write-through, pcu_types.h: the sort reads `tmp` on other XCDs)
             }
         }
     }
@@ -423,13 +438,37 @@ __device__ __forceinline__ void fold_xpartials(const Build2Side<T>& a) {
     put_sentinels(a.sorted, a.n);
 }
 
+// Output offset of bucket b = the points of the buckets before it (every thread; zeroes the bucket's cell counters on the way; two barriers).
+// The fill words are requested by the CALLER, ahead of whatever it wants in flight meanwhile: part = this thread's share of fill[0, b).
+constexpr int kHeadTrips = (kStagedMaxBuckets + kSortThreads - 1) / kSortThreads;
+template <typename T>
+__device__ __forceinline__ void sort2_head_request(const Build2Side<T>& a, const int b, unsigned long long (&fw)[kHeadTrips]) {
+#pragma unroll
+    for (int q = 0; q < kHeadTrips; ++q) { const int i = q * kSortThreads + (int)threadIdx.x; fw[q] = i < b ? a.fill[i] : 0ull; }      // (b <= kStagedMaxBuckets)
+}
+__device__ __forceinline__ unsigned sort2_head_fold(const unsigned long long (&fw)[kHeadTrips], unsigned* const s_cnt, const int CB, unsigned* const s_w) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned part = 0;
+#pragma unroll
+    for (int q = 0; q < kHeadTrips; ++q) part += (unsigned)(fw[q] >> 32);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+    if (lane == 0) s_w[wave] = part;
+    for (int i = tid; i < CB; i += kSortThreads) s_cnt[i] = 0u;
+    __syncthreads();
+    unsigned s = 0;
+    for (int w = 0; w < kSortThreads / 64; ++w) s += s_w[w];
+    __syncthreads();
+    return s;
+}
+
 constexpr int kRegIters = (kStageRecs + kSortThreads - 1) / kSortThreads;       // 5 at 4352 / 1024: trips over a slot whose records a thread keeps in registers
 // FAST (the normal case): the slot's records (holes included) make at most kRegIters trips and its points fit the LDS stage -- the records stay
 // in registers from their single read to their placement in the stage. !FAST (an over-full bucket): the slot is read twice and the records are
 // placed directly. (The kernel is bound by instruction issue, not by latency: with the register count forced down to 64 -- two resident
 // 1024-thread blocks per CU -- every block ran twice as long, and the spills made it 42 us instead of 26; profiles/r04_build_ab.txt.)
 template <typename T, bool FAST>
-__device__ __forceinline__ void sort2_body(const int b, const Build2Side<T>& a, const int cnt_cap, const unsigned s, const unsigned pf, const unsigned nvalid,
+__device__ __forceinline__ void sort2_body(const int b, const Build2Side<T>& a, const int cnt_cap, const unsigned long long (&hw)[kHeadTrips], const unsigned pf, const unsigned nvalid,
                                            unsigned* const s_cnt, Pt4<T>* const s_stage, unsigned* const s_w, unsigned long long* const s_q, long long t_prev) {
     GridParams<T>* const gp = a.gp;
     const CellMap<T> cm(*gp);
@@ -442,7 +481,6 @@ __device__ __forceinline__ void sort2_body(const int b, const Build2Side<T>& a, 
     const unsigned cap = a.cap;
     const unsigned c0 = (unsigned)b << shift;
     const int ncl = min(CB, ncells - (int)c0);
-    const unsigned e = s + nvalid;
     const Pt4<T>* const slot = a.tmp + (size_t)b * cap;
     const unsigned lastp = pf ? pf - 1u : 0u;
     typedef typename RawRec<T>::type Raw;
@@ -454,6 +492,12 @@ __device__ __forceinline__ void sort2_body(const int b, const Build2Side<T>& a, 
         const Raw* const rslot = reinterpret_cast<const Raw*>(slot);
 #pragma unroll
         for (int u = 0; u < kRegIters; ++u) recs[u] = rslot[min((unsigned)(u * kSortThreads + tid), lastp)];
+    }
+    // (the slot's loads need fill[b] and cap only; the fold over fill[0, b) -- a wave butterfly and two barriers -- runs while they are in flight)
+    const unsigned s = sort2_head_fold(hw, s_cnt, CB, s_w);
+    const unsigned e = s + nvalid;
+    S2_PROF(0);                                    // head (FAST: with the slot's loads in flight)
+    if (FAST) {
 #pragma unroll
         for (int u = 0; u < kRegIters; ++u) {
             const unsigned p = (unsigned)(u * kSortThreads + tid);
@@ -550,9 +594,13 @@ __device__ __forceinline__ void sort2_body(const int b, const Build2Side<T>& a, 
     // the copy-out is one ds_read_b128 + one 16-byte store per 4 (2) scalars instead of index arithmetic per scalar.
     constexpr unsigned V = 16 / sizeof(T);                           // scalars per 16 bytes
     T* const st = reinterpret_cast<T*>(s_stage);
-    int* const sidx = reinterpret_cast<int*>(st + (V + 3 * kStageRecs + V - 1) / V * V);
-    static_assert(((V + 3 * kStageRecs + V - 1) / V * V) * sizeof(T) + (size_t)kStageRecs * 4 <= (size_t)kStageRecs * sizeof(Pt4<T>) + 64, "both streams fit the stage (bucket_sort_lds_bytes)");
+    // The row ids likewise: `iph` words into their (16-byte aligned) part of the stage, iph = the word of its 16-byte chunk idx32[s] is (the
+    // id stream starts wherever the coordinate stream of n + 8 records ends: any residue).
+    int* const sidx0 = reinterpret_cast<int*>(st + (V + 3 * kStageRecs + V - 1) / V * V);
+    static_assert(((V + 3 * kStageRecs + V - 1) / V * V) * sizeof(T) + ((size_t)kStageRecs + 4) * 4 <= (size_t)kStageRecs * sizeof(Pt4<T>) + 64, "both streams fit the stage (bucket_sort_lds_bytes)");
     const unsigned phase = (unsigned)((3ull * (unsigned long long)s) & (V - 1));
+    const unsigned iph = (unsigned)((reinterpret_cast<size_t>(idx32 + s) >> 2) & 3u);
+    int* const sidx = sidx0 + iph;
     {
 #pragma unroll
         for (int u = 0; u < kRegIters; ++u) {
@@ -567,19 +615,18 @@ __device__ __forceinline__ void sort2_body(const int b, const Build2Side<T>& a, 
     }
     __syncthreads();
     S2_PROF(3);                                    // placement in the stage
-    for (unsigned i = tid; i < nvalid; i += kSortThreads) {
-        const int id = sidx[i];
-        idx32[s + i] = id;
-        if (a.want_pt4) { Pt4<T> r; const T* const o = st + phase + 3u * i; r.x = o[0]; r.y = o[1]; r.z = o[2]; r.idx = id; a.sorted[s + i] = r; }
+    if (a.want_pt4) {
+        for (unsigned i = tid; i < nvalid; i += kSortThreads) { Pt4<T> r; const T* const o = st + phase + 3u * i; r.x = o[0]; r.y = o[1]; r.z = o[2]; r.idx = sidx[i]; a.sorted[s + i] = r; }
     }
+    // Both streams leave as whole 16-byte chunks, write-through (pcu_types.h: store16_wt -- the searches read them on other XCDs), and their
+    // partial chunks at both ends scalar by scalar with plain stores (a narrow write-through store costs several times a plain one).
     {
         // stage scalar L <-> output scalar 3 s - phase + L; the packed stream is stage[phase, end)
         const unsigned end = phase + 3u * nvalid;
         T* const out = xyz + (3 * (size_t)s - phase);                // (16-byte aligned: 3 s - phase is a multiple of V)
-        typedef typename RawRec<float>::type Raw16;                  // 16 bytes
         const unsigned v0 = (phase + V - 1) / V, v1 = end / V;       // whole chunks [v0, v1)
         for (unsigned c = v0 + tid; c < v1; c += kSortThreads)
-            reinterpret_cast<Raw16*>(out)[c] = reinterpret_cast<const Raw16*>(st)[c];
+            store16_wt(reinterpret_cast<Chunk16*>(out) + c, reinterpret_cast<const Chunk16*>(st)[c]);
         if (tid < V) {                                               // the partial chunks at both ends, scalar by scalar
             const unsigned La = phase + tid;                         // head: [phase, min(v0 V, end))
             if (La < min(v0 * V, end)) out[La] = st[La];
@@ -587,12 +634,27 @@ __device__ __forceinline__ void sort2_body(const int b, const Build2Side<T>& a, 
             if (v1 >= v0 && Lb < end) out[Lb] = st[Lb];
         }
     }
+    {
+        // stage word L <-> output word s - iph + L; the id stream is stage[iph, iend)
+        const unsigned iend = iph + nvalid;
+        int* const iout = idx32 + s - iph;                           // (16-byte aligned by the choice of iph; never dereferenced below word iph)
+        const unsigned w0 = (iph + 3u) / 4u, w1 = iend / 4u;         // whole chunks [w0, w1)
+        for (unsigned c = w0 + tid; c < w1; c += kSortThreads)
+            store16_wt(reinterpret_cast<Chunk16*>(iout) + c, reinterpret_cast<const Chunk16*>(sidx0)[c]);
+        if (tid >= 64 && tid < 68) {                                 // (the second wave's first lanes: the first wave's have the coordinates' ends)
+            const unsigned t = (unsigned)tid - 64u;
+            const unsigned La = iph + t;                             // head: [iph, min(4 w0, iend))
+            if (La < min(w0 * 4u, iend)) iout[La] = sidx0[La];
+            const unsigned Lb = max(w1 * 4u, w0 * 4u) + t;           // tail: [4 max(w1, w0), iend)
+            if (w1 >= w0 && Lb < iend) iout[Lb] = sidx0[Lb];
+        }
+    }
     S2_PROF(4);                                    // copies issued
     if (prof) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); S2_PROF(5); if (tid == 0) atomicAdd((unsigned long long*)&prof[7], 1ull); }
 #undef S2_PROF
 }
 
-// One bucket: its output offset and fill, then the path that fits it.
+// One bucket: its fill, then the path that fits it.
 template <typename T>
 __device__ __forceinline__ void sort2_bucket(const int b, const Build2Side<T>& a, const int cnt_cap) {
     // dynamic LDS: [cnt_cap counters][kStageRecs records]
@@ -605,28 +667,15 @@ __device__ __forceinline__ void sort2_bucket(const int b, const Build2Side<T>& a
     const int CB = 1 << a.shift;
     const int NB = (uniform(a.gp->ncells) + CB - 1) >> a.shift;
     if (b >= NB) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     long long t_prev = a.prof ? wall_clock64() : 0;
-    // output offset = the points of the buckets before this one
-    unsigned s;
-    {
-        unsigned part = 0;
-        for (int i = tid; i < b; i += kSortThreads) part += (unsigned)(a.fill[i] >> 32);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-        if (lane == 0) s_w[wave] = part;
-        for (int i = tid; i < CB; i += kSortThreads) s_cnt[i] = 0u;
-        __syncthreads();
-        s = 0;
-        for (int w = 0; w < kSortThreads / 64; ++w) s += s_w[w];
-        __syncthreads();
-    }
-    if (a.prof && tid == 0) { const long long t_now = wall_clock64(); atomicAdd((unsigned long long*)&a.prof[0], (unsigned long long)(t_now - t_prev)); t_prev = t_now; }      // head
+    // The bucket's own fill word and the words its output offset is folded from (sort2_head_fold, inside the body) in ONE round trip.
     const unsigned long long fw = a.fill[b];
-    const unsigned pf = min((unsigned)fw, a.cap), nvalid = (unsigned)(fw >> 32);
+    unsigned long long hw[kHeadTrips];
+    sort2_head_request<T>(a, b, hw);
+    const unsigned pf = min((unsigned)uniform(fw), a.cap), nvalid = (unsigned)(uniform(fw) >> 32);
     static_assert(kSortThreads * kSortIters >= kLargeBucket, "one trip per record of a full slot");
-    if (pf <= (unsigned)(kRegIters * kSortThreads) && nvalid <= (unsigned)kStageRecs) sort2_body<T, true>(b, a, cnt_cap, s, pf, nvalid, s_cnt, s_stage, s_w, s_q, t_prev);      // (uniform in the block)
-    else sort2_body<T, false>(b, a, cnt_cap, s, pf, nvalid, s_cnt, s_stage, s_w, s_q, t_prev);
+    if (pf <= (unsigned)(kRegIters * kSortThreads) && nvalid <= (unsigned)kStageRecs) sort2_body<T, true>(b, a, cnt_cap, hw, pf, nvalid, s_cnt, s_stage, s_w, s_q, t_prev);      // (uniform in the block)
+    else sort2_body<T, false>(b, a, cnt_cap, hw, pf, nvalid, s_cnt, s_stage, s_w, s_q, t_prev);
 }
 
 // (the side's arguments through an index into the kernel-argument segment, see k_bucket_onepass3)

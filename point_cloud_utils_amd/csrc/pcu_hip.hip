@@ -1918,6 +1918,12 @@ static size_t pair_bytes(int64_t nx, int64_t ny, double occ_x, double occ_y, boo
 // wave-per-query pass -- a launch on the critical path of every call for a few hundred queries -- runs only when a direction's lists are not
 // empty afterwards (fused_needs_wave; then: wave pass + a second fold).
 static int wait_result_block(pcu_hip_ctx* c, hipStream_t s);
+// The launch that ends a fused call (reduce.h): the instantiation of the call's epilogue.
+template <typename T>
+static void fuse_tail_launch(hipStream_t s, const FuseTail<T>& t) {
+    if (t.mode == FUSE_SUM) hipLaunchKernelGGL((k_fuse_tail<T, FUSE_SUM>), dim3(1), dim3(kTailThreads), 0, s, t);
+    else hipLaunchKernelGGL((k_fuse_tail<T, FUSE_ARGMAX>), dim3(1), dim3(kTailThreads), 0, s, t);
+}
 template <typename T>
 static int pair_search_enqueue(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, pcu_hip_stats* st) {
     const bool lazy_wave = P.fuse && P.two && lane_k1_job(P.xy) && lane_k1_job(P.yx);
@@ -1926,7 +1932,7 @@ static int pair_search_enqueue(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, p
     P.wave_pending = lazy_wave;
     if (P.fuse) {               // the launch that ends a fused call (reduce.h)
         P.tail.nwaves = lazy_wave ? 0 : kWaveBlocks * (kBlock / 64);       // (no wave pass yet: its per-wave slots hold nothing)
-        hipLaunchKernelGGL(k_fuse_tail<T>, dim3(1), dim3(kTailThreads), 0, s, P.tail);
+        fuse_tail_launch<T>(s, P.tail);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -1947,7 +1953,7 @@ static int fused_wave_if_needed(pcu_hip_ctx* c, hipStream_t s, PairState<T>& P, 
     if (!need || broken) return 0;            // (a pass that gave up listed nothing: the row-based path takes the call over)
     if (search_enqueue_pair(c, s, P.xy, P.yx, st, 2)) return -1;
     P.tail.nwaves = kWaveBlocks * (kBlock / 64); P.tail.seq = ++c->seq;
-    hipLaunchKernelGGL(k_fuse_tail<T>, dim3(1), dim3(kTailThreads), 0, s, P.tail);
+    fuse_tail_launch<T>(s, P.tail);
     HIP_TRY(hipGetLastError());
     if (wait_result_block(c, s)) return -1;
     memcpy(&host, c->h_pinned, sizeof host);
@@ -2108,7 +2114,7 @@ static int fused_continue(pcu_hip_ctx* c, Arena& ar, hipStream_t s, PairState<T>
         if (int r = search_finish(c, ar, s, d ? P.yx : P.xy, st, host.counters[d], fin)) return r;
     }
     P.tail.seq = ++c->seq;
-    hipLaunchKernelGGL(k_fuse_tail<T>, dim3(1), dim3(kTailThreads), 0, s, P.tail);
+    fuse_tail_launch<T>(s, P.tail);
     HIP_TRY(hipGetLastError());
     if (wait_result_block(c, s)) return -1;
     memcpy(&host, c->h_pinned, sizeof host);

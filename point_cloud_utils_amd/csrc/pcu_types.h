@@ -58,8 +58,19 @@ __device__ __forceinline__ unsigned long long uniform(unsigned long long v) {
 }
 __device__ __forceinline__ double uniform(double v) { return __longlong_as_double((long long)uniform((unsigned long long)__double_as_longlong(v))); }
 
+// A 16-byte WRITE-THROUGH store (`sc1`): the bytes go to memory as the store retires and their line does not stay in the XCD's L2. For the bulk
+// output of a kernel whose readers all run in the NEXT kernel, on whatever XCD: a plain store parks the line dirty in the L2 and the kernel
+// boundary waits for the write-back (dirty bytes / ~6 TB/s with the GPU idle), a write-through store drains under the work that follows it.
+// Only at 16 bytes per lane: narrower write-through stores are one fabric write each (2.7x -- 12x the time per byte). The asm reads no memory
+// and nobody in the storing kernel may read what it writes (visibility comes with the kernel boundary, as for a plain store), so it carries
+// no memory clobber; the trailing s_nop keeps the compiler's next instruction off the data registers until the store has read them.
+typedef unsigned __attribute__((ext_vector_type(4))) Chunk16;
+__device__ __forceinline__ void store16_wt(void* p, const Chunk16 v) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v));
+}
+
 template <typename T> struct Limits;
-template <> struct Limits<float>  { static constexpr float  max_v = FLT_MAX; static constexpr float  eps = FLT_EPSILON; };
+template <> struct Limits<float> { static constexpr float  max_v = FLT_MAX; static constexpr float  eps = FLT_EPSILON; };
 template <> struct Limits<double> { static constexpr double max_v = DBL_MAX; static constexpr double eps = DBL_EPSILON; };
 
 // Order-preserving float -> unsigned encoding, so that bbox min/max can use integer atomics.

@@ -227,9 +227,12 @@ struct VK { double v; long long k; };           // (value widened to double: exa
 __device__ __forceinline__ VK comb_max(VK a, VK b) { return (b.v > a.v || (b.v == a.v && b.k < a.k)) ? b : a; }
 __device__ __forceinline__ VK shfl_vk(VK a, int o) { VK r; r.v = __shfl_xor(a.v, o, 64); r.k = __shfl_xor(a.k, o, 64); return r; }
 
-// The fold as a block-level routine of NT threads (the sums do not depend on NT: tail_sum).
-template <typename T, int NT>
+// The fold as a block-level routine of NT threads (the sums do not depend on NT: tail_sum). MODE = the call's FuseTail::mode, at compile time:
+// the FUSE_SUM instantiation holds the sum fold and the hand-off only -- a few hundred instructions that a lone block fetches into a cold
+// instruction cache at the end of every Chamfer step, instead of the 2500 with the arg-max fold and the 5 x 5 x 5 resolution behind them.
+template <typename T, int NT, int MODE>
 __device__ __forceinline__ void fuse_tail_body(const FuseTail<T>& ft) {
+    static_assert(MODE == FUSE_SUM || MODE == FUSE_ARGMAX, "the two fused epilogues");
     __shared__ double s_d[kTailLanes / 64]; __shared__ double s_mv[NT / 64]; __shared__ long long s_mk[NT / 64];
     __shared__ int s_res[64]; __shared__ unsigned long long s_mask;
     constexpr int kTailThreads = NT, V = kTailLanes / NT;
@@ -244,7 +247,7 @@ __device__ __forceinline__ void fuse_tail_body(const FuseTail<T>& ft) {
 #pragma unroll
     for (int jb = 0; jb < 2; ++jb) {           // (constant trip count + unroll: the per-direction values stay in registers)
         if (jb >= ft.njobs) continue;
-        if (ft.mode == FUSE_SUM) {
+        if (MODE == FUSE_SUM) {
             // virtual thread vt = tid + q * NT: its strided partials (in order), then its limb term. The loads of a batch of kBatch trips
             // of all V virtual threads are requested together and only then added, in the fixed order: a plain `acc += p[i]` loop is a
             // chain of dependent L2 round trips (8 per thread at 1M-vs-1M, which WAS the 7 us of this fold).
@@ -289,7 +292,7 @@ __device__ __forceinline__ void fuse_tail_body(const FuseTail<T>& ft) {
     }
     TAIL_PROF(0);                                   // partials in, combined per thread
     if (tid == 0) s_mask = 0ull;
-    if (ft.mode == FUSE_SUM && V == 1) {
+    if (MODE == FUSE_SUM && V == 1) {
         // tail_sum's order (butterfly inside a wave, the 16 wave sums added in order) for both directions behind ONE pair of barriers
         __shared__ double s_ws[2][kTailLanes / 64];
         double w[2] = {acc[0][0], acc[1][0]};
@@ -310,7 +313,7 @@ __device__ __forceinline__ void fuse_tail_body(const FuseTail<T>& ft) {
                 *reinterpret_cast<double*>(&s_res[ft.w_sums + 2 * jb]) = r; s_mask |= 3ull << (ft.w_sums + 2 * jb);
             }
         }
-    } else if (ft.mode == FUSE_SUM) {
+    } else if (MODE == FUSE_SUM) {
 #pragma unroll
         for (int jb = 0; jb < 2; ++jb) {
             if (jb >= ft.njobs) continue;
@@ -384,8 +387,8 @@ __device__ __forceinline__ void fuse_tail_body(const FuseTail<T>& ft) {
         if (tid == 63) __hip_atomic_store(&ft.host_block[63], (int)ft.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
-template <typename T>
-__global__ __launch_bounds__(1024) void k_fuse_tail(const FuseTail<T> ft) { fuse_tail_body<T, 1024>(ft); }
+template <typename T, int MODE>
+__global__ __launch_bounds__(1024) void k_fuse_tail(const FuseTail<T> ft) { fuse_tail_body<T, 1024, MODE>(ft); }
 
 // Hausdorff, row-based path: is the arg-max source row (ij[0], in the call's result block) one of the direction's queries
 // with a genuine tie? Only then does the returned j depend on the reference's tie order (pcu_hip.hip, hausdorff_end).
