@@ -38,7 +38,7 @@ CANCEL_BY_SIGINT = 2        # ... or the chained SIGINT handler
 _COMPUTE_ENTRY_POINTS = [f"pcu_hip_{op}_{suf}" for suf in ("f32", "f64") for op in (
     "knn", "one_sided_hausdorff", "hausdorff", "chamfer", "index_create", "index_knn", "hausdorff_batch", "chamfer_batch", "normals_knn",
     "normals_ball", "dedup", "pairwise", "sinkhorn", "dot", "debug_kd_tree", "poisson_disk", "closest_points_on_mesh", "mesh_index_create",
-    "mesh_index_closest")] + [
+    "mesh_index_closest", "ray_mesh_intersection", "mesh_index_rays")] + [
     "pcu_hip_morton_encode", "pcu_hip_morton_decode", "pcu_hip_morton_addsub", "pcu_hip_morton_knn"] + [
     f"pcu_hip_voxel_downsample_{sp}_{sa}" for sp in ("f32", "f64") for sa in ("f32", "f64")]
 
@@ -120,6 +120,9 @@ def lib():
             getattr(L, "pcu_hip_closest_points_on_mesh_" + sp).argtypes = [vp, vp, i64, vp, i64, ci, vp, i64, vp, vp, vp, u, vp, vp]
             getattr(L, "pcu_hip_mesh_index_create_" + sp).argtypes = [vp, vp, i64, vp, i64, ci, u, vp, ctypes.POINTER(ctypes.c_void_p)]
             getattr(L, "pcu_hip_mesh_index_closest_" + sp).argtypes = [vp, vp, vp, i64, vp, vp, vp, u, vp, vp]
+            dbl = ctypes.c_double
+            getattr(L, "pcu_hip_ray_mesh_intersection_" + sp).argtypes = [vp, vp, i64, vp, i64, ci, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, u, vp, vp]
+            getattr(L, "pcu_hip_mesh_index_rays_" + sp).argtypes = [vp, vp, vp, i64, vp, i64, dbl, dbl, vp, vp, vp, u, vp, vp]
         for sp in ("f32", "f64"):
             getattr(L, "pcu_hip_pairwise_" + sp).argtypes = [vp, vp, vp, i64, i64, i64, i64, ctypes.c_double, vp, u, vp]
             getattr(L, "pcu_hip_sinkhorn_" + sp).argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_double, ci, ctypes.c_double, vp, vp, u, vp]

@@ -16,6 +16,22 @@ def _face_dtype_name(f):
     return np.asarray(f).dtype.name
 
 
+def _check_scalar_v(v):
+    from . import _dtype_name
+    dv = _dtype_name(v)
+    if dv not in ("float32", "float64"):
+        raise ValueError(f"Invalid scalar type ({dv}) for argument 'v'. Expected one of ['float32', 'float64'].")
+    return dv
+
+
+def _check_face_dtype(f):
+    from . import _is_torch
+    df = _face_dtype_name(f)
+    kinds = ["int32", "int64"] if _is_torch(f) else list(_FACE_KINDS)
+    if df not in kinds:
+        raise ValueError(f"Invalid scalar type ({df}) for argument 'f'. Expected one of {kinds}.")
+
+
 def _check_mesh(v, f, want=None):
     """Scalar types, then validate_mesh (src/common/common.h:133-147), then this package's row limit. Returns (dtype name, #v, #f)."""
     from . import _dtype_name, _is_torch, _shape2
@@ -133,6 +149,137 @@ def closest_points_on_mesh(p, v, f):
     return _finish(dist, fi, bc, ff, n)
 
 
+_RAY_ROWS = ("ray_o and ray_d must have the same number of rows (one ray origin per ray direction). "
+             "(Note: ray_o can have one row to use the same origin for all directions)")
+
+
+def _size(a):
+    n = 1
+    for x in a.shape:
+        n *= int(x)
+    return n
+
+
+def _check_rays(ray_o, ray_d, want, match):
+    """Scalar types (both must be `want`; `match` names what that is), then the reference's shape checks in its order
+    (src/ray_mesh_intersection.cpp:117-134). Returns (#rays, single origin?)."""
+    from . import _dtype_name, _shape2
+    for name, a in (("ray_o", ray_o), ("ray_d", ray_d)):
+        dt = _dtype_name(a)
+        if dt != want:
+            raise ValueError(f"Invalid scalar type ({dt}) for argument '{name}'. Expected it to match {match} which is of type {want}.")
+    so, sd = _shape2(ray_o), _shape2(ray_d)
+    single = _size(ray_o) == 3
+    if not single and so[0] != sd[0]:
+        raise ValueError(_RAY_ROWS)
+    if so[1] != 3 and not single:
+        raise ValueError(f"Invalid shape for ray_o must have shape (N, 3) but got ({so[0]}, {so[1]}).")
+    if sd[1] != 3:
+        raise ValueError(f"Invalid shape for ray_d must have shape (N, 3) but got ({sd[0]}, {sd[1]}).")
+    return sd[0], single
+
+
+def _check_ray_limits(n, ray_near, ray_far):
+    if n > _MAX_ROWS:
+        raise ValueError("meshes and point clouds with more than 2^27-16 rows are not supported")
+    ray_near, ray_far = float(ray_near), float(ray_far)
+    if ray_near != ray_near or ray_far != ray_far:
+        raise ValueError("ray_near and ray_far must not be NaN")
+    return ray_near, ray_far
+
+
+def _host_ray_checks(ray_o, ray_d):
+    if not bool(np.isfinite(ray_o).all()):
+        raise ValueError("ray_o must not contain NaN or infinite coordinates")
+    if not bool(np.isfinite(ray_d).all()):
+        raise ValueError("ray_d must not contain NaN or infinite coordinates")
+
+
+def _origins_for(d, ray_o, single):
+    """ray_o next to the resolved arrays of a call (_faces_for), as (1, 3) or (n, 3). Returns (array, rows)."""
+    oo = _faces_for(d, ray_o)
+    if single:
+        oo = oo.reshape(1, 3)
+    return oo, int(oo.shape[0])
+
+
+def _ray_results(d, n):
+    return d.empty((n,), "i64"), d.empty((n, 3), "T"), d.empty((n,), "T")
+
+
+def _finish_rays(fi, bc, t, like, n):
+    """f_id in the dtype of `like` (-1 wraps for an unsigned one, as the reference's assignment does); one ray: squeezed as _finish does."""
+    from . import _is_torch
+    fi = fi.to(like.dtype) if _is_torch(fi) else fi.astype(like.dtype, copy=False)
+    if n == 1:
+        return fi.reshape(()), bc.reshape(3), t.reshape(())
+    return fi, bc, t
+
+
+def ray_mesh_intersection(v, f, ray_o, ray_d, ray_near=0.0, ray_far=np.inf):
+    """
+    Compute intersection between a set of rays and a triangle mesh
+
+    Args:
+      v : (#v, 3)-shaped array of mesh vertex positions (float32 or float64; numpy, or a CUDA/HIP torch tensor)
+      f : (#f, 3)-shaped array of triangle face indices (int32, int64, uint32 or uint64; int32 / int64 for torch)
+      ray_o : array of shape (#rays, 3) of ray origins (one per row) or an array of three elements, (3,) or (1, 3), used for all rays (v's dtype)
+      ray_d : array of shape (#rays, 3) of ray directions (one per row; v's dtype; not normalised: t is in units of the direction's length)
+      ray_near : an optional floating point value indicating the distance along each ray to start searching (default 0.0)
+      ray_far : an optional floating point value indicating the maximum distance along each ray to search (default inf)
+
+    Returns:
+      f_id : an array of shape (#rays,) representing the face id hit by each ray (f's dtype; -1 for a miss)
+      bc : an array of shape (#rays, 3) where each row is the barycentric coordinates within each face of the ray intersection (0 for a miss)
+      t : the distance along each ray to the intersection (inf for a miss)
+
+    Notes:
+      Every face is tested by one watertight ray / triangle test (Woop, Benthin, Wald 2013) in the input dtype: a ray through an edge or a vertex
+      shared by faces hits one of them. The nearest crossing with ray_near <= t <= ray_far is returned, among faces of exactly equal t the
+      lowest face index. A zero direction, a face of no area and a face seen exactly edge-on are misses; ray_near > ray_far gives all misses.
+      Non-finite coordinates, NaN ray_near / ray_far, face indices outside [0, #v) and arrays of more than 2**27 - 16 rows raise ValueError.
+    """
+    from . import _lib, _Dev, _fn, _is_torch, _record, Stats
+    dv = _check_scalar_v(v)
+    _check_face_dtype(f)
+    n, single = _check_rays(ray_o, ray_d, dv, "argument 'v'")
+    _, nv, nf = _check_mesh(v, f)
+    ray_near, ray_far = _check_ray_limits(n, ray_near, ray_far)
+    if not (_is_torch(v) or _is_torch(f) or _is_torch(ray_o) or _is_torch(ray_d)):
+        _host_mesh_checks(np.asarray(v), np.asarray(f))
+        _host_ray_checks(np.asarray(ray_o), np.asarray(ray_d))
+    d = _Dev(ray_d, v)
+    ff = _faces_for(d, f)
+    oo, o_rows = _origins_for(d, ray_o, single)
+    fi, bc, t = _ray_results(d, n)
+    st = Stats()
+    rc = _fn("ray_mesh_intersection", d.suffix)(d.ctx, d.pb, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)], _Dev.ptr(oo), o_rows, d.pa, n,
+                                                ray_near, ray_far, _Dev.ptr(fi), _Dev.ptr(bc), _Dev.ptr(t), d.flags, d.stream, ctypes.addressof(st))
+    if rc:
+        _lib.check(rc)
+    _record(st)
+    return _finish_rays(fi, bc, t, ff, n)
+
+
+def interpolate_barycentric_coords(f, fi, bc, attribute):
+    """
+    Interpolate an attribute stored at each vertex of a mesh across the faces of a triangle mesh using barycentric coordinates
+
+    Args:
+      f : a (#faces, 3)-shaped array of mesh faces (indexing into some vertex array)
+      fi : a (#attribs,)-shaped array of indexes into f indicating which face each attribute lies within
+      bc : a (#attribs, 3)-shaped array of barycentric coordinates for each attribute
+      attribute : a (#vertices, dim)-shaped array of attributes at each of the mesh vertices
+
+    Returns:
+      A (#attribs, dim)-shaped array of interpolated attributes (numpy arrays or torch tensors, as given).
+    """
+    from . import _is_torch
+    if _is_torch(attribute):
+        return (attribute[f.long()[fi.long()]] * bc[:, :, None]).sum(1)
+    return (attribute[f[fi]] * bc[:, :, np.newaxis]).sum(1)
+
+
 class MeshIndex:
     """A triangle mesh kept on the GPU as its search index (not in the reference API, which rebuilds libigl's AABB tree on every call): build
     once, query many times.
@@ -178,13 +325,40 @@ class MeshIndex:
         if rc:
             _lib.check(rc)
         _record(st)
+        return _finish(dist, fi, bc, self._like_for(d), n)
+
+    def _like_for(self, d):
+        """An empty array of f's dtype and of the kind (numpy / torch) of the call's results."""
+        from . import _is_torch
         like = self._face_like
         if _is_torch(like) and not d.torch:          # index built from tensors, numpy queries: numpy results
             like = np.empty((0,), dtype=str(like.dtype).replace("torch.", ""))
         elif d.torch and not _is_torch(like):
             import torch
             like = torch.empty((0,), dtype=getattr(torch, like.dtype.name if like.dtype.kind == "i" else "int64"))
-        return _finish(dist, fi, bc, like, n)
+        return like
+
+    def intersect_rays(self, ray_o, ray_d, ray_near=0.0, ray_far=np.inf):
+        """See point_cloud_utils_amd.ray_mesh_intersection; the mesh is the indexed one and the rays must have its dtype."""
+        from . import _lib, _Dev, _fn, _record, _is_torch, Stats
+        if self._h is None:
+            raise ValueError("the mesh index has been closed")
+        n, single = _check_rays(ray_o, ray_d, self._dtype_name, "the indexed mesh")
+        ray_near, ray_far = _check_ray_limits(n, ray_near, ray_far)
+        if not (_is_torch(ray_o) or _is_torch(ray_d)):
+            _host_ray_checks(np.asarray(ray_o), np.asarray(ray_d))
+        d = _Dev(ray_d, ray_d)
+        if d.device != self._device:
+            raise ValueError("rays and mesh index live on different devices")
+        oo, o_rows = _origins_for(d, ray_o, single)
+        fi, bc, t = _ray_results(d, n)
+        st = Stats()
+        rc = _fn("mesh_index_rays", d.suffix)(d.ctx, self._h, _Dev.ptr(oo), o_rows, d.pa, n, ray_near, ray_far, _Dev.ptr(fi), _Dev.ptr(bc), _Dev.ptr(t),
+                                              d.flags, d.stream, ctypes.addressof(st))
+        if rc:
+            _lib.check(rc)
+        _record(st)
+        return _finish_rays(fi, bc, t, self._like_for(d), n)
 
     def close(self):
         if getattr(self, "_h", None) is not None:
@@ -204,3 +378,67 @@ class MeshIndex:
             self.close()
         except Exception:
             pass
+
+
+class RayMeshIntersector:
+    """
+    Class used to find the intersection between rays and a triangle mesh (the reference's point_cloud_utils.RayMeshIntersector): the mesh is
+    indexed once (a MeshIndex) and queried many times. f_id comes back as int32 and bc, t in ray_o's dtype, as in the reference; rays of the
+    other float dtype are converted to the mesh's. close() (or `with`) frees the index.
+    """
+    def __init__(self, mesh_v, mesh_f):
+        """
+        Create a RayMeshIntersector object which can be used to do ray/mesh queries with a triangle mesh.
+
+        Args:
+          mesh_v : #v by 3 array of vertex positions (each row is a vertex)
+          mesh_f : #f by 3 Matrix of face (triangle) indices
+        """
+        self.v = mesh_v
+        self.f = mesh_f
+        self._index = MeshIndex(mesh_v, mesh_f)
+
+    def intersect_rays(self, ray_o, ray_d, ray_near=0.0, ray_far=np.inf):
+        """
+        Compute intersection between a set of rays and the triangle mesh enclosed in this class
+
+        Args:
+          ray_o : array of shape (#rays, 3) of ray origins (one per row) or a single array of shape (3,) to use
+          ray_d : array of shape (#rays, 3) of ray directions (one per row)
+          ray_near : an optional floating point value indicating the distance along each ray to start searching (default 0.0)
+          ray_far : an optional floating point value indicating the maximum distance along each ray to search (default inf)
+
+        Returns:
+          f_id : an array of shape (#rays,) representing the face id hit by each ray
+          bc : an array of shape (#rays, 3) where each row is the barycentric coordinates within each face of the ray intersection
+          t : the distance along each ray to the intersection
+        """
+        from . import _dtype_name, _is_torch
+        do = _dtype_name(ray_o)
+        if do not in ("float32", "float64"):
+            raise ValueError(f"Invalid scalar type ({do}) for argument 'ray_o'. Expected one of ['float32', 'float64'].")
+        dd = _dtype_name(ray_d)
+        if dd != do:
+            raise ValueError(f"Invalid scalar type ({dd}) for argument 'ray_d'. Expected it to match argument 'ray_o' which is of type {do}.")
+        want = self._index._dtype_name
+        if do != want:
+            conv = (lambda a: a.to(getattr(__import__("torch"), want))) if _is_torch(ray_o) else (lambda a: np.asarray(a).astype(want))
+            fi, bc, t = self._index.intersect_rays(conv(ray_o), conv(ray_d), ray_near, ray_far)
+            back = (lambda a: a.to(ray_o.dtype)) if _is_torch(ray_o) else (lambda a: a.astype(do))
+            bc, t = back(bc), back(t)
+        else:
+            fi, bc, t = self._index.intersect_rays(ray_o, ray_d, ray_near, ray_far)
+        if _is_torch(fi):
+            import torch
+            return fi.to(torch.int32), bc, t
+        return fi.astype(np.int32), bc, t
+
+    def close(self):
+        self._index.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+        return False

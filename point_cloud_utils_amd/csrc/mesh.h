@@ -323,4 +323,215 @@ __global__ __launch_bounds__(kMeshBlock) void k_mesh_closest(const MeshQuery<T> 
     a.out_bc[3 * (size_t)row] = u; a.out_bc[3 * (size_t)row + 1] = bv; a.out_bc[3 * (size_t)row + 2] = bw;
 }
 
+// ---------------------------------------------------------------------------------------------------- rays
+// ray_mesh_intersection: replaces npe_function(ray_mesh_intersection) (src/ray_mesh_intersection.cpp:107-177, Embree through libigl, always in
+// float32). Embree's bits cannot be reproduced, so the operator has a contract of its own that does not depend on the index. All arithmetic in
+// T, separate multiplies and adds, IEEE division; S as above.
+//   per ray    kz = the dominant axis of d (0 if |d0| >= |d1| and |d0| >= |d2|, else 1 if |d1| >= |d2|, else 2), kx = (kz+1)%3, ky = (kx+1)%3,
+//              kx and ky swapped if d[kz] < 0; Sx = d[kx]/d[kz], Sy = d[ky]/d[kz], Sz = 1/d[kz]; inv[k] = 1/d[k];
+//              pad = max(16 eps S, 16 eps max_k |o[k]|)
+//   per face   HIT(ray, a, b, c) -> (hit, t, b1, b2):
+//              1 the watertight test (Woop, Benthin, Wald, JCGT 2013, without its double-precision fallback): A = a - o (B, C alike),
+//                Ax = A[kx] - Sx*A[kz], Ay = A[ky] - Sy*A[kz], Az = Sz*A[kz]; U = Cx*By - Cy*Bx, V = Ax*Cy - Ay*Cx, W = Bx*Ay - By*Ax;
+//                reject if (U<0 || V<0 || W<0) && (U>0 || V>0 || W>0); det = (U+V)+W, reject if det == 0;
+//                t = ((U*Az + V*Bz) + W*Cz)/det, b1 = V/det, b2 = W/det
+//              2 the window: accept only if t >= near && t <= far
+//              3 the box clip: (t_in, t_out) = BOX(o, inv, min(a,b,c) - pad, max(a,b,c) + pad); accept only if t_in <= t && t <= t_out
+//              BOX per axis: t1 = (lo[k]-o[k])*inv[k], t2 = (hi[k]-o[k])*inv[k]; t_in = fmax over k of fmin(t1,t2), t_out = fmin over k of fmax(t1,t2)
+//   per ray    the smallest accepted t, the LOWEST face index among equal t; hit: face, bc = ((1-b1)-b2, b1, b2), t; miss: -1, 0, +inf.
+// The edge function of a directed edge is the same two products whichever face evaluates it and, without FMA, its exact negation for the
+// reversed edge: a ray through a shared edge or vertex cannot slip between two faces.
+// Pruning that cannot change the result: rounded subtraction, multiplication, fmin and fmax are monotone, so BOX is monotone in its box. A
+// face's clip box lies inside (node box - pad, node box + pad) of every node that holds it (node boxes are the faces' boxes padded by 16 eps S
+// already), so a face step 3 accepts at t has t_in(node) <= t <= t_out(node): a node is skipped only if !(t_in <= min(far, best)) ||
+// !(t_out >= near) || !(t_in <= t_out), or if it is a padding node (the empty box). A node whose t_in EQUALS the best t is visited.
+constexpr int kMeshBadOrigin = 1, kMeshBadDir = 2;
+
+template <typename T> __device__ __forceinline__ bool mesh_finite3(const T* p) {
+    return (p[0] - p[0] == (T)0) && (p[1] - p[1] == (T)0) && (p[2] - p[2] == (T)0);
+}
+// Sort key of every ray, so that the lanes of a wave walk the same nodes: the 7-bit-per-axis Morton cell of the point where the ray enters the
+// mesh's bounding box (the origin if it is inside; a ray that misses the box gets the cell of a clamped point), then 11 bits of direction
+// (dominant axis and sign, the other two components over the dominant one in 16 steps each). Results do not depend on it. Non-finite rows
+// are flagged. o_stride is 0 (one origin for all rays) or 3.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_mesh_rkeys(const T* __restrict__ o, int o_stride, const T* __restrict__ d, int n, const MeshHead<T>* __restrict__ h,
+                                                       unsigned long long* __restrict__ keys, int* __restrict__ bad) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    bool bad_o = false, bad_d = false;
+    if (i < n) {
+        const T* po = o + (size_t)o_stride * i;
+        const T* pd = d + 3 * (size_t)i;
+        bad_o = !mesh_finite3(po); bad_d = !mesh_finite3(pd);
+        const double oo[3] = {(double)po[0], (double)po[1], (double)po[2]}, dd[3] = {(double)pd[0], (double)pd[1], (double)pd[2]};
+        double t_in = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double inv = 1.0 / dd[k];
+            const double t1 = ((double)dec(h->elo[k]) - oo[k]) * inv, t2 = ((double)dec(h->ehi[k]) - oo[k]) * inv;
+            t_in = fmax(t_in, fmin(t1, t2));
+        }
+        unsigned cell[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cell[k] = mesh_cell(((oo[k] + t_in * dd[k]) - (double)h->lo[k]) * (double)h->inv[k] * (1.0 / 16384.0), 127u);
+        const double a0 = fabs(dd[0]), a1 = fabs(dd[1]), a2 = fabs(dd[2]);
+        const int kz = (a0 >= a1 && a0 >= a2) ? 0 : (a1 >= a2 ? 1 : 2);
+        const double dz = kz == 0 ? dd[0] : (kz == 1 ? dd[1] : dd[2]), du = kz == 0 ? dd[1] : (kz == 1 ? dd[2] : dd[0]), dv = kz == 0 ? dd[2] : (kz == 1 ? dd[0] : dd[1]);
+        const double s = 8.0 / fabs(dz);
+        const unsigned dir = ((unsigned)kz * 2u + (dz < 0.0 ? 1u : 0u)) << 8 | mesh_cell(du * s + 8.0, 15u) << 4 | mesh_cell(dv * s + 8.0, 15u);
+        keys[i] = (morton_split21(cell[0]) | morton_split21(cell[1]) << 1 | morton_split21(cell[2]) << 2) << 11 | dir;
+    }
+    const unsigned long long any_o = __ballot(bad_o), any_d = __ballot(bad_d);
+    if ((any_o | any_d) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, (any_o ? kMeshBadOrigin : 0) | (any_d ? kMeshBadDir : 0));
+}
+constexpr int kMeshRayKeyBits = 32;
+
+template <typename T>
+struct MeshRay {                                // one ray, its axes already permuted: x, y the sheared axes, z the dominant one
+    T o[3], inv[3];                             // origin and slab reciprocals, in the caller's axis order
+    T ox, oy, oz, Sx, Sy, Sz, pad, near, far;
+    int kx, ky, kz;
+};
+template <typename T> __device__ __forceinline__ T mesh_pick(const T* p, int k) { return k == 0 ? p[0] : (k == 1 ? p[1] : p[2]); }
+
+// BOX of the contract for the box (lo - pad, hi + pad)
+template <typename T>
+__device__ __forceinline__ void mesh_ray_box(const MeshRay<T>& r, const T lo[3], const T hi[3], T& t_in, T& t_out) {
+    T n[3], f[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const T t1 = ((lo[k] - r.pad) - r.o[k]) * r.inv[k], t2 = ((hi[k] + r.pad) - r.o[k]) * r.inv[k];
+        n[k] = fmin(t1, t2); f[k] = fmax(t1, t2);
+    }
+    t_in = fmax(fmax(n[0], n[1]), n[2]); t_out = fmin(fmin(f[0], f[1]), f[2]);
+}
+// whether a node can hold a face that beats `best` (see "Pruning" above); t_in orders the children
+template <typename T>
+__device__ __forceinline__ bool mesh_ray_node(const MeshRay<T>& r, const T* __restrict__ bx, T best, T& t_in) {
+    const T lo[3] = {bx[0], bx[1], bx[2]}, hi[3] = {bx[3], bx[4], bx[5]};
+    T t_out;
+    mesh_ray_box(r, lo, hi, t_in, t_out);
+    const T lim = r.far < best ? r.far : best;
+    return lo[0] <= hi[0] && t_in <= lim && t_out >= r.near && t_in <= t_out;
+}
+// HIT of the contract
+template <typename T>
+__device__ __forceinline__ bool mesh_ray_face(const MeshRay<T>& r, const T a[3], const T b[3], const T c[3], T& t, T& b1, T& b2) {
+    const T Az_ = mesh_pick(a, r.kz) - r.oz, Bz_ = mesh_pick(b, r.kz) - r.oz, Cz_ = mesh_pick(c, r.kz) - r.oz;
+    const T Ax = (mesh_pick(a, r.kx) - r.ox) - r.Sx * Az_, Ay = (mesh_pick(a, r.ky) - r.oy) - r.Sy * Az_;
+    const T Bx = (mesh_pick(b, r.kx) - r.ox) - r.Sx * Bz_, By = (mesh_pick(b, r.ky) - r.oy) - r.Sy * Bz_;
+    const T Cx = (mesh_pick(c, r.kx) - r.ox) - r.Sx * Cz_, Cy = (mesh_pick(c, r.ky) - r.oy) - r.Sy * Cz_;
+    const T U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    const T z = (T)0;
+    if ((U < z || V < z || W < z) && (U > z || V > z || W > z)) return false;
+    const T det = (U + V) + W;
+    if (det == z) return false;
+    const T Az = r.Sz * Az_, Bz = r.Sz * Bz_, Cz = r.Sz * Cz_;
+    t = ((U * Az + V * Bz) + W * Cz) / det;
+    if (!(t >= r.near && t <= r.far)) return false;
+    T lo[3], hi[3], t_in, t_out;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const T m = a[k] < b[k] ? a[k] : b[k], M = a[k] > b[k] ? a[k] : b[k];
+        lo[k] = m < c[k] ? m : c[k]; hi[k] = M > c[k] ? M : c[k];
+    }
+    mesh_ray_box(r, lo, hi, t_in, t_out);
+    if (!(t_in <= t && t <= t_out)) return false;
+    b1 = V / det; b2 = W / det;
+    return true;
+}
+
+template <typename T>
+struct MeshRays {
+    const T* o; int o_stride; const T* d; const unsigned* order; int n;
+    MeshIdx<T> ix;
+    T near, far;
+    long long* out_fi; T* out_bc; T* out_t;
+    const unsigned* cancel_word; unsigned cancel_gen;          // pcu_types.h: cancel_seen
+};
+
+// One lane per ray, rays in key order. The child the ray enters first is taken first, the other pushed if it passes the node test: at most one
+// entry per level, so the stack (LDS, one column per lane, as in k_mesh_closest) holds kMeshStack node ids. A popped node is tested again,
+// against the best t of that moment.
+template <typename T>
+__global__ __launch_bounds__(kMeshBlock) void k_mesh_rays(const MeshRays<T> a) {
+    __shared__ int s_stack[kMeshStack][kMeshBlock];
+    const int i = blockIdx.x * kMeshBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const unsigned row = a.order[i];
+    const T* po = a.o + (size_t)a.o_stride * row;
+    const T* pd = a.d + 3 * (size_t)row;
+    const T d[3] = {pd[0], pd[1], pd[2]};
+    MeshRay<T> r;
+    r.o[0] = po[0]; r.o[1] = po[1]; r.o[2] = po[2];
+    bool live = mesh_finite3(r.o) && mesh_finite3(d);          // (a non-finite row is refused by the host after the launch)
+    {
+        const T a0 = fabs(d[0]), a1 = fabs(d[1]), a2 = fabs(d[2]);
+        r.kz = (a0 >= a1 && a0 >= a2) ? 0 : (a1 >= a2 ? 1 : 2);
+        r.kx = r.kz == 2 ? 0 : r.kz + 1;
+        r.ky = r.kx == 2 ? 0 : r.kx + 1;
+        const T dz = mesh_pick(d, r.kz);
+        if (dz < (T)0) { const int k = r.kx; r.kx = r.ky; r.ky = k; }
+        r.Sx = mesh_pick(d, r.kx) / dz; r.Sy = mesh_pick(d, r.ky) / dz; r.Sz = (T)1 / dz;
+        r.ox = mesh_pick(r.o, r.kx); r.oy = mesh_pick(r.o, r.ky); r.oz = mesh_pick(r.o, r.kz);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) r.inv[k] = (T)1 / d[k];
+        T m = fabs(r.o[0]) > fabs(r.o[1]) ? fabs(r.o[0]) : fabs(r.o[1]);
+        m = m > fabs(r.o[2]) ? m : fabs(r.o[2]);
+        const T pad_o = (T)16 * Limits<T>::eps * m, pad_s = a.ix.head->pad;
+        r.pad = pad_s > pad_o ? pad_s : pad_o;
+        r.near = a.near; r.far = a.far;
+    }
+    const T* __restrict__ box = a.ix.box;
+    const T* __restrict__ tri = a.ix.tri;
+    const int first_leaf = a.ix.P - 1, nf = a.ix.nf;
+    T best = (T)INFINITY, bv = (T)0, bw = (T)0;
+    unsigned bf = 0xffffffffu;
+    int sp = 0, node = 0;
+    unsigned steps = 0;
+    long long t_poll = wall_clock64();
+    { T t_in; live = live && mesh_ray_node(r, box, best, t_in); }
+    while (live) {
+        if ((++steps & 63u) == 0u) { const long long t_now = wall_clock64(); if (t_now - t_poll > 20000ll) { t_poll = t_now; if (cancel_seen(a.cancel_word, a.cancel_gen)) return; } }
+        bool descend = false;
+        if (node >= first_leaf) {
+            const long long s0 = (long long)kMeshLeaf * (node - first_leaf);
+            for (int j = 0; j < kMeshLeaf; ++j) {
+                const long long s = s0 + j;
+                if (s >= nf) break;
+                const T* tr = tri + 9 * (size_t)s;
+                const T fa[3] = {tr[0], tr[1], tr[2]}, fb[3] = {tr[3], tr[4], tr[5]}, fc[3] = {tr[6], tr[7], tr[8]};
+                T t, b1, b2;
+                if (!mesh_ray_face(r, fa, fb, fc, t, b1, b2)) continue;
+                const unsigned id = a.ix.face[s];
+                if (t < best || (t == best && id < bf && t < (T)INFINITY)) { best = t; bf = id; bv = b1; bw = b2; }
+            }
+        } else {
+            const int c0 = 2 * node + 1;
+            T l0, l1;
+            const bool v0 = mesh_ray_node(r, box + 6 * (size_t)c0, best, l0), v1 = mesh_ray_node(r, box + 6 * (size_t)c0 + 6, best, l1);
+            if (v0 && v1) {
+                const bool left_first = l0 <= l1;
+                s_stack[sp++][threadIdx.x] = left_first ? c0 + 1 : c0;
+                node = left_first ? c0 : c0 + 1;
+                descend = true;
+            } else if (v0 || v1) {
+                node = v0 ? c0 : c0 + 1;
+                descend = true;
+            }
+        }
+        if (descend) continue;
+        live = false;
+        while (sp > 0) {
+            const int n = s_stack[--sp][threadIdx.x];
+            T t_in;
+            if (mesh_ray_node(r, box + 6 * (size_t)n, best, t_in)) { node = n; live = true; break; }
+        }
+    }
+    const bool hit = bf != 0xffffffffu;
+    a.out_t[row] = hit ? best : (T)INFINITY;
+    a.out_fi[row] = hit ? (long long)bf : -1ll;
+    a.out_bc[3 * (size_t)row] = hit ? ((T)1 - bv) - bw : (T)0; a.out_bc[3 * (size_t)row + 1] = hit ? bv : (T)0; a.out_bc[3 * (size_t)row + 2] = hit ? bw : (T)0;
+}
+
 }  // namespace pcu

@@ -201,3 +201,101 @@ static int mesh_index_closest_impl(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix,
     if (!rc) mesh_stats(st, tm, np, false);
     return attempt_exit(c, rc);
 }
+
+// ---------------------------------------------------------------------------------------------------- rays (mesh.h)
+template <typename T>
+static size_t mesh_rays_bytes(int64_t n, bool on_dev) {
+    size_t b = mesh_sort_bytes(n) + 4096;
+    if (!on_dev) b += 3 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n * sizeof(T), 256) + align_up((size_t)n * 8, 256);
+    return b;
+}
+static int mesh_rays_validate(int64_t o_rows, int64_t n, double ray_near, double ray_far) {
+    if (n < 0) return fail(PCU_HIP_ERR_INVALID, "negative number of rays");
+    if (n > 0x07fffff0ll) return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported");
+    if (o_rows != 1 && o_rows != n)
+        return fail(PCU_HIP_ERR_INVALID, "ray_o and ray_d must have the same number of rows (one ray origin per ray direction). "
+                                         "(Note: ray_o can have one row to use the same origin for all directions)");
+    if (ray_near != ray_near || ray_far != ray_far) return fail(PCU_HIP_ERR_INVALID, "ray_near and ray_far must not be NaN");
+    return 0;
+}
+
+// Enqueues the rays and waits for them. Events 1 / 2 of the context bracket the query phase.
+template <typename T>
+static int mesh_rays(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const MeshIdx<T>& M, const T* o, int64_t o_rows, const T* d, int64_t n, double ray_near,
+                     double ray_far, bool on_dev, int64_t* out_fi, T* out_bc, T* out_t, Timer& tm) {
+    tm.mark(1);
+    if (n == 0) { tm.mark(2); HIP_WAIT(s); return 0; }
+    const T *dor = nullptr, *dd = nullptr;
+    if (stage_in(ar, o, o_rows, on_dev, s, &dor) || stage_in(ar, d, n, on_dev, s, &dd)) return -1;
+    int* d_bad = nullptr;
+    unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
+    if (aalloc(ar, &d_bad, 1) || aalloc(ar, &ka, (size_t)n) || aalloc(ar, &kb, (size_t)n) || aalloc(ar, &ia, (size_t)n) || aalloc(ar, &ib, (size_t)n)) return -1;
+    T *d_t = out_t, *d_bc = out_bc; long long* d_fi = reinterpret_cast<long long*>(out_fi);
+    if (!on_dev && (aalloc(ar, &d_t, (size_t)n) || aalloc(ar, &d_fi, (size_t)n) || aalloc(ar, &d_bc, (size_t)n * 3))) return -1;
+    const int o_stride = o_rows == 1 && n != 1 ? 0 : 3;
+    const int nb = (int)((n + kBlock - 1) / kBlock);
+    HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_mesh_rkeys<T>, dim3(nb), dim3(kBlock), 0, s, dor, o_stride, dd, (int)n, (const MeshHead<T>*)M.head, ka, d_bad);
+    if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)n, kMeshRayKeyBits)) return -1;
+    MeshRays<T> a;
+    a.o = dor; a.o_stride = o_stride; a.d = dd; a.order = ia; a.n = (int)n; a.ix = M;
+    a.near = (T)ray_near; a.far = (T)ray_far;
+    a.out_fi = d_fi; a.out_bc = d_bc; a.out_t = d_t;
+    a.cancel_word = g_cancel_mirror.load(std::memory_order_relaxed); a.cancel_gen = t_call_gen;
+    hipLaunchKernelGGL(k_mesh_rays<T>, dim3((unsigned)((n + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    tm.mark(2);
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (!on_dev) {
+        HIP_TRY(hipMemcpyAsync(out_t, d_t, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)n * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+    }
+    HIP_WAIT(s);
+    if (bad & kMeshBadOrigin) return fail(PCU_HIP_ERR_INVALID, "ray_o must not contain NaN or infinite coordinates");
+    if (bad & kMeshBadDir) return fail(PCU_HIP_ERR_INVALID, "ray_d must not contain NaN or infinite coordinates");
+    return 0;
+}
+
+// ray_mesh_intersection (src/ray_mesh_intersection.cpp:107-177): index, rays and temporaries in the call's arena
+template <typename T>
+static int mesh_rays_oneshot_impl(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* o, int64_t o_rows, const T* d,
+                                  int64_t n, double ray_near, double ray_far, int64_t* out_fi, T* out_bc, T* out_t, unsigned flags, void* stream,
+                                  pcu_hip_stats* st) {
+    if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
+    if (st) memset(st, 0, sizeof *st);
+    if (int rc = mesh_rays_validate(o_rows, n, ray_near, ray_far)) return rc;
+    if (int rc = mesh_validate(nv, nf, n, f_kind)) return rc;
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
+    hipStream_t s = pick_stream(c, flags, stream);
+    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
+    if (ctx_begin(c, mesh_index_bytes<T>(nf) + mesh_build_bytes<T>(nv, nf, f_kind, on_dev) + mesh_rays_bytes<T>(n, on_dev))) return PCU_HIP_ERR_RUNTIME;
+    Arena ar{c};
+    Timer tm{c, s, st};
+    MeshIdx<T> M;
+    tm.mark(0);
+    int rc = mesh_build<T>(ar, ar, s, v, nv, f, nf, f_kind, on_dev, M);
+    if (!rc) rc = mesh_rays<T>(c, ar, s, M, o, o_rows, d, n, ray_near, ray_far, on_dev, out_fi, out_bc, out_t, tm);
+    if (!rc) mesh_stats(st, tm, n, true);
+    return attempt_exit(c, rc);
+}
+
+template <typename T>
+static int mesh_index_rays_impl(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* o, int64_t o_rows, const T* d, int64_t n, double ray_near,
+                                double ray_far, int64_t* out_fi, T* out_bc, T* out_t, unsigned flags, void* stream, pcu_hip_stats* st) {
+    if (!c || !ix) return fail(PCU_HIP_ERR_INVALID, "null context / mesh index");
+    if (st) memset(st, 0, sizeof *st);
+    if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the mesh index was built for the other scalar type");
+    if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the mesh index lives on another device than the context");
+    if (int rc = mesh_rays_validate(o_rows, n, ray_near, ray_far)) return rc;
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
+    hipStream_t s = pick_stream(c, flags, stream);
+    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
+    if (ctx_begin(c, mesh_rays_bytes<T>(n, on_dev))) return PCU_HIP_ERR_RUNTIME;
+    Arena ar{c};
+    Timer tm{c, s, st};
+    int rc = mesh_rays<T>(c, ar, s, mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)), o, o_rows, d, n, ray_near, ray_far, on_dev, out_fi, out_bc, out_t, tm);
+    if (!rc) mesh_stats(st, tm, n, false);
+    return attempt_exit(c, rc);
+}

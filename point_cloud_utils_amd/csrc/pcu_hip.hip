@@ -2927,6 +2927,19 @@ int pcu_hip_mesh_index_closest_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_index* i
     CallGuard dg(c); return abi_rc(mesh_index_closest_impl<T>(c, ix, p, np, out_d, out_fi, out_bc, flags, stream, st)); }
 PCU_MESH(f32, float) PCU_MESH(f64, double)
 #undef PCU_MESH
+// ray_mesh_intersection (mesh.h, mesh_host.h)
+#define PCU_MESH_RAYS(SUF, T)                                                                                                                         \
+int pcu_hip_ray_mesh_intersection_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* ray_o, int64_t o_rows, \
+                                        const T* ray_d, int64_t n, double ray_near, double ray_far, int64_t* out_fi, T* out_bc, T* out_t,            \
+                                        unsigned flags, void* stream, pcu_hip_stats* st) {                                                           \
+    CallGuard dg(c);                                                                                                                                 \
+    return abi_rc(mesh_rays_oneshot_impl<T>(c, v, nv, f, nf, f_kind, ray_o, o_rows, ray_d, n, ray_near, ray_far, out_fi, out_bc, out_t, flags, stream, st)); } \
+int pcu_hip_mesh_index_rays_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* ray_o, int64_t o_rows, const T* ray_d, int64_t n,            \
+                                  double ray_near, double ray_far, int64_t* out_fi, T* out_bc, T* out_t, unsigned flags, void* stream,               \
+                                  pcu_hip_stats* st) {                                                                                               \
+    CallGuard dg(c); return abi_rc(mesh_index_rays_impl<T>(c, ix, ray_o, o_rows, ray_d, n, ray_near, ray_far, out_fi, out_bc, out_t, flags, stream, st)); }
+PCU_MESH_RAYS(f32, float) PCU_MESH_RAYS(f64, double)
+#undef PCU_MESH_RAYS
 int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }
 void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) {
     if (!ix) return;
