@@ -32,26 +32,25 @@ def _check_face_dtype(f):
         raise ValueError(f"Invalid scalar type ({df}) for argument 'f'. Expected one of {kinds}.")
 
 
+def _check_rows(*counts):
+    if max(counts) > _MAX_ROWS:
+        raise ValueError("meshes and point clouds with more than 2^27-16 rows are not supported")
+
+
 def _check_mesh(v, f, want=None):
     """Scalar types, then validate_mesh (src/common/common.h:133-147), then this package's row limit. Returns (dtype name, #v, #f)."""
-    from . import _dtype_name, _is_torch, _shape2
-    dv = _dtype_name(v)
-    if want is None and dv not in ("float32", "float64"):
-        raise ValueError(f"Invalid scalar type ({dv}) for argument 'v'. Expected one of ['float32', 'float64'].")
+    from . import _dtype_name, _shape2
+    dv = _check_scalar_v(v) if want is None else _dtype_name(v)
     if want is not None and dv != want:
         raise ValueError(f"Invalid scalar type ({dv}) for argument 'v'. Expected it to match argument 'p' which is of type {want}.")
-    df = _face_dtype_name(f)
-    kinds = ["int32", "int64"] if _is_torch(f) else list(_FACE_KINDS)
-    if df not in kinds:
-        raise ValueError(f"Invalid scalar type ({df}) for argument 'f'. Expected one of {kinds}.")
+    _check_face_dtype(f)
     sv, sf = _shape2(v), _shape2(f)
     got = f"Got v.shape =({sv[0]}, {sv[1]}), f.shape = ({sf[0]}, {sf[1]})."
     if sv[0] == 0 or sf[0] == 0:
         raise ValueError("Invalid input mesh with zero elements: v and f must have shape (n, 3) and (m, 3) (n, m > 0). " + got)
     if sv[1] != 3 or sf[1] != 3:
         raise ValueError("Only 3D inputs are supported: v and f must have shape (n, 3) and (m, 3) (n, m > 0). " + got)
-    if sv[0] > _MAX_ROWS or sf[0] > _MAX_ROWS:
-        raise ValueError("meshes and point clouds with more than 2^27-16 rows are not supported")
+    _check_rows(sv[0], sf[0])
     return dv, sv[0], sf[0]
 
 
@@ -66,8 +65,7 @@ def _check_points(p, want=None):
     sp = _shape2(p)
     if sp[1] != 3:
         raise ValueError(f"Only 3D inputs are supported: v must have shape (n, 3) (n > 0). Got points.shape =({sp[0]}, {sp[1]}).")
-    if sp[0] > _MAX_ROWS:
-        raise ValueError("meshes and point clouds with more than 2^27-16 rows are not supported")
+    _check_rows(sp[0])
     return dp, sp[0]
 
 
@@ -97,17 +95,33 @@ def _faces_for(d, f):
     return np.ascontiguousarray(f)
 
 
+_POINT_ORDER, _RAY_ORDER = (0, 1, 2), (1, 2, 0)     # (d, f_idx, bc) and (f_id, bc, t) out of _results' (value, face, barycentrics)
+
+
 def _results(d, n):
+    """What both operators write per row: one value (distance / t), one int64 face, three barycentric coordinates."""
     return d.empty((n,), "T"), d.empty((n,), "i64"), d.empty((n, 3), "T")
 
 
-def _finish(dist, fi, bc, f, n):
-    """fi in f's dtype; singleton dimensions squeezed as the package's other calls do (numpyeigen's squeeze)."""
+def _finish(val, fi, bc, like, n, order):
+    """The results in the operator's return order. The face in the dtype of `like`, f's (-1 wraps for an unsigned one, as the reference's
+    assignment does); singleton dimensions squeezed as the package's other calls do (numpyeigen's squeeze)."""
     from . import _is_torch
-    fi = fi.to(f.dtype) if _is_torch(fi) else fi.astype(f.dtype, copy=False)
+    fi = fi.to(like.dtype) if _is_torch(fi) else fi.astype(like.dtype, copy=False)
     if n == 1:
-        return dist.reshape(()), fi.reshape(()), bc.reshape(3)
-    return dist, fi, bc
+        val, fi, bc = val.reshape(()), fi.reshape(()), bc.reshape(3)
+    res = (val, fi, bc)
+    return tuple(res[i] for i in order)
+
+
+def _call(name, d, *args):
+    """The library's `name` for the arrays `d` resolved: raises what it refuses, records its statistics."""
+    from . import _lib, _fn, _record, Stats
+    st = Stats()
+    rc = _fn(name, d.suffix)(d.ctx, *args, d.flags, d.stream, ctypes.addressof(st))
+    if rc:
+        _lib.check(rc)
+    _record(st)
 
 
 def closest_points_on_mesh(p, v, f):
@@ -131,7 +145,7 @@ def closest_points_on_mesh(p, v, f):
       returned, with that face's barycentric coordinates (u = (1 - v) - w may undershoot 0 by one rounding). Non-finite coordinates, face indices
       outside [0, #v) and arrays of more than 2**27 - 16 rows raise ValueError.
     """
-    from . import _lib, _Dev, _fn, _is_torch, _record, Stats
+    from . import _Dev, _is_torch
     dp, n = _check_points(p)
     _, nv, nf = _check_mesh(v, f, want=dp)
     if not (_is_torch(p) or _is_torch(v) or _is_torch(f)):
@@ -140,13 +154,8 @@ def closest_points_on_mesh(p, v, f):
     d = _Dev(p, v)
     ff = _faces_for(d, f)
     dist, fi, bc = _results(d, n)
-    st = Stats()
-    rc = _fn("closest_points_on_mesh", d.suffix)(d.ctx, d.pb, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)], d.pa, n,
-                                                 _Dev.ptr(dist), _Dev.ptr(fi), _Dev.ptr(bc), d.flags, d.stream, ctypes.addressof(st))
-    if rc:
-        _lib.check(rc)
-    _record(st)
-    return _finish(dist, fi, bc, ff, n)
+    _call("closest_points_on_mesh", d, d.pb, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)], d.pa, n, _Dev.ptr(dist), _Dev.ptr(fi), _Dev.ptr(bc))
+    return _finish(dist, fi, bc, ff, n, _POINT_ORDER)
 
 
 _RAY_ROWS = ("ray_o and ray_d must have the same number of rows (one ray origin per ray direction). "
@@ -180,8 +189,7 @@ def _check_rays(ray_o, ray_d, want, match):
 
 
 def _check_ray_limits(n, ray_near, ray_far):
-    if n > _MAX_ROWS:
-        raise ValueError("meshes and point clouds with more than 2^27-16 rows are not supported")
+    _check_rows(n)
     ray_near, ray_far = float(ray_near), float(ray_far)
     if ray_near != ray_near or ray_far != ray_far:
         raise ValueError("ray_near and ray_far must not be NaN")
@@ -201,19 +209,6 @@ def _origins_for(d, ray_o, single):
     if single:
         oo = oo.reshape(1, 3)
     return oo, int(oo.shape[0])
-
-
-def _ray_results(d, n):
-    return d.empty((n,), "i64"), d.empty((n, 3), "T"), d.empty((n,), "T")
-
-
-def _finish_rays(fi, bc, t, like, n):
-    """f_id in the dtype of `like` (-1 wraps for an unsigned one, as the reference's assignment does); one ray: squeezed as _finish does."""
-    from . import _is_torch
-    fi = fi.to(like.dtype) if _is_torch(fi) else fi.astype(like.dtype, copy=False)
-    if n == 1:
-        return fi.reshape(()), bc.reshape(3), t.reshape(())
-    return fi, bc, t
 
 
 def ray_mesh_intersection(v, f, ray_o, ray_d, ray_near=0.0, ray_far=np.inf):
@@ -239,7 +234,7 @@ def ray_mesh_intersection(v, f, ray_o, ray_d, ray_near=0.0, ray_far=np.inf):
       lowest face index. A zero direction, a face of no area and a face seen exactly edge-on are misses; ray_near > ray_far gives all misses.
       Non-finite coordinates, NaN ray_near / ray_far, face indices outside [0, #v) and arrays of more than 2**27 - 16 rows raise ValueError.
     """
-    from . import _lib, _Dev, _fn, _is_torch, _record, Stats
+    from . import _Dev, _is_torch
     dv = _check_scalar_v(v)
     _check_face_dtype(f)
     n, single = _check_rays(ray_o, ray_d, dv, "argument 'v'")
@@ -251,14 +246,10 @@ def ray_mesh_intersection(v, f, ray_o, ray_d, ray_near=0.0, ray_far=np.inf):
     d = _Dev(ray_d, v)
     ff = _faces_for(d, f)
     oo, o_rows = _origins_for(d, ray_o, single)
-    fi, bc, t = _ray_results(d, n)
-    st = Stats()
-    rc = _fn("ray_mesh_intersection", d.suffix)(d.ctx, d.pb, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)], _Dev.ptr(oo), o_rows, d.pa, n,
-                                                ray_near, ray_far, _Dev.ptr(fi), _Dev.ptr(bc), _Dev.ptr(t), d.flags, d.stream, ctypes.addressof(st))
-    if rc:
-        _lib.check(rc)
-    _record(st)
-    return _finish_rays(fi, bc, t, ff, n)
+    t, fi, bc = _results(d, n)
+    _call("ray_mesh_intersection", d, d.pb, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)], _Dev.ptr(oo), o_rows, d.pa, n, ray_near, ray_far,
+          _Dev.ptr(fi), _Dev.ptr(bc), _Dev.ptr(t))
+    return _finish(t, fi, bc, ff, n, _RAY_ORDER)
 
 
 def interpolate_barycentric_coords(f, fi, bc, attribute):
@@ -309,9 +300,8 @@ class MeshIndex:
 
     def closest_points(self, p):
         """See point_cloud_utils_amd.closest_points_on_mesh; the mesh is the indexed one."""
-        from . import _lib, _Dev, _fn, _record, _is_torch, Stats
-        if self._h is None:
-            raise ValueError("the mesh index has been closed")
+        from . import _Dev, _is_torch
+        self._check_open()
         _, n = _check_points(p, want=self._dtype_name)
         if not _is_torch(p):
             _host_point_checks(np.asarray(p))
@@ -319,13 +309,12 @@ class MeshIndex:
         if d.device != self._device:
             raise ValueError("query points and mesh index live on different devices")
         dist, fi, bc = _results(d, n)
-        st = Stats()
-        rc = _fn("mesh_index_closest", d.suffix)(d.ctx, self._h, d.pa, n, _Dev.ptr(dist), _Dev.ptr(fi), _Dev.ptr(bc), d.flags, d.stream,
-                                                 ctypes.addressof(st))
-        if rc:
-            _lib.check(rc)
-        _record(st)
-        return _finish(dist, fi, bc, self._like_for(d), n)
+        _call("mesh_index_closest", d, self._h, d.pa, n, _Dev.ptr(dist), _Dev.ptr(fi), _Dev.ptr(bc))
+        return _finish(dist, fi, bc, self._like_for(d), n, _POINT_ORDER)
+
+    def _check_open(self):
+        if self._h is None:
+            raise ValueError("the mesh index has been closed")
 
     def _like_for(self, d):
         """An empty array of f's dtype and of the kind (numpy / torch) of the call's results."""
@@ -340,9 +329,8 @@ class MeshIndex:
 
     def intersect_rays(self, ray_o, ray_d, ray_near=0.0, ray_far=np.inf):
         """See point_cloud_utils_amd.ray_mesh_intersection; the mesh is the indexed one and the rays must have its dtype."""
-        from . import _lib, _Dev, _fn, _record, _is_torch, Stats
-        if self._h is None:
-            raise ValueError("the mesh index has been closed")
+        from . import _Dev, _is_torch
+        self._check_open()
         n, single = _check_rays(ray_o, ray_d, self._dtype_name, "the indexed mesh")
         ray_near, ray_far = _check_ray_limits(n, ray_near, ray_far)
         if not (_is_torch(ray_o) or _is_torch(ray_d)):
@@ -351,14 +339,9 @@ class MeshIndex:
         if d.device != self._device:
             raise ValueError("rays and mesh index live on different devices")
         oo, o_rows = _origins_for(d, ray_o, single)
-        fi, bc, t = _ray_results(d, n)
-        st = Stats()
-        rc = _fn("mesh_index_rays", d.suffix)(d.ctx, self._h, _Dev.ptr(oo), o_rows, d.pa, n, ray_near, ray_far, _Dev.ptr(fi), _Dev.ptr(bc), _Dev.ptr(t),
-                                              d.flags, d.stream, ctypes.addressof(st))
-        if rc:
-            _lib.check(rc)
-        _record(st)
-        return _finish_rays(fi, bc, t, self._like_for(d), n)
+        t, fi, bc = _results(d, n)
+        _call("mesh_index_rays", d, self._h, _Dev.ptr(oo), o_rows, d.pa, n, ray_near, ray_far, _Dev.ptr(fi), _Dev.ptr(bc), _Dev.ptr(t))
+        return _finish(t, fi, bc, self._like_for(d), n, _RAY_ORDER)
 
     def close(self):
         if getattr(self, "_h", None) is not None:

@@ -195,6 +195,9 @@ __global__ __launch_bounds__(kBlock) void k_mesh_refit(T* __restrict__ box, int 
 }
 
 // ---------------------------------------------------------------------------------------------------- queries
+template <typename T> __device__ __forceinline__ bool mesh_finite3(const T* p) {
+    return (p[0] - p[0] == (T)0) && (p[1] - p[1] == (T)0) && (p[2] - p[2] == (T)0);
+}
 // 30-bit Morton key of every query in the mesh's frame (clamped to it), so that the lanes of a wave walk the same nodes; non-finite rows are flagged
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_mesh_qcodes(const T* __restrict__ p, int np, const MeshHead<T>* __restrict__ h, unsigned long long* __restrict__ keys,
@@ -202,11 +205,11 @@ __global__ __launch_bounds__(kBlock) void k_mesh_qcodes(const T* __restrict__ p,
     const int i = blockIdx.x * kBlock + threadIdx.x;
     bool nf = false;
     if (i < np) {
+        nf = !mesh_finite3(p + 3 * (size_t)i);
         unsigned cell[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const T x = p[3 * (size_t)i + k];
-            nf |= !(x - x == (T)0);
             cell[k] = mesh_cell(((double)x - (double)h->lo[k]) * (double)h->inv[k] * (1.0 / 2048.0), 1023u);
         }
         keys[i] = morton_split21(cell[0]) | morton_split21(cell[1]) << 1 | morton_split21(cell[2]) << 2;
@@ -262,44 +265,41 @@ struct MeshQuery {
     const unsigned* cancel_word; unsigned cancel_gen;          // pcu_types.h: cancel_seen
 };
 
-// One lane per query, queries in Morton order. Near child first, the far child pushed if its bound allows: at most one entry per level, so the
-// stack (LDS, one column per lane: a runtime-indexed private array would live in scratch memory) holds kMeshStack node ids. A popped node's
-// bound is computed again, against the best of that moment.
-template <typename T>
-__global__ __launch_bounds__(kMeshBlock) void k_mesh_closest(const MeshQuery<T> a) {
+// The walk both operators share. One lane per row, rows in key order so that the lanes of a wave walk the same nodes. A Visitor is the lane's
+// row and its best so far:
+//   node(box, key) -> whether the node can still hold the winner (the operator's "Pruning" rule, against the best of that moment), and the key
+//                     that orders two children (the lower one is taken first);
+//   face(a, b, c, id) evaluates one face and keeps it if it beats the best; `id` points at its face index.
+// The child with the lower key is taken first and the other pushed if it passes too: at most one entry per level, so the stack (LDS, one column
+// per lane: a runtime-indexed private array would live in scratch memory) holds kMeshStack node ids. A popped node is tested again, against the
+// best of that moment. `live` says whether the lane walks at all (the root is not tested here). Returns true if the call was cancelled: the
+// caller then returns without writing its row. The leaf loop stays rolled: unrolled, it is a four times larger kernel for the point visitor.
+template <typename T, typename Visitor>
+__device__ __forceinline__ bool mesh_walk(const MeshIdx<T>& ix, Visitor& vis, bool live, const unsigned* cancel_word, unsigned cancel_gen) {
     __shared__ int s_stack[kMeshStack][kMeshBlock];
-    const int i = blockIdx.x * kMeshBlock + threadIdx.x;
-    if (i >= a.np) return;
-    const unsigned row = a.order[i];
-    const T q[3] = {a.p[3 * (size_t)row], a.p[3 * (size_t)row + 1], a.p[3 * (size_t)row + 2]};
-    const T* __restrict__ box = a.ix.box;
-    const T* __restrict__ tri = a.ix.tri;
-    const int first_leaf = a.ix.P - 1, nf = a.ix.nf;
-    T best = (T)INFINITY, bv = (T)0, bw = (T)0;
-    unsigned bf = 0xffffffffu;
+    const T* __restrict__ box = ix.box;
+    const T* __restrict__ tri = ix.tri;
+    const int first_leaf = ix.P - 1, nf = ix.nf;
     int sp = 0, node = 0;
     unsigned steps = 0;
     long long t_poll = wall_clock64();
-    bool live = (q[0] - q[0] == (T)0) && (q[1] - q[1] == (T)0) && (q[2] - q[2] == (T)0);        // (a non-finite row is refused by the host after the launch)
     while (live) {
-        if ((++steps & 63u) == 0u) { const long long t_now = wall_clock64(); if (t_now - t_poll > 20000ll) { t_poll = t_now; if (cancel_seen(a.cancel_word, a.cancel_gen)) return; } }
+        if ((++steps & 63u) == 0u) { const long long t_now = wall_clock64(); if (t_now - t_poll > 20000ll) { t_poll = t_now; if (cancel_seen(cancel_word, cancel_gen)) return true; } }
         bool descend = false;
         if (node >= first_leaf) {
             const long long s0 = (long long)kMeshLeaf * (node - first_leaf);
+#pragma unroll 1
             for (int t = 0; t < kMeshLeaf; ++t) {
                 const long long s = s0 + t;
                 if (s >= nf) break;
                 const T* tr = tri + 9 * (size_t)s;
                 const T fa[3] = {tr[0], tr[1], tr[2]}, fb[3] = {tr[3], tr[4], tr[5]}, fc[3] = {tr[6], tr[7], tr[8]};
-                T d2, v, w;
-                mesh_face_d2(q, fa, fb, fc, d2, v, w);
-                const unsigned id = a.ix.face[s];
-                if (d2 < best || (d2 == best && id < bf)) { best = d2; bf = id; bv = v; bw = w; }
+                vis.face(fa, fb, fc, ix.face + s);
             }
         } else {
             const int c0 = 2 * node + 1;
-            const T l0 = mesh_bound(box + 6 * (size_t)c0, q), l1 = mesh_bound(box + 6 * (size_t)c0 + 6, q);
-            const bool v0 = l0 <= best, v1 = l1 <= best;
+            T l0, l1;
+            const bool v0 = vis.node(box + 6 * (size_t)c0, l0), v1 = vis.node(box + 6 * (size_t)c0 + 6, l1);
             if (v0 && v1) {
                 const bool left_first = l0 <= l1;
                 s_stack[sp++][threadIdx.x] = left_first ? c0 + 1 : c0;
@@ -314,13 +314,42 @@ __global__ __launch_bounds__(kMeshBlock) void k_mesh_closest(const MeshQuery<T> 
         live = false;
         while (sp > 0) {
             const int n = s_stack[--sp][threadIdx.x];
-            if (mesh_bound(box + 6 * (size_t)n, q) <= best) { node = n; live = true; break; }
+            T key;
+            if (vis.node(box + 6 * (size_t)n, key)) { node = n; live = true; break; }
         }
     }
-    const T u = ((T)1 - bv) - bw;
-    a.out_d[row] = sqrt(best);
-    a.out_fi[row] = bf == 0xffffffffu ? -1ll : (long long)bf;
-    a.out_bc[3 * (size_t)row] = u; a.out_bc[3 * (size_t)row + 1] = bv; a.out_bc[3 * (size_t)row + 2] = bw;
+    return false;
+}
+
+// The best so far of both visitors: the winning value (d2 or t), its face and that face's last two barycentric coordinates
+template <typename T>
+struct MeshBest { T best = (T)INFINITY, bv = (T)0, bw = (T)0; unsigned bf = 0xffffffffu; };
+
+template <typename T>
+struct MeshPointVisitor : MeshBest<T> {         // lexicographic (d2, face); a node whose bound EQUALS the best is visited
+    T q[3];
+    __device__ __forceinline__ bool node(const T* __restrict__ bx, T& key) const { key = mesh_bound(bx, q); return key <= this->best; }
+    __device__ __forceinline__ void face(const T a[3], const T b[3], const T c[3], const unsigned* __restrict__ pid) {
+        T d2, v, w;
+        mesh_face_d2(q, a, b, c, d2, v, w);
+        const unsigned id = *pid;
+        if (d2 < this->best || (d2 == this->best && id < this->bf)) { this->best = d2; this->bf = id; this->bv = v; this->bw = w; }
+    }
+};
+
+// One query per lane (mesh_walk). The root is not box-tested: every finite query has a closest face.
+template <typename T>
+__global__ __launch_bounds__(kMeshBlock) void k_mesh_closest(const MeshQuery<T> a) {
+    const int i = blockIdx.x * kMeshBlock + threadIdx.x;
+    if (i >= a.np) return;
+    const unsigned row = a.order[i];
+    MeshPointVisitor<T> vis;
+    vis.q[0] = a.p[3 * (size_t)row]; vis.q[1] = a.p[3 * (size_t)row + 1]; vis.q[2] = a.p[3 * (size_t)row + 2];
+    if (mesh_walk(a.ix, vis, mesh_finite3(vis.q), a.cancel_word, a.cancel_gen)) return;     // (a non-finite row is refused by the host after the launch)
+    const T u = ((T)1 - vis.bv) - vis.bw;
+    a.out_d[row] = sqrt(vis.best);
+    a.out_fi[row] = vis.bf == 0xffffffffu ? -1ll : (long long)vis.bf;
+    a.out_bc[3 * (size_t)row] = u; a.out_bc[3 * (size_t)row + 1] = vis.bv; a.out_bc[3 * (size_t)row + 2] = vis.bw;
 }
 
 // ---------------------------------------------------------------------------------------------------- rays
@@ -347,9 +376,6 @@ __global__ __launch_bounds__(kMeshBlock) void k_mesh_closest(const MeshQuery<T> 
 // !(t_out >= near) || !(t_in <= t_out), or if it is a padding node (the empty box). A node whose t_in EQUALS the best t is visited.
 constexpr int kMeshBadOrigin = 1, kMeshBadDir = 2;
 
-template <typename T> __device__ __forceinline__ bool mesh_finite3(const T* p) {
-    return (p[0] - p[0] == (T)0) && (p[1] - p[1] == (T)0) && (p[2] - p[2] == (T)0);
-}
 // Sort key of every ray, so that the lanes of a wave walk the same nodes: the 7-bit-per-axis Morton cell of the point where the ray enters the
 // mesh's bounding box (the origin if it is inside; a ray that misses the box gets the cell of a clamped point), then 11 bits of direction
 // (dominant axis and sign, the other two components over the dominant one in 16 steps each). Results do not depend on it. Non-finite rows
@@ -393,6 +419,26 @@ struct MeshRay {                                // one ray, its axes already per
     int kx, ky, kz;
 };
 template <typename T> __device__ __forceinline__ T mesh_pick(const T* p, int k) { return k == 0 ? p[0] : (k == 1 ? p[1] : p[2]); }
+// "per ray" of the contract: the ray of origin o and direction d, on a mesh whose leaf boxes are padded by pad_s
+template <typename T>
+__device__ __forceinline__ void mesh_ray_setup(MeshRay<T>& r, const T* o, const T d[3], T pad_s, T near, T far) {
+    r.o[0] = o[0]; r.o[1] = o[1]; r.o[2] = o[2];
+    const T a0 = fabs(d[0]), a1 = fabs(d[1]), a2 = fabs(d[2]);
+    r.kz = (a0 >= a1 && a0 >= a2) ? 0 : (a1 >= a2 ? 1 : 2);
+    r.kx = r.kz == 2 ? 0 : r.kz + 1;
+    r.ky = r.kx == 2 ? 0 : r.kx + 1;
+    const T dz = mesh_pick(d, r.kz);
+    if (dz < (T)0) { const int k = r.kx; r.kx = r.ky; r.ky = k; }
+    r.Sx = mesh_pick(d, r.kx) / dz; r.Sy = mesh_pick(d, r.ky) / dz; r.Sz = (T)1 / dz;
+    r.ox = mesh_pick(r.o, r.kx); r.oy = mesh_pick(r.o, r.ky); r.oz = mesh_pick(r.o, r.kz);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.inv[k] = (T)1 / d[k];
+    T m = fabs(r.o[0]) > fabs(r.o[1]) ? fabs(r.o[0]) : fabs(r.o[1]);
+    m = m > fabs(r.o[2]) ? m : fabs(r.o[2]);
+    const T pad_o = (T)16 * Limits<T>::eps * m;
+    r.pad = pad_s > pad_o ? pad_s : pad_o;
+    r.near = near; r.far = far;
+}
 
 // BOX of the contract for the box (lo - pad, hi + pad)
 template <typename T>
@@ -450,88 +496,36 @@ struct MeshRays {
     const unsigned* cancel_word; unsigned cancel_gen;          // pcu_types.h: cancel_seen
 };
 
-// One lane per ray, rays in key order. The child the ray enters first is taken first, the other pushed if it passes the node test: at most one
-// entry per level, so the stack (LDS, one column per lane, as in k_mesh_closest) holds kMeshStack node ids. A popped node is tested again,
-// against the best t of that moment.
+template <typename T>
+struct MeshRayVisitor : MeshBest<T> {           // the smallest accepted t, the lowest face among equal t; a node whose t_in EQUALS the best is visited
+    MeshRay<T> r;
+    __device__ __forceinline__ bool node(const T* __restrict__ bx, T& key) const { return mesh_ray_node(r, bx, this->best, key); }
+    __device__ __forceinline__ void face(const T a[3], const T b[3], const T c[3], const unsigned* __restrict__ pid) {
+        T t, b1, b2;
+        if (!mesh_ray_face(r, a, b, c, t, b1, b2)) return;
+        const unsigned id = *pid;
+        if (t < this->best || (t == this->best && id < this->bf && t < (T)INFINITY)) { this->best = t; this->bf = id; this->bv = b1; this->bw = b2; }
+    }
+};
+
+// One ray per lane (mesh_walk). The root is box-tested before the walk: a ray that misses the mesh's box visits nothing.
 template <typename T>
 __global__ __launch_bounds__(kMeshBlock) void k_mesh_rays(const MeshRays<T> a) {
-    __shared__ int s_stack[kMeshStack][kMeshBlock];
     const int i = blockIdx.x * kMeshBlock + threadIdx.x;
     if (i >= a.n) return;
     const unsigned row = a.order[i];
     const T* po = a.o + (size_t)a.o_stride * row;
     const T* pd = a.d + 3 * (size_t)row;
     const T d[3] = {pd[0], pd[1], pd[2]};
-    MeshRay<T> r;
-    r.o[0] = po[0]; r.o[1] = po[1]; r.o[2] = po[2];
-    bool live = mesh_finite3(r.o) && mesh_finite3(d);          // (a non-finite row is refused by the host after the launch)
-    {
-        const T a0 = fabs(d[0]), a1 = fabs(d[1]), a2 = fabs(d[2]);
-        r.kz = (a0 >= a1 && a0 >= a2) ? 0 : (a1 >= a2 ? 1 : 2);
-        r.kx = r.kz == 2 ? 0 : r.kz + 1;
-        r.ky = r.kx == 2 ? 0 : r.kx + 1;
-        const T dz = mesh_pick(d, r.kz);
-        if (dz < (T)0) { const int k = r.kx; r.kx = r.ky; r.ky = k; }
-        r.Sx = mesh_pick(d, r.kx) / dz; r.Sy = mesh_pick(d, r.ky) / dz; r.Sz = (T)1 / dz;
-        r.ox = mesh_pick(r.o, r.kx); r.oy = mesh_pick(r.o, r.ky); r.oz = mesh_pick(r.o, r.kz);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) r.inv[k] = (T)1 / d[k];
-        T m = fabs(r.o[0]) > fabs(r.o[1]) ? fabs(r.o[0]) : fabs(r.o[1]);
-        m = m > fabs(r.o[2]) ? m : fabs(r.o[2]);
-        const T pad_o = (T)16 * Limits<T>::eps * m, pad_s = a.ix.head->pad;
-        r.pad = pad_s > pad_o ? pad_s : pad_o;
-        r.near = a.near; r.far = a.far;
-    }
-    const T* __restrict__ box = a.ix.box;
-    const T* __restrict__ tri = a.ix.tri;
-    const int first_leaf = a.ix.P - 1, nf = a.ix.nf;
-    T best = (T)INFINITY, bv = (T)0, bw = (T)0;
-    unsigned bf = 0xffffffffu;
-    int sp = 0, node = 0;
-    unsigned steps = 0;
-    long long t_poll = wall_clock64();
-    { T t_in; live = live && mesh_ray_node(r, box, best, t_in); }
-    while (live) {
-        if ((++steps & 63u) == 0u) { const long long t_now = wall_clock64(); if (t_now - t_poll > 20000ll) { t_poll = t_now; if (cancel_seen(a.cancel_word, a.cancel_gen)) return; } }
-        bool descend = false;
-        if (node >= first_leaf) {
-            const long long s0 = (long long)kMeshLeaf * (node - first_leaf);
-            for (int j = 0; j < kMeshLeaf; ++j) {
-                const long long s = s0 + j;
-                if (s >= nf) break;
-                const T* tr = tri + 9 * (size_t)s;
-                const T fa[3] = {tr[0], tr[1], tr[2]}, fb[3] = {tr[3], tr[4], tr[5]}, fc[3] = {tr[6], tr[7], tr[8]};
-                T t, b1, b2;
-                if (!mesh_ray_face(r, fa, fb, fc, t, b1, b2)) continue;
-                const unsigned id = a.ix.face[s];
-                if (t < best || (t == best && id < bf && t < (T)INFINITY)) { best = t; bf = id; bv = b1; bw = b2; }
-            }
-        } else {
-            const int c0 = 2 * node + 1;
-            T l0, l1;
-            const bool v0 = mesh_ray_node(r, box + 6 * (size_t)c0, best, l0), v1 = mesh_ray_node(r, box + 6 * (size_t)c0 + 6, best, l1);
-            if (v0 && v1) {
-                const bool left_first = l0 <= l1;
-                s_stack[sp++][threadIdx.x] = left_first ? c0 + 1 : c0;
-                node = left_first ? c0 : c0 + 1;
-                descend = true;
-            } else if (v0 || v1) {
-                node = v0 ? c0 : c0 + 1;
-                descend = true;
-            }
-        }
-        if (descend) continue;
-        live = false;
-        while (sp > 0) {
-            const int n = s_stack[--sp][threadIdx.x];
-            T t_in;
-            if (mesh_ray_node(r, box + 6 * (size_t)n, best, t_in)) { node = n; live = true; break; }
-        }
-    }
-    const bool hit = bf != 0xffffffffu;
-    a.out_t[row] = hit ? best : (T)INFINITY;
-    a.out_fi[row] = hit ? (long long)bf : -1ll;
-    a.out_bc[3 * (size_t)row] = hit ? ((T)1 - bv) - bw : (T)0; a.out_bc[3 * (size_t)row + 1] = hit ? bv : (T)0; a.out_bc[3 * (size_t)row + 2] = hit ? bw : (T)0;
+    MeshRayVisitor<T> vis;
+    mesh_ray_setup(vis.r, po, d, a.ix.head->pad, a.near, a.far);
+    T t_in;
+    const bool live = mesh_finite3(vis.r.o) && mesh_finite3(d) && vis.node(a.ix.box, t_in);     // (a non-finite row is refused by the host after the launch)
+    if (mesh_walk(a.ix, vis, live, a.cancel_word, a.cancel_gen)) return;
+    const bool hit = vis.bf != 0xffffffffu;
+    a.out_t[row] = hit ? vis.best : (T)INFINITY;
+    a.out_fi[row] = hit ? (long long)vis.bf : -1ll;
+    a.out_bc[3 * (size_t)row] = hit ? ((T)1 - vis.bv) - vis.bw : (T)0; a.out_bc[3 * (size_t)row + 1] = hit ? vis.bv : (T)0; a.out_bc[3 * (size_t)row + 2] = hit ? vis.bw : (T)0;
 }
 
 }  // namespace pcu

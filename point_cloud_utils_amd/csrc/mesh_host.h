@@ -1,4 +1,4 @@
-// csrc/mesh_host.h -- host orchestration of closest_points_on_mesh (kernels, contract and index layout: mesh.h). Included by pcu_hip.hip after
+// csrc/mesh_host.h -- host orchestration of closest_points_on_mesh and ray_mesh_intersection (kernels, contracts and index layout: mesh.h). Included by pcu_hip.hip after
 // the arena, staging and radix-sort helpers.
 #pragma once
 
@@ -41,12 +41,15 @@ static size_t mesh_build_bytes(int64_t nv, int64_t nf, int f_kind, bool on_dev) 
     if (!on_dev) b += align_up((size_t)nv * 3 * sizeof(T), 256) + align_up((size_t)nf * 3 * mesh_face_bytes(f_kind), 256);
     return b;
 }
+// the query phase: the sort, the result staging of host output and rows3 staged (n,3) arrays (inputs and barycentrics)
 template <typename T>
-static size_t mesh_query_bytes(int64_t np, bool on_dev) {
-    size_t b = mesh_sort_bytes(np) + 4096;
-    if (!on_dev) b += 2 * align_up((size_t)np * 3 * sizeof(T), 256) + align_up((size_t)np * sizeof(T), 256) + align_up((size_t)np * 8, 256);
+static size_t mesh_run_bytes(int64_t n, int rows3, bool on_dev) {
+    size_t b = mesh_sort_bytes(n) + 4096;
+    if (!on_dev) b += rows3 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n * sizeof(T), 256) + align_up((size_t)n * 8, 256);
     return b;
 }
+constexpr int64_t kMeshMaxRows = 0x07fffff0ll;
+static int mesh_row_limit() { return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported"); }
 // validate_mesh (src/common/common.h:133-147) and this package's row limit
 static int mesh_validate(int64_t nv, int64_t nf, int64_t np, int f_kind) {
     if (nv <= 0 || nf <= 0)
@@ -54,7 +57,7 @@ static int mesh_validate(int64_t nv, int64_t nf, int64_t np, int f_kind) {
                     (long long)nv, (long long)nf);
     if (np < 0) return fail(PCU_HIP_ERR_INVALID, "negative number of query points");
     if (f_kind < 0 || f_kind > 3) return fail(PCU_HIP_ERR_INVALID, "f_kind must be one of PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64");
-    if (nv > 0x07fffff0ll || nf > 0x07fffff0ll || np > 0x07fffff0ll) return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported");
+    if (nv > kMeshMaxRows || nf > kMeshMaxRows || np > kMeshMaxRows) return mesh_row_limit();
     return 0;
 }
 
@@ -90,40 +93,83 @@ static int mesh_build(Arena& ari, Arena& ar, hipStream_t s, const T* v, int64_t 
     return 0;
 }
 
-// Enqueues the queries and waits for them. Events 1 / 2 of the context bracket the query phase.
+// ---------------------------------------------------------------------------------------------------- the two operators
+// Both answer, per row, with one T (distance / t), one int64 face and three T barycentrics. What differs is an Op: its inputs, how many (n,3)
+// arrays a call with host arrays stages (kRows3, inputs and barycentrics), its checks ahead of the mesh's, the kernel and the bits of the sort
+// key, the walk kernel with its parameters and the message of each bit of the flag word.
 template <typename T>
-static int mesh_query(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const MeshIdx<T>& M, const T* p, int64_t np, bool on_dev, T* out_d, int64_t* out_fi, T* out_bc,
-                      Timer& tm) {
+struct MeshPointsOp {                           // closest_points_on_mesh (src/closest_point_on_mesh.cpp:25-50)
+    const T* p;
+    using Params = MeshQuery<T>;
+    static constexpr int kRows3 = 2, kKeyBits = 30;
+    int validate(int64_t) const { return 0; }
+    int stage(Arena& ar, hipStream_t s, int64_t n, bool on_dev) { return stage_in(ar, p, n, on_dev, s, &p); }
+    void keys(hipStream_t s, int64_t n, const MeshHead<T>* h, unsigned long long* k, int* d_bad) const {
+        hipLaunchKernelGGL(k_mesh_qcodes<T>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p, (int)n, h, k, d_bad);
+    }
+    void walk(hipStream_t s, MeshQuery<T> a, T* val, int64_t n) const {
+        a.p = p; a.np = (int)n; a.out_d = val;
+        hipLaunchKernelGGL(k_mesh_closest<T>, dim3((unsigned)((n + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0, s, a);
+    }
+    static int message(int) { return fail(PCU_HIP_ERR_INVALID, "p must not contain NaN or infinite coordinates"); }
+};
+template <typename T>
+struct MeshRaysOp {                             // ray_mesh_intersection (src/ray_mesh_intersection.cpp:107-177)
+    const T* o; int64_t o_rows; const T* d; double ray_near, ray_far;
+    using Params = MeshRays<T>;
+    static constexpr int kRows3 = 3, kKeyBits = kMeshRayKeyBits;
+    int validate(int64_t n) const {
+        if (n < 0) return fail(PCU_HIP_ERR_INVALID, "negative number of rays");
+        if (n > kMeshMaxRows) return mesh_row_limit();
+        if (o_rows != 1 && o_rows != n)
+            return fail(PCU_HIP_ERR_INVALID, "ray_o and ray_d must have the same number of rows (one ray origin per ray direction). "
+                                             "(Note: ray_o can have one row to use the same origin for all directions)");
+        if (ray_near != ray_near || ray_far != ray_far) return fail(PCU_HIP_ERR_INVALID, "ray_near and ray_far must not be NaN");
+        return 0;
+    }
+    int o_stride(int64_t n) const { return o_rows == 1 && n != 1 ? 0 : 3; }
+    int stage(Arena& ar, hipStream_t s, int64_t n, bool on_dev) { return (stage_in(ar, o, o_rows, on_dev, s, &o) || stage_in(ar, d, n, on_dev, s, &d)) ? -1 : 0; }
+    void keys(hipStream_t s, int64_t n, const MeshHead<T>* h, unsigned long long* k, int* d_bad) const {
+        hipLaunchKernelGGL(k_mesh_rkeys<T>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, o, o_stride(n), d, (int)n, h, k, d_bad);
+    }
+    void walk(hipStream_t s, MeshRays<T> a, T* val, int64_t n) const {
+        a.o = o; a.o_stride = o_stride(n); a.d = d; a.n = (int)n; a.near = (T)ray_near; a.far = (T)ray_far; a.out_t = val;
+        hipLaunchKernelGGL(k_mesh_rays<T>, dim3((unsigned)((n + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0, s, a);
+    }
+    static int message(int bad) {
+        return fail(PCU_HIP_ERR_INVALID, "%s must not contain NaN or infinite coordinates", (bad & kMeshBadOrigin) ? "ray_o" : "ray_d");
+    }
+};
+
+// Enqueues the rows of one operator and waits for them. Events 1 / 2 of the context bracket the query phase.
+template <typename T, typename Op>
+static int mesh_run(Arena& ar, hipStream_t s, const MeshIdx<T>& M, Op op, int64_t n, bool on_dev, T* out_val, int64_t* out_fi, T* out_bc, Timer& tm) {
     tm.mark(1);
-    if (np == 0) { tm.mark(2); HIP_WAIT(s); return 0; }
-    const T* dp = nullptr;
-    if (stage_in(ar, p, np, on_dev, s, &dp)) return -1;
+    if (n == 0) { tm.mark(2); HIP_WAIT(s); return 0; }
+    if (op.stage(ar, s, n, on_dev)) return -1;
     int* d_bad = nullptr;
     unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
-    if (aalloc(ar, &d_bad, 1) || aalloc(ar, &ka, (size_t)np) || aalloc(ar, &kb, (size_t)np) || aalloc(ar, &ia, (size_t)np) || aalloc(ar, &ib, (size_t)np)) return -1;
-    T *d_d = out_d, *d_bc = out_bc; long long* d_fi = reinterpret_cast<long long*>(out_fi);
-    if (!on_dev && (aalloc(ar, &d_d, (size_t)np) || aalloc(ar, &d_fi, (size_t)np) || aalloc(ar, &d_bc, (size_t)np * 3))) return -1;
-    const int nb = (int)((np + kBlock - 1) / kBlock);
+    if (aalloc(ar, &d_bad, 1) || aalloc(ar, &ka, (size_t)n) || aalloc(ar, &kb, (size_t)n) || aalloc(ar, &ia, (size_t)n) || aalloc(ar, &ib, (size_t)n)) return -1;
+    T *d_val = out_val, *d_bc = out_bc; long long* d_fi = reinterpret_cast<long long*>(out_fi);
+    if (!on_dev && (aalloc(ar, &d_val, (size_t)n) || aalloc(ar, &d_fi, (size_t)n) || aalloc(ar, &d_bc, (size_t)n * 3))) return -1;
     HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_mesh_qcodes<T>, dim3(nb), dim3(kBlock), 0, s, dp, (int)np, (const MeshHead<T>*)M.head, ka, d_bad);
-    if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)np, 30)) return -1;
-    MeshQuery<T> a;
-    a.p = dp; a.order = ia; a.np = (int)np; a.ix = M;
-    a.out_d = d_d; a.out_fi = d_fi; a.out_bc = d_bc;
+    op.keys(s, n, M.head, ka, d_bad);
+    if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)n, Op::kKeyBits)) return -1;
+    typename Op::Params a{};
+    a.order = ia; a.ix = M; a.out_fi = d_fi; a.out_bc = d_bc;
     a.cancel_word = g_cancel_mirror.load(std::memory_order_relaxed); a.cancel_gen = t_call_gen;
-    hipLaunchKernelGGL(k_mesh_closest<T>, dim3((unsigned)((np + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0, s, a);
+    op.walk(s, a, d_val, n);
     HIP_TRY(hipGetLastError());
     tm.mark(2);
     int bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
     if (!on_dev) {
-        HIP_TRY(hipMemcpyAsync(out_d, d_d, (size_t)np * sizeof(T), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)np * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)np * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_val, d_val, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)n * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
     }
     HIP_WAIT(s);
-    if (bad) return fail(PCU_HIP_ERR_INVALID, "p must not contain NaN or infinite coordinates");
-    return 0;
+    return bad ? Op::message(bad) : 0;
 }
 static void mesh_stats(pcu_hip_stats* st, Timer& tm, int64_t np, bool built) {
     if (!st) return;
@@ -133,24 +179,33 @@ static void mesh_stats(pcu_hip_stats* st, Timer& tm, int64_t np, bool built) {
     st->ms_total = built ? tm.span(0, 2) : st->ms_search;
 }
 
-// closest_points_on_mesh (src/closest_point_on_mesh.cpp:25-50): index, queries and temporaries in the call's arena
-template <typename T>
-static int mesh_oneshot_impl(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* p, int64_t np,
-                             T* out_d, int64_t* out_fi, T* out_bc, unsigned flags, void* stream, pcu_hip_stats* st) {
-    if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
+// One call of either operator. Mesh given (`mesh`): index, rows and temporaries in the call's arena; index given (`ix`): rows and temporaries.
+template <typename T> struct MeshGiven { const T* v; int64_t nv; const void* f; int64_t nf; int f_kind; };
+template <typename T, typename Op>
+static int mesh_call(pcu_hip_ctx* c, const MeshGiven<T>* mesh, const pcu_hip_mesh_index* ix, Op op, int64_t n, T* out_val, int64_t* out_fi, T* out_bc,
+                     unsigned flags, void* stream, pcu_hip_stats* st) {
+    if (mesh ? !c : (!c || !ix)) return fail(PCU_HIP_ERR_INVALID, mesh ? "null context" : "null context / mesh index");
     if (st) memset(st, 0, sizeof *st);
-    if (int rc = mesh_validate(nv, nf, np, f_kind)) return rc;
+    if (!mesh) {
+        if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the mesh index was built for the other scalar type");
+        if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the mesh index lives on another device than the context");
+    }
+    if (int rc = op.validate(n)) return rc;
+    if (mesh) { if (int rc = mesh_validate(mesh->nv, mesh->nf, n, mesh->f_kind)) return rc; }
+    else if (n < 0 || n > kMeshMaxRows) return mesh_row_limit();
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
     hipStream_t s = pick_stream(c, flags, stream);
     c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
-    if (ctx_begin(c, mesh_index_bytes<T>(nf) + mesh_build_bytes<T>(nv, nf, f_kind, on_dev) + mesh_query_bytes<T>(np, on_dev))) return PCU_HIP_ERR_RUNTIME;
+    size_t bytes = mesh_run_bytes<T>(n, Op::kRows3, on_dev);
+    if (mesh) bytes += mesh_index_bytes<T>(mesh->nf) + mesh_build_bytes<T>(mesh->nv, mesh->nf, mesh->f_kind, on_dev);
+    if (ctx_begin(c, bytes)) return PCU_HIP_ERR_RUNTIME;
     Arena ar{c};
     Timer tm{c, s, st};
-    MeshIdx<T> M;
-    tm.mark(0);
-    int rc = mesh_build<T>(ar, ar, s, v, nv, f, nf, f_kind, on_dev, M);
-    if (!rc) rc = mesh_query<T>(c, ar, s, M, p, np, on_dev, out_d, out_fi, out_bc, tm);
-    if (!rc) mesh_stats(st, tm, np, true);
+    MeshIdx<T> built;
+    int rc = 0;
+    if (mesh) { tm.mark(0); rc = mesh_build<T>(ar, ar, s, mesh->v, mesh->nv, mesh->f, mesh->nf, mesh->f_kind, on_dev, built); }
+    if (!rc) rc = mesh_run<T>(ar, s, mesh ? built : mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)), op, n, on_dev, out_val, out_fi, out_bc, tm);
+    if (!rc) mesh_stats(st, tm, n, mesh != nullptr);
     return attempt_exit(c, rc);
 }
 
@@ -167,135 +222,13 @@ static int mesh_index_create_impl(pcu_hip_ctx* c, const T* v, int64_t nv, const 
     const size_t bytes = mesh_index_bytes<T>(nf);
     if (hipMalloc(&p->mem, bytes) != hipSuccess) { p->mem = nullptr; mesh_index_free(p); return fail(PCU_HIP_ERR_RUNTIME, "out of device memory for the mesh index"); }
     if (ctx_begin(c, mesh_build_bytes<T>(nv, nf, f_kind, on_dev))) { mesh_index_free(p); return PCU_HIP_ERR_RUNTIME; }
-    pcu_hip_ctx holder;                             // only its arena fields are used: a bump allocator over the index's own block
-    holder.device = c->device; holder.arena = static_cast<char*>(p->mem); holder.arena_cap = bytes; holder.arena_off = 0;
-    Arena ari{&holder}, ar{c};
+    ArenaState blk;                                 // a bump allocator over the index's own block
+    blk.base = static_cast<char*>(p->mem); blk.cap = bytes;
+    Arena ari{&blk}, ar{c};
     int rc = mesh_build<T>(ari, ar, s, v, nv, f, nf, f_kind, on_dev, mesh_idx<T>(p));
     if (!rc) rc = wait_stream(s);                   // (the temporaries go back to the context with this call)
-    if (!holder.extra.empty()) {
-        (void)hipDeviceSynchronize();
-        for (void* q : holder.extra) (void)hipFree(q);
-        if (!rc) rc = fail(PCU_HIP_ERR_RUNTIME, "internal: mesh index block too small");
-    }
-    rc = attempt_exit(c, rc);
+    rc = attempt_exit(c, index_block_exit(blk, rc, "mesh index"));
     if (rc) { (void)hipStreamSynchronize(s); mesh_index_free(p); return rc; }
     *out = p;
     return 0;
-}
-
-template <typename T>
-static int mesh_index_closest_impl(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* p, int64_t np, T* out_d, int64_t* out_fi, T* out_bc,
-                                   unsigned flags, void* stream, pcu_hip_stats* st) {
-    if (!c || !ix) return fail(PCU_HIP_ERR_INVALID, "null context / mesh index");
-    if (st) memset(st, 0, sizeof *st);
-    if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the mesh index was built for the other scalar type");
-    if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the mesh index lives on another device than the context");
-    if (np < 0 || np > 0x07fffff0ll) return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported");
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
-    if (ctx_begin(c, mesh_query_bytes<T>(np, on_dev))) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    Timer tm{c, s, st};
-    int rc = mesh_query<T>(c, ar, s, mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)), p, np, on_dev, out_d, out_fi, out_bc, tm);
-    if (!rc) mesh_stats(st, tm, np, false);
-    return attempt_exit(c, rc);
-}
-
-// ---------------------------------------------------------------------------------------------------- rays (mesh.h)
-template <typename T>
-static size_t mesh_rays_bytes(int64_t n, bool on_dev) {
-    size_t b = mesh_sort_bytes(n) + 4096;
-    if (!on_dev) b += 3 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n * sizeof(T), 256) + align_up((size_t)n * 8, 256);
-    return b;
-}
-static int mesh_rays_validate(int64_t o_rows, int64_t n, double ray_near, double ray_far) {
-    if (n < 0) return fail(PCU_HIP_ERR_INVALID, "negative number of rays");
-    if (n > 0x07fffff0ll) return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported");
-    if (o_rows != 1 && o_rows != n)
-        return fail(PCU_HIP_ERR_INVALID, "ray_o and ray_d must have the same number of rows (one ray origin per ray direction). "
-                                         "(Note: ray_o can have one row to use the same origin for all directions)");
-    if (ray_near != ray_near || ray_far != ray_far) return fail(PCU_HIP_ERR_INVALID, "ray_near and ray_far must not be NaN");
-    return 0;
-}
-
-// Enqueues the rays and waits for them. Events 1 / 2 of the context bracket the query phase.
-template <typename T>
-static int mesh_rays(pcu_hip_ctx* c, Arena& ar, hipStream_t s, const MeshIdx<T>& M, const T* o, int64_t o_rows, const T* d, int64_t n, double ray_near,
-                     double ray_far, bool on_dev, int64_t* out_fi, T* out_bc, T* out_t, Timer& tm) {
-    tm.mark(1);
-    if (n == 0) { tm.mark(2); HIP_WAIT(s); return 0; }
-    const T *dor = nullptr, *dd = nullptr;
-    if (stage_in(ar, o, o_rows, on_dev, s, &dor) || stage_in(ar, d, n, on_dev, s, &dd)) return -1;
-    int* d_bad = nullptr;
-    unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
-    if (aalloc(ar, &d_bad, 1) || aalloc(ar, &ka, (size_t)n) || aalloc(ar, &kb, (size_t)n) || aalloc(ar, &ia, (size_t)n) || aalloc(ar, &ib, (size_t)n)) return -1;
-    T *d_t = out_t, *d_bc = out_bc; long long* d_fi = reinterpret_cast<long long*>(out_fi);
-    if (!on_dev && (aalloc(ar, &d_t, (size_t)n) || aalloc(ar, &d_fi, (size_t)n) || aalloc(ar, &d_bc, (size_t)n * 3))) return -1;
-    const int o_stride = o_rows == 1 && n != 1 ? 0 : 3;
-    const int nb = (int)((n + kBlock - 1) / kBlock);
-    HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_mesh_rkeys<T>, dim3(nb), dim3(kBlock), 0, s, dor, o_stride, dd, (int)n, (const MeshHead<T>*)M.head, ka, d_bad);
-    if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)n, kMeshRayKeyBits)) return -1;
-    MeshRays<T> a;
-    a.o = dor; a.o_stride = o_stride; a.d = dd; a.order = ia; a.n = (int)n; a.ix = M;
-    a.near = (T)ray_near; a.far = (T)ray_far;
-    a.out_fi = d_fi; a.out_bc = d_bc; a.out_t = d_t;
-    a.cancel_word = g_cancel_mirror.load(std::memory_order_relaxed); a.cancel_gen = t_call_gen;
-    hipLaunchKernelGGL(k_mesh_rays<T>, dim3((unsigned)((n + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    tm.mark(2);
-    int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (!on_dev) {
-        HIP_TRY(hipMemcpyAsync(out_t, d_t, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)n * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
-    }
-    HIP_WAIT(s);
-    if (bad & kMeshBadOrigin) return fail(PCU_HIP_ERR_INVALID, "ray_o must not contain NaN or infinite coordinates");
-    if (bad & kMeshBadDir) return fail(PCU_HIP_ERR_INVALID, "ray_d must not contain NaN or infinite coordinates");
-    return 0;
-}
-
-// ray_mesh_intersection (src/ray_mesh_intersection.cpp:107-177): index, rays and temporaries in the call's arena
-template <typename T>
-static int mesh_rays_oneshot_impl(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* o, int64_t o_rows, const T* d,
-                                  int64_t n, double ray_near, double ray_far, int64_t* out_fi, T* out_bc, T* out_t, unsigned flags, void* stream,
-                                  pcu_hip_stats* st) {
-    if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
-    if (st) memset(st, 0, sizeof *st);
-    if (int rc = mesh_rays_validate(o_rows, n, ray_near, ray_far)) return rc;
-    if (int rc = mesh_validate(nv, nf, n, f_kind)) return rc;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
-    if (ctx_begin(c, mesh_index_bytes<T>(nf) + mesh_build_bytes<T>(nv, nf, f_kind, on_dev) + mesh_rays_bytes<T>(n, on_dev))) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    Timer tm{c, s, st};
-    MeshIdx<T> M;
-    tm.mark(0);
-    int rc = mesh_build<T>(ar, ar, s, v, nv, f, nf, f_kind, on_dev, M);
-    if (!rc) rc = mesh_rays<T>(c, ar, s, M, o, o_rows, d, n, ray_near, ray_far, on_dev, out_fi, out_bc, out_t, tm);
-    if (!rc) mesh_stats(st, tm, n, true);
-    return attempt_exit(c, rc);
-}
-
-template <typename T>
-static int mesh_index_rays_impl(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* o, int64_t o_rows, const T* d, int64_t n, double ray_near,
-                                double ray_far, int64_t* out_fi, T* out_bc, T* out_t, unsigned flags, void* stream, pcu_hip_stats* st) {
-    if (!c || !ix) return fail(PCU_HIP_ERR_INVALID, "null context / mesh index");
-    if (st) memset(st, 0, sizeof *st);
-    if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the mesh index was built for the other scalar type");
-    if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the mesh index lives on another device than the context");
-    if (int rc = mesh_rays_validate(o_rows, n, ray_near, ray_far)) return rc;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
-    if (ctx_begin(c, mesh_rays_bytes<T>(n, on_dev))) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    Timer tm{c, s, st};
-    int rc = mesh_rays<T>(c, ar, s, mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)), o, o_rows, d, n, ray_near, ray_far, on_dev, out_fi, out_bc, out_t, tm);
-    if (!rc) mesh_stats(st, tm, n, false);
-    return attempt_exit(c, rc);
 }

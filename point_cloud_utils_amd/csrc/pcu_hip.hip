@@ -195,6 +195,13 @@ static bool attr_unset_here(std::atomic<unsigned long long>& mask) {
     return !(mask.fetch_or(bit) & bit);
 }
 // ------------------------------------------------------------------------------------------------ context
+// What a bump allocator (Arena) works on: one device block and what had to be hipMalloc'ed on top of it. A context has one for its calls'
+// temporaries; an index object's build makes one over the object's own block.
+struct ArenaState {
+    char* base = nullptr; size_t cap = 0, off = 0;
+    std::vector<void*> extra;                 // overflow allocations (of the current call)
+    size_t extra_bytes = 0;
+};
 struct pcu_hip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -202,9 +209,7 @@ struct pcu_hip_ctx {
     hipStream_t aux_stream = nullptr;          // second lane for two-sided ops: the two clouds' index builds and the two
                                                // search directions are independent and latency-bound, so they overlap
     hipEvent_t jev[4] = {};                    // fork/join events between the caller's stream and aux_stream
-    char* arena = nullptr; size_t arena_cap = 0, arena_off = 0;
-    std::vector<void*> extra;                 // overflow allocations of the current call
-    size_t extra_bytes = 0;
+    ArenaState arena;                         // the calls' workspace
     size_t extra_hint = 0;                    // largest overflow seen: added to the arena request of later calls
     hipEvent_t ev[8] = {};
     hipEvent_t kev[8] = {};                    // brackets of the main (pass-0) search launches of a call
@@ -286,19 +291,31 @@ static void drain_call(hipStream_t s) {
 }
 
 struct Arena {
-    pcu_hip_ctx* c;
-    // Bump allocation out of the context arena; falls back to a tracked hipMalloc when the arena is full
-    // (only happens for lazily built coarse grids).
+    ArenaState* a = nullptr;
+    Arena() = default;
+    Arena(pcu_hip_ctx* c) : a(&c->arena) {}
+    explicit Arena(ArenaState* st) : a(st) {}
+    // Bump allocation out of the block; falls back to a tracked hipMalloc when the block is full
+    // (in a context, only happens for lazily built coarse grids).
     int alloc(void** out, size_t bytes) {
         bytes = align_up(bytes ? bytes : 16, 256);
-        if (c->arena_off + bytes <= c->arena_cap) { *out = c->arena + c->arena_off; c->arena_off += bytes; return 0; }
+        if (a->off + bytes <= a->cap) { *out = a->base + a->off; a->off += bytes; return 0; }
         void* p = nullptr;
         HIP_TRY(hipMalloc(&p, bytes));
-        c->extra.push_back(p); c->extra_bytes += bytes;
+        a->extra.push_back(p); a->extra_bytes += bytes;
         *out = p;
         return 0;
     }
 };
+// The foot of a build into an index object's own block, which was sized to hold all of it: overflow blocks go, and having needed one is an
+// internal error (unless the build has failed already).
+static int index_block_exit(ArenaState& blk, int rc, const char* what) {
+    if (blk.extra.empty()) return rc;
+    (void)hipDeviceSynchronize();
+    for (void* q : blk.extra) (void)hipFree(q);
+    blk.extra.clear(); blk.extra_bytes = 0;
+    return rc ? rc : fail(PCU_HIP_ERR_RUNTIME, "internal: %s block too small", what);
+}
 template <typename U> static int aalloc(Arena& a, U** out, size_t count) { return a.alloc((void**)out, count * sizeof(U)); }
 
 // Bump allocator over the context's kd workspace (grown, never shrunk; growth invalidates the cached graphs).
@@ -344,17 +361,18 @@ static int ctx_begin(pcu_hip_ctx* c, size_t want_bytes) {
         c->cancel_epoch = ep;
     }
     want_bytes += c->extra_hint;                // what earlier calls had to hipMalloc on top of their estimate (refitted / coarse grids)
-    if (want_bytes > c->arena_cap) {
-        if (c->arena) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->arena)); c->arena = nullptr; c->arena_cap = 0; }
+    ArenaState& ws = c->arena;
+    if (want_bytes > ws.cap) {
+        if (ws.base) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(ws.base)); ws.base = nullptr; ws.cap = 0; }
         size_t cap = align_up(want_bytes + (want_bytes >> 3), 1 << 20);
-        HIP_TRY(hipMalloc((void**)&c->arena, cap));
-        c->arena_cap = cap;
+        HIP_TRY(hipMalloc((void**)&ws.base, cap));
+        ws.cap = cap;
     }
-    c->arena_off = 0;
+    ws.off = 0;
     c->n_kev = 0;
     // debugging: poison the workspace (PCU_HIP_DEBUG_POISON=<byte>) so that reads of memory no kernel of this call wrote show up
     static const int poison = getenv("PCU_HIP_DEBUG_POISON") ? atoi(getenv("PCU_HIP_DEBUG_POISON")) : -1;
-    if (poison >= 0 && c->arena) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipMemset(c->arena, poison, c->arena_cap)); HIP_TRY(hipDeviceSynchronize()); }
+    if (poison >= 0 && ws.base) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipMemset(ws.base, poison, ws.cap)); HIP_TRY(hipDeviceSynchronize()); }
     return 0;
 }
 // Sum of the bracketed main-search kernel durations of this call (valid after the final stream sync).
@@ -369,9 +387,10 @@ static void collect_kernel_times(pcu_hip_ctx* c, pcu_hip_stats* st) {
 static void ctx_end(pcu_hip_ctx* c) {
     // overflow blocks cost a hipMalloc + hipFree (device-synchronising, ~ms) per call: remember how much was needed so that
     // the next call's arena holds it (tight-cluster Chamfer 9.5 -> 4.9 ms once its refit grids stopped overflowing)
-    if (c->extra_bytes > c->extra_hint) c->extra_hint = c->extra_bytes + (c->extra_bytes >> 2);
-    for (void* p : c->extra) (void)hipFree(p);
-    c->extra.clear(); c->extra_bytes = 0;
+    ArenaState& ws = c->arena;
+    if (ws.extra_bytes > c->extra_hint) c->extra_hint = ws.extra_bytes + (ws.extra_bytes >> 2);
+    for (void* p : ws.extra) (void)hipFree(p);
+    ws.extra.clear(); ws.extra_bytes = 0;
 }
 
 // ------------------------------------------------------------------------------------------------ grid index
@@ -2653,14 +2672,11 @@ static int index_create_impl(pcu_hip_ctx* c, const T* dataset, int64_t nr, int k
         }
         const size_t bytes = index_bytes<T>(nr, p->occ) + 4096;
         if (hipMalloc(&p->mem, bytes) != hipSuccess) { rc = fail(PCU_HIP_ERR_RUNTIME, "out of device memory for the index"); break; }
-        pcu_hip_ctx holder;                         // only its arena fields are used: a bump allocator over the index's own block
-        holder.device = c->device; holder.arena = static_cast<char*>(p->mem); holder.arena_cap = bytes; holder.arena_off = 0;
-        Arena ar{&holder};
+        ArenaState blk;                             // a bump allocator over the index's own block
+        blk.base = static_cast<char*>(p->mem); blk.cap = bytes;
+        Arena ar{&blk};
         GridIndex<T>& g = index_grid_mut<T>(p);
-        if (index_alloc(ar, g, nr, p->occ) || !holder.extra.empty()) {
-            for (void* q : holder.extra) (void)hipFree(q);
-            rc = fail(PCU_HIP_ERR_RUNTIME, "internal: index block too small"); break;
-        }
+        if ((rc = index_block_exit(blk, index_alloc(ar, g, nr, p->occ), "index"))) break;
         if ((rc = index_build<T>(g, static_cast<const T*>(p->pts), p->occ, s))) break;
         if ((rc = check_nonfinite<T>(g.gp, kNfNaN | kNfBothInf, s))) break;
     } while (0);
@@ -2769,7 +2785,7 @@ void pcu_hip_ctx_destroy(pcu_hip_ctx* c) {
     if (c->tickets) (void)hipFree(c->tickets);
     if (c->fill2) (void)hipFree(c->fill2);
     if (c->geo.dev) (void)hipFree(c->geo.dev);
-    if (c->arena) (void)hipFree(c->arena);
+    if (c->arena.base) (void)hipFree(c->arena.base);
     for (hipEvent_t e : {c->kd_spec.ev_fork, c->kd_spec.ev_init, c->kd_spec.ev_done}) if (e) (void)hipEventDestroy(e);
     kd_graph_drop(c);
     if (c->kd_ws) (void)hipFree(c->kd_ws);
@@ -2784,7 +2800,7 @@ void pcu_hip_ctx_destroy(pcu_hip_ctx* c) {
     delete c;
 }
 int pcu_hip_ctx_set_cell_occupancy(pcu_hip_ctx* c, double ppc) { if (!c) return fail(PCU_HIP_ERR_INVALID, "null context"); c->occupancy = ppc; return 0; }
-int64_t pcu_hip_ctx_workspace_bytes(pcu_hip_ctx* c) { return c ? (int64_t)c->arena_cap : 0; }
+int64_t pcu_hip_ctx_workspace_bytes(pcu_hip_ctx* c) { return c ? (int64_t)c->arena.cap : 0; }
 
 int pcu_hip_knn_f32(pcu_hip_ctx* c, const float* q, int64_t nq, const float* r, int64_t nr, int k, int max_leaf, float* od, int64_t* oi,
                     unsigned flags, void* stream, pcu_hip_stats* st) { CallGuard dg(c); return abi_rc(knn_impl<float>(c, q, nq, r, nr, k, max_leaf, od, oi, flags, stream, st)); }
@@ -2915,7 +2931,8 @@ void pcu_hip_index_destroy(pcu_hip_index* ix) {
 #define PCU_MESH(SUF, T)                                                                                                                              \
 int pcu_hip_closest_points_on_mesh_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* p, int64_t np,      \
                                          T* out_d, int64_t* out_fi, T* out_bc, unsigned flags, void* stream, pcu_hip_stats* st) {                   \
-    CallGuard dg(c); return abi_rc(mesh_oneshot_impl<T>(c, v, nv, f, nf, f_kind, p, np, out_d, out_fi, out_bc, flags, stream, st)); }                \
+    CallGuard dg(c); const MeshGiven<T> m{v, nv, f, nf, f_kind};                                                                                     \
+    return abi_rc(mesh_call<T>(c, &m, nullptr, MeshPointsOp<T>{p}, np, out_d, out_fi, out_bc, flags, stream, st)); }                                 \
 int pcu_hip_mesh_index_create_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, unsigned flags, void* stream,    \
                                     pcu_hip_mesh_index** out) {                                                                                      \
     CallGuard dg(c);                                                                                                                                 \
@@ -2924,7 +2941,7 @@ int pcu_hip_mesh_index_create_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, cons
     return rc; }                                                                                                                                     \
 int pcu_hip_mesh_index_closest_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* p, int64_t np, T* out_d, int64_t* out_fi, T* out_bc,     \
                                      unsigned flags, void* stream, pcu_hip_stats* st) {                                                              \
-    CallGuard dg(c); return abi_rc(mesh_index_closest_impl<T>(c, ix, p, np, out_d, out_fi, out_bc, flags, stream, st)); }
+    CallGuard dg(c); return abi_rc(mesh_call<T>(c, nullptr, ix, MeshPointsOp<T>{p}, np, out_d, out_fi, out_bc, flags, stream, st)); }
 PCU_MESH(f32, float) PCU_MESH(f64, double)
 #undef PCU_MESH
 // ray_mesh_intersection (mesh.h, mesh_host.h)
@@ -2932,12 +2949,13 @@ PCU_MESH(f32, float) PCU_MESH(f64, double)
 int pcu_hip_ray_mesh_intersection_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* ray_o, int64_t o_rows, \
                                         const T* ray_d, int64_t n, double ray_near, double ray_far, int64_t* out_fi, T* out_bc, T* out_t,            \
                                         unsigned flags, void* stream, pcu_hip_stats* st) {                                                           \
-    CallGuard dg(c);                                                                                                                                 \
-    return abi_rc(mesh_rays_oneshot_impl<T>(c, v, nv, f, nf, f_kind, ray_o, o_rows, ray_d, n, ray_near, ray_far, out_fi, out_bc, out_t, flags, stream, st)); } \
+    CallGuard dg(c); const MeshGiven<T> m{v, nv, f, nf, f_kind};                                                                                     \
+    return abi_rc(mesh_call<T>(c, &m, nullptr, MeshRaysOp<T>{ray_o, o_rows, ray_d, ray_near, ray_far}, n, out_t, out_fi, out_bc, flags, stream, st)); } \
 int pcu_hip_mesh_index_rays_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* ray_o, int64_t o_rows, const T* ray_d, int64_t n,            \
                                   double ray_near, double ray_far, int64_t* out_fi, T* out_bc, T* out_t, unsigned flags, void* stream,               \
                                   pcu_hip_stats* st) {                                                                                               \
-    CallGuard dg(c); return abi_rc(mesh_index_rays_impl<T>(c, ix, ray_o, o_rows, ray_d, n, ray_near, ray_far, out_fi, out_bc, out_t, flags, stream, st)); }
+    CallGuard dg(c);                                                                                                                                 \
+    return abi_rc(mesh_call<T>(c, nullptr, ix, MeshRaysOp<T>{ray_o, o_rows, ray_d, ray_near, ray_far}, n, out_t, out_fi, out_bc, flags, stream, st)); }
 PCU_MESH_RAYS(f32, float) PCU_MESH_RAYS(f64, double)
 #undef PCU_MESH_RAYS
 int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }

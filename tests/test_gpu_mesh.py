@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import mesh_contract as mc
+import ray_contract as rc
 
 pytestmark = pytest.mark.gpu
 DTYPES = [np.float32, np.float64]
@@ -97,6 +98,22 @@ def test_bunny_every_input_kind_and_face_dtype(pcu, T):
         got = pcu.closest_points_on_mesh(tq, tv, tf)
         assert all(isinstance(x, torch.Tensor) and x.is_cuda for x in got) and got[1].dtype == tdt and got[0].dtype == tq.dtype
         _assert_same(got, want, ("torch", fdt))
+
+
+@pytest.mark.parametrize("T", DTYPES)
+@pytest.mark.parametrize("nf", [1, 4, 5])
+def test_meshes_of_one_leaf_and_of_two(pcu, nf, T):
+    """1 face, 4 faces (one full leaf: the root is the leaf and the stack is never used), 5 faces (two leaves, one of them mostly padding)."""
+    rng = np.random.default_rng(nf)
+    v = rng.random((3 * nf, 3)).astype(T)
+    f = rng.permutation(3 * nf).reshape(nf, 3).astype(np.int64)
+    q = np.concatenate([mc.surface_samples(v, f, 200, 3), rng.random((400, 3)) * 3 - 1]).astype(T)
+    want = _brute(q, v, f)
+    assert len(np.unique(want[1])) == nf                                  # (every face is some query's closest)
+    _assert_same(pcu.closest_points_on_mesh(q, v, f), want, (nf, "numpy"))
+    got = pcu.closest_points_on_mesh(*_torch(q, v, f))
+    assert all(x.is_cuda for x in got)
+    _assert_same(got, want, (nf, "torch"))
 
 
 @pytest.fixture(scope="module")
@@ -277,6 +294,31 @@ def test_mesh_index_same_rows_as_the_one_shot_call(pcu, T):
     del tv, tf                                                            # (the mesh was copied)
     _assert_same(mesh.closest_points(_torch(q1)[0]), one1, "index built from tensors")
     mesh.close(); mesh.close()
+
+
+def _assert_bits(got, want, what):
+    """Three arrays of either operator, row for row: same shapes, dtypes and bits."""
+    for k, (a, b) in enumerate(zip(got, want)):
+        a, b = _to_numpy(a), _to_numpy(b)
+        assert a.dtype == b.dtype and a.shape == b.shape, (what, k)
+        same = a == b if a.dtype.kind in "iu" else _bits(a) == _bits(b)
+        assert same.all(), (what, k, f"{int((~same).sum())} of {same.size} values differ")
+
+
+@pytest.mark.parametrize("T", DTYPES)
+def test_points_rays_points_on_one_mesh_index(pcu, T):
+    """Both operators interleaved on one index (and one context): every call gives the rows of its one-shot call, the third those of the first."""
+    v, f = mc.bunny(T)
+    q = mc.query_sets(v, f, 2000, T, seed=67)["box"]
+    o, d = rc.rays_box_to_surface(v, f, 2000, T, 68)                      # (test_gpu_rays' family "box")
+    for kind, conv in (("host arrays", lambda *a: a), ("device tensors", _torch)):
+        cv, cf, cq, co, cd = conv(v, f, q, o, d)
+        one_p, one_r = pcu.closest_points_on_mesh(cq, cv, cf), pcu.ray_mesh_intersection(cv, cf, co, cd)
+        assert (_to_numpy(one_r[0]) >= 0).sum() >= 1000
+        with pcu.MeshIndex(cv, cf) as mesh:
+            first, rays, third = mesh.closest_points(cq), mesh.intersect_rays(co, cd), mesh.closest_points(cq)
+        _assert_bits(first, one_p, (kind, "points")); _assert_bits(rays, one_r, (kind, "rays")); _assert_bits(third, one_p, (kind, "points again"))
+        _assert_bits(third, first, (kind, "third against first"))
 
 
 # ---------------------------------------------------------------------------------------------------- 3. size
