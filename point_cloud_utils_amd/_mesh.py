@@ -1,6 +1,7 @@
 """closest_points_on_mesh: the reference's binding (src/closest_point_on_mesh.cpp:9-50) over the HIP linear BVH of csrc/mesh.h, and MeshIndex,
 the mesh-side twin of DatasetIndex. Same arguments, error texts, dtypes and return order; the rows follow this library's deterministic contract
- instead of libigl's AABB tree."""
+ instead of libigl's AABB tree. ray_mesh_intersection (f7), triangle_soup_fast_winding_number and signed_distance_to_mesh
+(f8, csrc/mesh_winding.h) are queries of the same index."""
 import ctypes
 
 import numpy as np
@@ -54,15 +55,19 @@ def _check_mesh(v, f, want=None):
     return dv, sv[0], sf[0]
 
 
-def _check_points(p, want=None):
-    """Scalar type, then validate_point_cloud (src/common/common.h:58-74; zero rows are allowed), then the row limit. Returns (dtype name, #p)."""
+def _check_points_dtype(p, want=None):
     from . import _dtype_name, _shape2
     dp = _dtype_name(p)
     if dp not in ("float32", "float64"):
         raise ValueError(f"Invalid scalar type ({dp}) for argument 'p'. Expected one of ['float32', 'float64'].")
     if want is not None and dp != want:
         raise ValueError(f"Invalid scalar type ({dp}) for argument 'p'. Expected it to match the indexed mesh which is of type {want}.")
-    sp = _shape2(p)
+    return dp, _shape2(p)
+
+
+def _check_points(p, want=None):
+    """Scalar type, then validate_point_cloud (src/common/common.h:58-74; zero rows are allowed), then the row limit. Returns (dtype name, #p)."""
+    dp, sp = _check_points_dtype(p, want)
     if sp[1] != 3:
         raise ValueError(f"Only 3D inputs are supported: v must have shape (n, 3) (n > 0). Got points.shape =({sp[0]}, {sp[1]}).")
     _check_rows(sp[0])
@@ -156,6 +161,122 @@ def closest_points_on_mesh(p, v, f):
     dist, fi, bc = _results(d, n)
     _call("closest_points_on_mesh", d, d.pb, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)], d.pa, n, _Dev.ptr(dist), _Dev.ptr(fi), _Dev.ptr(bc))
     return _finish(dist, fi, bc, ff, n, _POINT_ORDER)
+
+
+def _check_points_nonzero(p):
+    """validate_point_cloud(p, allow_0=false) (src/common/common.h:58-74), then the row limit. Returns #p."""
+    from . import _shape2
+    sp = _shape2(p)
+    if sp[0] == 0:
+        raise ValueError(f"Invalid input point cloud with zero points: points must have shape (n, 3) (n > 0). Got points.shape =({sp[0]}, {sp[1]}).")
+    if sp[1] != 3:
+        raise ValueError(f"Only 3D inputs are supported: v must have shape (n, 3) (n > 0). Got points.shape =({sp[0]}, {sp[1]}).")
+    _check_rows(sp[0])
+    return sp[0]
+
+
+def _check_beta(beta):
+    beta = float(beta)
+    if not beta > 0.0:
+        raise ValueError("beta must be greater than 0 (finite, or +inf for the plain sum over all faces)")
+    return beta
+
+
+def _check_bounds(lower_bound, upper_bound):
+    lower_bound, upper_bound = float(lower_bound), float(upper_bound)
+    if lower_bound != lower_bound or upper_bound != upper_bound:
+        raise ValueError("lower_bound and upper_bound must not be NaN")
+    if lower_bound > upper_bound:
+        raise ValueError("lower_bound must not be greater than upper_bound")
+    return lower_bound, upper_bound
+
+
+def _int32_like(d):
+    """An empty int32 array of the kind of the call's results: signed_distance_to_mesh returns int32 faces (the reference's EigenDense<int>)."""
+    if d.torch:
+        import torch
+        return torch.empty((0,), dtype=torch.int32)
+    return np.empty((0,), dtype=np.int32)
+
+
+def _scalar_rows(w, n):
+    return w.reshape(()) if n == 1 else w
+
+
+def triangle_soup_fast_winding_number(v, f, p, *, beta=2.0):
+    """
+    Compute a consistent inside/outside field given a triangle soup and evaluate that field at a set of query points
+
+    Args:
+      v : (#v, 3)-shaped array of mesh vertex positions (float32 or float64; numpy, or a CUDA/HIP torch tensor)
+      f : (#f, 3)-shaped array of mesh face indexes into v (int32, int64, uint32 or uint64; int32 / int64 for torch)
+      p : (#p, 3)-shaped array of query positions at which to evaluate the winding number field (v's dtype)
+      beta : accuracy of the fast evaluation (not in the reference API, which uses libigl's default 2): a tree node farther from the query
+             than beta times its radius is replaced by a three-term expansion; float('inf') gives the plain sum over all faces
+
+    Returns:
+      A (#p,)-shaped array with the generalized winding number of each query point: about 1 inside a closed, outward-oriented mesh and
+      about 0 outside.
+
+    Notes:
+      The fast winding number of Barill et al. (2018) with the tree, moments and evaluation order stated in DESIGN.md (f8): finite for every
+      finite query, equal bits for equal arguments. Non-finite coordinates, face indices outside [0, #v) and arrays of more than 2**27 - 16
+      rows raise ValueError.
+    """
+    from . import _Dev, _dtype_name, _is_torch
+    dv = _check_scalar_v(v)
+    _check_face_dtype(f)
+    dp = _dtype_name(p)
+    if dp != dv:
+        raise ValueError(f"Invalid scalar type ({dp}) for argument 'p'. Expected it to match argument 'v' which is of type {dv}.")
+    _, nv, nf = _check_mesh(v, f)
+    n = _check_points_nonzero(p)
+    beta = _check_beta(beta)
+    if not (_is_torch(p) or _is_torch(v) or _is_torch(f)):
+        _host_mesh_checks(np.asarray(v), np.asarray(f))
+        _host_point_checks(np.asarray(p))
+    d = _Dev(p, v)
+    ff = _faces_for(d, f)
+    w = d.empty((n,), "T")
+    _call("triangle_soup_fast_winding_number", d, d.pb, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)], d.pa, n, beta, _Dev.ptr(w))
+    return _scalar_rows(w, n)
+
+
+def signed_distance_to_mesh(p, v, f, lower_bound=-np.inf, upper_bound=np.inf):
+    """
+    Computes signed distances of a point cloud with respect to a Mesh using Fast Winding Numbers
+
+    Args:
+      p : (#p, 3)-shaped array point cloud (one 3D point per row; float32 or float64; numpy, or a CUDA/HIP torch tensor)
+      v : (#v, 3)-shaped array of mesh vertex positions (one vertex position per row; p's dtype)
+      f : (#f, 3)-shaped array of mesh face indexes into v (int32, int64, uint32 or uint64; int32 / int64 for torch)
+      lower_bound : The minimum distance value possible (use this to clamp SDF values). negative infinite by default
+      upper_bound : The maximum distance value possible (use this to clamp SDF values). infinite by default
+
+    Returns:
+      s : a (#p,) shaped array of signed distance values for each query point in p
+      fi : a (#p,) shaped int32 array of indices to the closest face for each query point in p
+      bc : a (#p, 3) shaped array of barycentric coordinates for the closest point on the mesh to each query point in p
+
+    Notes:
+      |s|, fi and bc are the rows of closest_points_on_mesh(p, v, f) bit for bit; s is negative where the fast winding number (beta = 2) is
+      above 1/2 in absolute value; then s is clamped to [lower_bound, upper_bound] (both rounded to float32 first, as the reference's
+      arguments are). A NaN bound or lower_bound > upper_bound raises ValueError.
+    """
+    from . import _Dev, _is_torch
+    dp, _ = _check_points_dtype(p)
+    _, nv, nf = _check_mesh(v, f, want=dp)
+    n = _check_points_nonzero(p)
+    lower_bound, upper_bound = _check_bounds(lower_bound, upper_bound)
+    if not (_is_torch(p) or _is_torch(v) or _is_torch(f)):
+        _host_mesh_checks(np.asarray(v), np.asarray(f))
+        _host_point_checks(np.asarray(p))
+    d = _Dev(p, v)
+    ff = _faces_for(d, f)
+    s, fi, bc = _results(d, n)
+    _call("signed_distance_to_mesh", d, d.pb, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)], d.pa, n, lower_bound, upper_bound, 2.0,
+          _Dev.ptr(s), _Dev.ptr(fi), _Dev.ptr(bc))
+    return _finish(s, fi, bc, _int32_like(d), n, _POINT_ORDER)
 
 
 _RAY_ROWS = ("ray_o and ray_d must have the same number of rows (one ray origin per ray direction). "
@@ -277,11 +398,15 @@ class MeshIndex:
 
         with pcu.MeshIndex(v, f) as mesh:
             d, fi, bc = mesh.closest_points(p)          # same rows as pcu.closest_points_on_mesh(p, v, f)
+        with pcu.MeshIndex(v, f, winding_numbers=True) as mesh:
+            w = mesh.winding_number(p)                  # same rows as pcu.triangle_soup_fast_winding_number(v, f, p)
+            s, fi, bc = mesh.signed_distance(p)         # same rows as pcu.signed_distance_to_mesh(p, v, f)
 
     `v`: (#v, 3) float32 / float64, `f`: (#f, 3) integer faces; numpy or CUDA/HIP torch tensors (copied; the caller's arrays can go away).
-    Queries must have the mesh's dtype. The index lives on one GPU; call close() (or use `with`) to free it."""
+    Queries must have the mesh's dtype. `winding_numbers=True` also builds what winding_number() and signed_distance() need (about 17 more
+    scalars per face). The index lives on one GPU; call close() (or use `with`) to free it."""
 
-    def __init__(self, v, f):
+    def __init__(self, v, f, winding_numbers=False):
         from . import _lib, _Dev, _fn, _is_torch
         dv, nv, nf = _check_mesh(v, f)
         if not (_is_torch(v) or _is_torch(f)):
@@ -291,8 +416,10 @@ class MeshIndex:
         self._suffix, self._dtype_name, self._device = d.suffix, dv, d.device
         self._face_like = ff[:0]                    # carries f's dtype (and kind of array) for the result
         self._h = None
+        self._winding = bool(winding_numbers)
         h = ctypes.c_void_p()
-        rc = _fn("mesh_index_create", d.suffix)(d.ctx, d.pa, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)], d.flags, d.stream, ctypes.byref(h))
+        rc = _fn("mesh_index_create", d.suffix)(d.ctx, d.pa, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)],
+                                                d.flags | (_lib.MESH_MOMENTS if self._winding else 0), d.stream, ctypes.byref(h))
         if rc:
             _lib.check(rc)
         self._h = h
@@ -311,6 +438,39 @@ class MeshIndex:
         dist, fi, bc = _results(d, n)
         _call("mesh_index_closest", d, self._h, d.pa, n, _Dev.ptr(dist), _Dev.ptr(fi), _Dev.ptr(bc))
         return _finish(dist, fi, bc, self._like_for(d), n, _POINT_ORDER)
+
+    def _points(self, p, what):
+        """The checks and resolved arrays of a winding_number / signed_distance call."""
+        from . import _Dev, _is_torch
+        self._check_open()
+        if not self._winding:
+            raise ValueError(f"{what} needs an index built with winding_numbers=True")
+        _check_points_dtype(p, want=self._dtype_name)
+        n = _check_points_nonzero(p)
+        if not _is_torch(p):
+            _host_point_checks(np.asarray(p))
+        d = _Dev(p, p)
+        if d.device != self._device:
+            raise ValueError("query points and mesh index live on different devices")
+        return d, n
+
+    def winding_number(self, p, *, beta=2.0):
+        """See point_cloud_utils_amd.triangle_soup_fast_winding_number; the mesh is the indexed one."""
+        from . import _Dev
+        beta = _check_beta(beta)
+        d, n = self._points(p, "winding_number")
+        w = d.empty((n,), "T")
+        _call("mesh_index_winding", d, self._h, d.pa, n, beta, _Dev.ptr(w))
+        return _scalar_rows(w, n)
+
+    def signed_distance(self, p, lower_bound=-np.inf, upper_bound=np.inf):
+        """See point_cloud_utils_amd.signed_distance_to_mesh; the mesh is the indexed one."""
+        from . import _Dev
+        lower_bound, upper_bound = _check_bounds(lower_bound, upper_bound)
+        d, n = self._points(p, "signed_distance")
+        s, fi, bc = _results(d, n)
+        _call("mesh_index_signed_distance", d, self._h, d.pa, n, lower_bound, upper_bound, 2.0, _Dev.ptr(s), _Dev.ptr(fi), _Dev.ptr(bc))
+        return _finish(s, fi, bc, _int32_like(d), n, _POINT_ORDER)
 
     def _check_open(self):
         if self._h is None:

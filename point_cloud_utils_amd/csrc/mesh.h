@@ -52,6 +52,8 @@ struct MeshIdx {                                // device pointers of one index
     T* tri = nullptr;                           // (nf, 9): the faces' corners in Morton order
     unsigned* face = nullptr;                   // (nf): face index of every sorted position
     T* box = nullptr;                           // (2P - 1, 6): lo[3], hi[3] of every node
+    T* ctr = nullptr;                           // (2P - 1, 4): centre and radius of every node's expansion (mesh_winding.h); null unless asked for
+    T* mom = nullptr;                           // (2P - 1, 30): its moments; null unless asked for
     int nf = 0, P = 0;
 };
 

@@ -1,5 +1,6 @@
-// csrc/mesh_host.h -- host orchestration of closest_points_on_mesh and ray_mesh_intersection (kernels, contracts and index layout: mesh.h). Included by pcu_hip.hip after
-// the arena, staging and radix-sort helpers.
+// csrc/mesh_host.h -- host orchestration of closest_points_on_mesh, ray_mesh_intersection (kernels, contracts and index layout: mesh.h),
+// triangle_soup_fast_winding_number and signed_distance_to_mesh (mesh_winding.h). Included by pcu_hip.hip after the arena, staging and
+// radix-sort helpers.
 #pragma once
 
 // A mesh kept on the GPU as its search index (pcu_hip_mesh_index_*): one block owned by the object, not by a call's arena.
@@ -29,15 +30,19 @@ static size_t mesh_sort_bytes(int64_t n) {
     const size_t N = (size_t)n, nwt = (N + kRsWaveTile - 1) / kRsWaveTile;
     return 2 * align_up(N * 8, 256) + 2 * align_up(N * 4, 256) + align_up(256 * nwt * 4, 256) + 1024;
 }
+// `moments`: with the centres, radii and moments of mesh_winding.h (34 more T per node, about 17 per face)
 template <typename T>
-static size_t mesh_index_bytes(int64_t nf) {
+static size_t mesh_index_bytes(int64_t nf, bool moments) {
     const size_t N = (size_t)nf, P = (size_t)mesh_leaves_pow2(nf);
-    return align_up(sizeof(MeshHead<T>), 256) + align_up(N * 9 * sizeof(T), 256) + align_up(N * 4, 256) + align_up(2 * P * 6 * sizeof(T), 256) + 1024;
+    size_t b = align_up(sizeof(MeshHead<T>), 256) + align_up(N * 9 * sizeof(T), 256) + align_up(N * 4, 256) + align_up(2 * P * 6 * sizeof(T), 256) + 1024;
+    if (moments) b += align_up(2 * P * 4 * sizeof(T), 256) + align_up(2 * P * 30 * sizeof(T), 256);
+    return b;
 }
 static int mesh_face_bytes(int f_kind) { return (f_kind == 0 || f_kind == 2) ? 4 : 8; }
 template <typename T>
-static size_t mesh_build_bytes(int64_t nv, int64_t nf, int f_kind, bool on_dev) {
+static size_t mesh_build_bytes(int64_t nv, int64_t nf, int f_kind, bool on_dev, bool moments) {
     size_t b = mesh_sort_bytes(nf) + align_up((size_t)nf * 12, 256) + 4096;
+    if (moments) b += align_up(2 * (size_t)mesh_leaves_pow2(nf) * sizeof(double), 256);      // (the nodes' areas)
     if (!on_dev) b += align_up((size_t)nv * 3 * sizeof(T), 256) + align_up((size_t)nf * 3 * mesh_face_bytes(f_kind), 256);
     return b;
 }
@@ -61,9 +66,11 @@ static int mesh_validate(int64_t nv, int64_t nf, int64_t np, int f_kind) {
     return 0;
 }
 
-// Enqueues the build on s and waits once (the validity flags). `ari` gives the buffers of the index, `ar` the temporaries.
+// Enqueues the build on s and waits once (the validity flags). `ari` gives the buffers of the index, `ar` the temporaries. `moments`: the
+// expansion data of mesh_winding.h too, bottom-up like the boxes: one launch for the leaves and one per level.
 template <typename T>
-static int mesh_build(Arena& ari, Arena& ar, hipStream_t s, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, bool on_dev, MeshIdx<T>& M) {
+static int mesh_build(Arena& ari, Arena& ar, hipStream_t s, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, bool on_dev, bool moments,
+                      MeshIdx<T>& M) {
     const T* dv = nullptr; const char* df = nullptr;
     if (stage_in(ar, v, nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(f), (size_t)nf * 3 * mesh_face_bytes(f_kind), on_dev, s, &df)) return -1;
     M.nf = (int)nf; M.P = mesh_leaves_pow2(nf);
@@ -89,19 +96,28 @@ static int mesh_build(Arena& ari, Arena& ar, hipStream_t s, const T* v, int64_t 
     hipLaunchKernelGGL(k_mesh_gather<T>, dim3(nbf), dim3(kBlock), 0, s, dv, (const int*)fidx, (const unsigned*)ia, (int)nf, M.tri, M.face);
     hipLaunchKernelGGL(k_mesh_leaves<T>, dim3((M.P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const T*)M.tri, (int)nf, M.P, (const MeshHead<T>*)M.head, M.box);
     for (int m = M.P / 2; m >= 1; m /= 2) hipLaunchKernelGGL(k_mesh_refit<T>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, M.box, m);
+    if (moments) {
+        double* area = nullptr;
+        if (aalloc(ari, &M.ctr, (size_t)M.P * 8) || aalloc(ari, &M.mom, (size_t)M.P * 60) || aalloc(ar, &area, (size_t)M.P * 2)) return -1;
+        hipLaunchKernelGGL(k_mesh_mleaves<T>, dim3((M.P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const T*)M.tri, (int)nf, M.P, (const T*)M.box, M.ctr, M.mom, area);
+        for (int m = M.P / 2; m >= 1; m /= 2)
+            hipLaunchKernelGGL(k_mesh_mrefit<T>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const T*)M.box, M.ctr, M.mom, area, m);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------- the two operators
-// Both answer, per row, with one T (distance / t), one int64 face and three T barycentrics. What differs is an Op: its inputs, how many (n,3)
-// arrays a call with host arrays stages (kRows3, inputs and barycentrics), its checks ahead of the mesh's, the kernel and the bits of the sort
-// key, the walk kernel with its parameters and the message of each bit of the flag word.
+// ---------------------------------------------------------------------------------------------------- the operators
+// All answer, per row, with one T (distance / t / w / s) and, unless kFaces is false, one int64 face and three T barycentrics. What differs is
+// an Op: its inputs, how many (n,3) arrays a call with host arrays stages (kRows3, inputs and barycentrics), whether it needs the moments of
+// mesh_winding.h (kMoments), its checks ahead of the mesh's, the kernel and the bits of the sort key, the walk kernel with its parameters and
+// the message of each bit of the flag word.
 template <typename T>
 struct MeshPointsOp {                           // closest_points_on_mesh (src/closest_point_on_mesh.cpp:25-50)
     const T* p;
     using Params = MeshQuery<T>;
     static constexpr int kRows3 = 2, kKeyBits = 30;
+    static constexpr bool kMoments = false, kFaces = true;
     int validate(int64_t) const { return 0; }
     int stage(Arena& ar, hipStream_t s, int64_t n, bool on_dev) { return stage_in(ar, p, n, on_dev, s, &p); }
     void keys(hipStream_t s, int64_t n, const MeshHead<T>* h, unsigned long long* k, int* d_bad) const {
@@ -118,6 +134,7 @@ struct MeshRaysOp {                             // ray_mesh_intersection (src/ra
     const T* o; int64_t o_rows; const T* d; double ray_near, ray_far;
     using Params = MeshRays<T>;
     static constexpr int kRows3 = 3, kKeyBits = kMeshRayKeyBits;
+    static constexpr bool kMoments = false, kFaces = true;
     int validate(int64_t n) const {
         if (n < 0) return fail(PCU_HIP_ERR_INVALID, "negative number of rays");
         if (n > kMeshMaxRows) return mesh_row_limit();
@@ -140,6 +157,37 @@ struct MeshRaysOp {                             // ray_mesh_intersection (src/ra
         return fail(PCU_HIP_ERR_INVALID, "%s must not contain NaN or infinite coordinates", (bad & kMeshBadOrigin) ? "ray_o" : "ray_d");
     }
 };
+static int mesh_beta_check(double beta) {
+    return beta > 0.0 ? 0 : fail(PCU_HIP_ERR_INVALID, "beta must be greater than 0 (finite, or +inf for the plain sum over all faces)");
+}
+template <typename T>
+struct MeshWindingOp : MeshPointsOp<T> {        // triangle_soup_fast_winding_number (src/fast_winding_numbers.cpp:20-34): one T per row, no face
+    double beta;
+    using Params = MeshSigned<T>;
+    static constexpr int kRows3 = 1;
+    static constexpr bool kMoments = true, kFaces = false;
+    int validate(int64_t) const { return mesh_beta_check(beta); }
+    void walk(hipStream_t s, MeshSigned<T> a, T* val, int64_t n) const {
+        a.p = this->p; a.np = (int)n; a.beta = (T)beta; a.out_val = val;
+        hipLaunchKernelGGL(k_mesh_winding<T>, dim3((unsigned)((n + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0, s, a);
+    }
+};
+template <typename T>
+struct MeshSdfOp : MeshPointsOp<T> {            // signed_distance_to_mesh (src/signed_distance.cpp:22-56)
+    double lower, upper, beta;
+    using Params = MeshSigned<T>;
+    static constexpr bool kMoments = true;
+    int validate(int64_t) const {
+        if (lower != lower || upper != upper) return fail(PCU_HIP_ERR_INVALID, "lower_bound and upper_bound must not be NaN");
+        if (lower > upper) return fail(PCU_HIP_ERR_INVALID, "lower_bound must not be greater than upper_bound");
+        return mesh_beta_check(beta);
+    }
+    void walk(hipStream_t s, MeshSigned<T> a, T* val, int64_t n) const {
+        a.p = this->p; a.np = (int)n; a.beta = (T)beta; a.out_val = val;
+        a.lower = (T)(float)lower; a.upper = (T)(float)upper;           // (the reference declares the bounds float)
+        hipLaunchKernelGGL(k_mesh_sdf<T>, dim3((unsigned)((n + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0, s, a);
+    }
+};
 
 // Enqueues the rows of one operator and waits for them. Events 1 / 2 of the context bracket the query phase.
 template <typename T, typename Op>
@@ -151,7 +199,7 @@ static int mesh_run(Arena& ar, hipStream_t s, const MeshIdx<T>& M, Op op, int64_
     unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
     if (aalloc(ar, &d_bad, 1) || aalloc(ar, &ka, (size_t)n) || aalloc(ar, &kb, (size_t)n) || aalloc(ar, &ia, (size_t)n) || aalloc(ar, &ib, (size_t)n)) return -1;
     T *d_val = out_val, *d_bc = out_bc; long long* d_fi = reinterpret_cast<long long*>(out_fi);
-    if (!on_dev && (aalloc(ar, &d_val, (size_t)n) || aalloc(ar, &d_fi, (size_t)n) || aalloc(ar, &d_bc, (size_t)n * 3))) return -1;
+    if (!on_dev && (aalloc(ar, &d_val, (size_t)n) || (Op::kFaces && (aalloc(ar, &d_fi, (size_t)n) || aalloc(ar, &d_bc, (size_t)n * 3))))) return -1;
     HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
     op.keys(s, n, M.head, ka, d_bad);
     if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)n, Op::kKeyBits)) return -1;
@@ -165,8 +213,10 @@ static int mesh_run(Arena& ar, hipStream_t s, const MeshIdx<T>& M, Op op, int64_
     HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
     if (!on_dev) {
         HIP_TRY(hipMemcpyAsync(out_val, d_val, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)n * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+        if (Op::kFaces) {
+            HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)n * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+        }
     }
     HIP_WAIT(s);
     return bad ? Op::message(bad) : 0;
@@ -189,6 +239,8 @@ static int mesh_call(pcu_hip_ctx* c, const MeshGiven<T>* mesh, const pcu_hip_mes
     if (!mesh) {
         if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the mesh index was built for the other scalar type");
         if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the mesh index lives on another device than the context");
+        if (Op::kMoments && !mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)).mom)
+            return fail(PCU_HIP_ERR_INVALID, "the mesh index was created without PCU_HIP_MESH_MOMENTS");
     }
     if (int rc = op.validate(n)) return rc;
     if (mesh) { if (int rc = mesh_validate(mesh->nv, mesh->nf, n, mesh->f_kind)) return rc; }
@@ -197,13 +249,13 @@ static int mesh_call(pcu_hip_ctx* c, const MeshGiven<T>* mesh, const pcu_hip_mes
     hipStream_t s = pick_stream(c, flags, stream);
     c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
     size_t bytes = mesh_run_bytes<T>(n, Op::kRows3, on_dev);
-    if (mesh) bytes += mesh_index_bytes<T>(mesh->nf) + mesh_build_bytes<T>(mesh->nv, mesh->nf, mesh->f_kind, on_dev);
+    if (mesh) bytes += mesh_index_bytes<T>(mesh->nf, Op::kMoments) + mesh_build_bytes<T>(mesh->nv, mesh->nf, mesh->f_kind, on_dev, Op::kMoments);
     if (ctx_begin(c, bytes)) return PCU_HIP_ERR_RUNTIME;
     Arena ar{c};
     Timer tm{c, s, st};
     MeshIdx<T> built;
     int rc = 0;
-    if (mesh) { tm.mark(0); rc = mesh_build<T>(ar, ar, s, mesh->v, mesh->nv, mesh->f, mesh->nf, mesh->f_kind, on_dev, built); }
+    if (mesh) { tm.mark(0); rc = mesh_build<T>(ar, ar, s, mesh->v, mesh->nv, mesh->f, mesh->nf, mesh->f_kind, on_dev, Op::kMoments, built); }
     if (!rc) rc = mesh_run<T>(ar, s, mesh ? built : mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)), op, n, on_dev, out_val, out_fi, out_bc, tm);
     if (!rc) mesh_stats(st, tm, n, mesh != nullptr);
     return attempt_exit(c, rc);
@@ -215,17 +267,17 @@ static int mesh_index_create_impl(pcu_hip_ctx* c, const T* v, int64_t nv, const 
     if (!c || !out) return fail(PCU_HIP_ERR_INVALID, "null context / output");
     *out = nullptr;
     if (int rc = mesh_validate(nv, nf, 0, f_kind)) return rc;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE, moments = flags & PCU_HIP_MESH_MOMENTS;
     hipStream_t s = pick_stream(c, flags, stream);
     pcu_hip_mesh_index* p = new pcu_hip_mesh_index();
     p->elem_size = (int)sizeof(T); p->device = c->device; p->nf = nf;
-    const size_t bytes = mesh_index_bytes<T>(nf);
+    const size_t bytes = mesh_index_bytes<T>(nf, moments);
     if (hipMalloc(&p->mem, bytes) != hipSuccess) { p->mem = nullptr; mesh_index_free(p); return fail(PCU_HIP_ERR_RUNTIME, "out of device memory for the mesh index"); }
-    if (ctx_begin(c, mesh_build_bytes<T>(nv, nf, f_kind, on_dev))) { mesh_index_free(p); return PCU_HIP_ERR_RUNTIME; }
+    if (ctx_begin(c, mesh_build_bytes<T>(nv, nf, f_kind, on_dev, moments))) { mesh_index_free(p); return PCU_HIP_ERR_RUNTIME; }
     ArenaState blk;                                 // a bump allocator over the index's own block
     blk.base = static_cast<char*>(p->mem); blk.cap = bytes;
     Arena ari{&blk}, ar{c};
-    int rc = mesh_build<T>(ari, ar, s, v, nv, f, nf, f_kind, on_dev, mesh_idx<T>(p));
+    int rc = mesh_build<T>(ari, ar, s, v, nv, f, nf, f_kind, on_dev, moments, mesh_idx<T>(p));
     if (!rc) rc = wait_stream(s);                   // (the temporaries go back to the context with this call)
     rc = attempt_exit(c, index_block_exit(blk, rc, "mesh index"));
     if (rc) { (void)hipStreamSynchronize(s); mesh_index_free(p); return rc; }

@@ -37,6 +37,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "sinkhorn.h"
 #include "poisson.h"
 #include "mesh.h"
+#include "mesh_winding.h"
 
 using namespace pcu;
 
@@ -2958,6 +2959,27 @@ int pcu_hip_mesh_index_rays_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, 
     return abi_rc(mesh_call<T>(c, nullptr, ix, MeshRaysOp<T>{ray_o, o_rows, ray_d, ray_near, ray_far}, n, out_t, out_fi, out_bc, flags, stream, st)); }
 PCU_MESH_RAYS(f32, float) PCU_MESH_RAYS(f64, double)
 #undef PCU_MESH_RAYS
+// triangle_soup_fast_winding_number and signed_distance_to_mesh (mesh_winding.h, mesh_host.h)
+#define PCU_MESH_WIND(SUF, T)                                                                                                                         \
+int pcu_hip_triangle_soup_fast_winding_number_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* p,       \
+                                                    int64_t np, double beta, T* out_w, unsigned flags, void* stream, pcu_hip_stats* st) {            \
+    CallGuard dg(c); const MeshGiven<T> m{v, nv, f, nf, f_kind};                                                                                     \
+    return abi_rc(mesh_call<T>(c, &m, nullptr, MeshWindingOp<T>{{p}, beta}, np, out_w, nullptr, nullptr, flags, stream, st)); }                      \
+int pcu_hip_signed_distance_to_mesh_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* p, int64_t np,     \
+                                          double lower, double upper, double beta, T* out_s, int64_t* out_fi, T* out_bc, unsigned flags,             \
+                                          void* stream, pcu_hip_stats* st) {                                                                         \
+    CallGuard dg(c); const MeshGiven<T> m{v, nv, f, nf, f_kind};                                                                                     \
+    return abi_rc(mesh_call<T>(c, &m, nullptr, MeshSdfOp<T>{{p}, lower, upper, beta}, np, out_s, out_fi, out_bc, flags, stream, st)); }              \
+int pcu_hip_mesh_index_winding_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* p, int64_t np, double beta, T* out_w, unsigned flags,    \
+                                     void* stream, pcu_hip_stats* st) {                                                                              \
+    CallGuard dg(c);                                                                                                                                 \
+    return abi_rc(mesh_call<T>(c, nullptr, ix, MeshWindingOp<T>{{p}, beta}, np, out_w, nullptr, nullptr, flags, stream, st)); }                      \
+int pcu_hip_mesh_index_signed_distance_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* p, int64_t np, double lower, double upper,       \
+                                             double beta, T* out_s, int64_t* out_fi, T* out_bc, unsigned flags, void* stream, pcu_hip_stats* st) {  \
+    CallGuard dg(c);                                                                                                                                 \
+    return abi_rc(mesh_call<T>(c, nullptr, ix, MeshSdfOp<T>{{p}, lower, upper, beta}, np, out_s, out_fi, out_bc, flags, stream, st)); }
+PCU_MESH_WIND(f32, float) PCU_MESH_WIND(f64, double)
+#undef PCU_MESH_WIND
 int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }
 void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) {
     if (!ix) return;
