@@ -395,345 +395,7 @@ static void ctx_end(pcu_hip_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------------ grid index
-template <typename T>
-struct GridIndex {
-    GridParams<T>* gp = nullptr;
-    unsigned* cell_start = nullptr;       // counts, scanned in place
-    Pt4<T>* sorted = nullptr;
-    unsigned* cell_of = nullptr; unsigned* rank = nullptr; unsigned* block_sums = nullptr;
-    T* bbox_partial = nullptr;
-    int n = 0, max_cells = 0, scan_blocks = 0;
-    // bucketed build (grid.h): cells per bucket = 1 << shift; nb_max = host bound on the number of buckets
-    bool bucketed = false; int shift = 0, nb_max = 0, n_zero = 0;
-    double h_want = 0.0;                  // > 0: cells at least this large (fixed-radius searches)
-    Pt4<T>* tmp = nullptr; unsigned *bucket_total = nullptr, *bucket_start = nullptr, *block_base = nullptr, *large_list = nullptr, *n_large = nullptr;
-    bool one_pass = false;                // build with k_bucket_onepass (tmp holds nb_max slots of kLargeBucket records); cleared after an overflow
-    T* xpartial = nullptr;                // one-pass build, second form (grid2.h): the scatter blocks' bbox partials
-    bool lean = false;                    // the Pt4 records of `sorted` are not written (grid2.h: fused k = 1 calls read the coordinate + row-id streams only);
-                                          // make_pt4() fills them in when some other kernel needs them
-    const T* src = nullptr; double occ_built = 0.0;       // what the index was built from (rebuild after an overflow)
-    bool shared_grid = false;             // asked for: this cloud and its partner of a two-sided call are laid over ONE grid (grid2.h: Build2Side::spts1); allocated for
-                                          // the larger cloud's plan. Cleared by a build that did not take the second-form one-pass path
-};
-
-static int max_cells_for(int64_t n, double occ) {
-    double c = (double)n / (occ > 0 ? occ : 1.0) * 1.25 + 64.0;
-    if (c > 64.0 * 1024 * 1024) c = 64.0 * 1024 * 1024;
-    return (int)c;
-}
-// Bucketed build: applicable when the cells split into <= kBkMaxBuckets buckets of <= 4096 cells (~kBucketPts = 4096 expected points
-// each) and the (block, bucket) reservation table stays small; otherwise (tiny or huge clouds, very coarse grids) the atomic build.
-// Workspace of the one-pass variant: every bucket owns a fixed slot of kLargeBucket = 8192 records in `tmp`, i.e. max(n, buckets x 8192)
-// records -- about 4x the cloud at 1M points (67 MB instead of 16), bounded by kBkMaxBuckets x 8192 records (2 GiB for float64) beyond
-// which it grows with n like everything else; index_bytes() counts exactly what index_alloc() takes.
-static bool bucket_plan(int64_t n, double occ, int* shift, int* nb_max) {
-    static const bool off = [] { const char* e = getenv("PCU_HIP_INDEX"); return e && strcmp(e, "atomic") == 0; }();
-    static const int64_t n_min = getenv("PCU_HIP_BUCKET_MIN") ? atoll(getenv("PCU_HIP_BUCKET_MIN")) : 64;         // below: the atomic build (round 4: 32768; see wave_only_below)
-    if (off || n < n_min || occ > 64.0) return false;
-    const int mc = max_cells_for(n, occ);
-    int sh = 5;
-    while (sh < 12 && (double)(2 << sh) * occ <= (double)kBucketPts) ++sh;             // largest bucket with <= ~kBucketPts expected points
-    while (sh < 12 && ((mc >> sh) + 1) > kBkMaxBuckets) ++sh;
-    const int nb = (mc >> sh) + 1;
-    if (nb > kBkMaxBuckets) return false;
-    if ((double)(1 << sh) * occ > 0.5 * (double)kLargeBucket) return false;
-    const int64_t blocks = (n + kBkBlockPts - 1) / kBkBlockPts;
-    if (blocks * (int64_t)nb > 32ll * 1024 * 1024) return false;      // (block, bucket) reservation table: at most 128 MB
-    *shift = sh; *nb_max = nb;
-    return true;
-}
-template <typename T>
-static size_t index_bytes(int64_t n, double occ) {
-    int mc = max_cells_for(n, occ);
-    size_t b = align_up(sizeof(GridParams<T>), 256) + align_up((size_t)(mc + 1 + kBkMaxBuckets + 8 + 64) * 4, 256) + align_up(sorted_records_bytes((size_t)n, sizeof(Pt4<T>), sizeof(T)), 256) +
-               2 * align_up((size_t)n * 4, 256) + align_up((size_t)(mc / kScanChunk + 2) * 4, 256) + align_up(kBboxBlocks * kBboxStride * sizeof(T), 256);
-    int sh = 0, nb = 0;
-    if (bucket_plan(n, occ, &sh, &nb))
-        b += align_up(std::max((size_t)n, (size_t)nb * kLargeBucket) * sizeof(Pt4<T>), 256) + 2 * align_up((size_t)(nb + 1) * 4, 256) +
-             align_up((size_t)((n + kBkBlockPts - 1) / kBkBlockPts) * nb * 4, 256) +
-             align_up((size_t)((n + 2047) / 2048) * kXPartStride * sizeof(T), 256);
-    return b;
-}
-template <typename T>
-static int index_alloc(Arena& a, GridIndex<T>& g, int64_t n, double occ, bool allow_bucketed = true, bool one_pass = false, int64_t n_plan = 0) {
-    // (n_plan: the cell / bucket plan of a larger cloud -- the partner this cloud shares its grid with, see GridIndex::shared_grid)
-    const int64_t np = n_plan > n ? n_plan : n;
-    g.n = (int)n; g.max_cells = max_cells_for(np, occ); g.scan_blocks = g.max_cells / kScanChunk + 1;
-    g.bucketed = allow_bucketed && bucket_plan(np, occ, &g.shift, &g.nb_max);
-    if (aalloc(a, &g.gp, 1)) return -1;
-    // (cell_start sits 256 bytes INTO its block: the k = 1 / k > 1 lane kernels read the row table of a query in the first cell of the first row
-    // from one word BEFORE cell_start (search.h: "uniform four-word tables"; the word is never used, but its address must be mapped -- also when
-    // the block is an overflow hipMalloc of its own))
-    if (aalloc(a, &g.cell_start, (size_t)g.max_cells + 1 + kBkMaxBuckets + 8 + 64)) return -1;    // + bucket totals + large-bucket count (zeroed together)
-    g.cell_start += 64;
-    if (a.alloc((void**)&g.sorted, sorted_records_bytes((size_t)n, sizeof(Pt4<T>), sizeof(T)))) return -1;        // + the +inf sentinel records + the coordinates-only copy (pcu_types.h: xyz_of)
-    if (aalloc(a, &g.cell_of, (size_t)n)) return -1;
-    if (aalloc(a, &g.rank, (size_t)n)) return -1;
-    if (aalloc(a, &g.block_sums, (size_t)g.scan_blocks + 1)) return -1;
-    if (aalloc(a, &g.bbox_partial, (size_t)kBboxBlocks * kBboxStride)) return -1;
-    g.n_zero = g.max_cells + 1;
-    if (g.bucketed) {
-        g.bucket_total = g.cell_start + g.max_cells + 1; g.n_large = g.bucket_total + g.nb_max; g.n_zero = g.max_cells + 1 + g.nb_max + 1;
-        g.one_pass = one_pass;
-        if (aalloc(a, &g.tmp, one_pass ? std::max((size_t)n, (size_t)g.nb_max * kLargeBucket) : (size_t)n)) return -1;
-        if (aalloc(a, &g.bucket_start, (size_t)g.nb_max + 1) || aalloc(a, &g.large_list, (size_t)g.nb_max + 1)) return -1;
-        if (aalloc(a, &g.block_base, (size_t)((n + kBkBlockPts - 1) / kBkBlockPts) * g.nb_max)) return -1;
-        if (one_pass && aalloc(a, &g.xpartial, (size_t)((n + 2047) / 2048) * kXPartStride)) return -1;        // (one partial per scatter block: 2048 points at least, grid2.h)
-    }
-    return 0;
-}
-// Placement of the records of over-full buckets (grid.h): one launch for up to two indexes built back to back.
-template <typename T>
-static LargeJob<T> large_job(const GridIndex<T>& g) { return LargeJob<T>{g.gp, g.bucket_start, g.large_list, g.n_large, g.tmp, g.rank, g.cell_start, g.sorted, g.n}; }
-template <typename T>
-static void index_large_pass(const GridIndex<T>& a, const GridIndex<T>* b, hipStream_t s) {
-    const bool ua = a.bucketed, ub = b && b->bucketed;
-    if (!ua && !ub) return;
-    const LargeJob<T> ja = large_job(ua ? a : *b), jb = large_job(ua && ub ? *b : (ua ? a : *b));
-    hipLaunchKernelGGL(k_bucket_large<T>, dim3(4 * kBboxBlocks), dim3(kBlock), 0, s, ja, jb, (ua && ub) ? 2 : 1);        // (grid-strided; 256 blocks left the chip three quarters empty: 111 us on a Gaussian cloud)
-    // every record is placed now: searches may use the index (GridParams::has_large)
-    if (ua) (void)hipMemsetAsync(reinterpret_cast<char*>(a.gp) + offsetof(GridParams<T>, has_large), 0, sizeof(int), s);
-    if (ub) (void)hipMemsetAsync(reinterpret_cast<char*>(b->gp) + offsetof(GridParams<T>, has_large), 0, sizeof(int), s);
-}
-// Enqueue the build of one or two indexes on `s`: every pass is ONE launch serving both clouds (grid.h: blocks [0, nb0)
-// work on the first, the rest on the second). No memset, no host synchronisation. zero2: a small region (the call's
-// result block) zeroed on the way by the first launch.
-template <typename T>
-static BucketSide<T> bucket_side(const GridIndex<T>& g, const T* pts) {
-    return BucketSide<T>{pts, g.n, g.gp, g.shift, g.nb_max, g.bucket_total, g.block_base, g.bucket_start, g.tmp, g.cell_start, g.rank,
-                         g.sorted, g.large_list, g.n_large, g.one_pass ? kLargeBucket : 0u};
-}
-template <typename T>
-static int index_build_pair(GridIndex<T>& a, const T* pa, double occa, GridIndex<T>* b, const T* pb, double occb, hipStream_t s,
-                            bool defer_large = false, void* zero2 = nullptr, int n_zero2 = 0, pcu_hip_ctx* ctx = nullptr, bool keep_layout = false) {
-    a.src = pa; a.occ_built = occa;
-    if (b) { b->src = pb; b->occ_built = occb; }
-    // one launch set serves both clouds only if they are built the same way
-    if (b && a.bucketed && b->bucketed && a.one_pass != b->one_pass) a.one_pass = b->one_pass = false;
-    const GridSide<T> g0{a.gp, a.bbox_partial, kBboxBlocks, a.n, occa, a.max_cells, a.sorted + a.n, a.h_want, pa};
-    const GridSide<T> g1 = b ? GridSide<T>{b->gp, b->bbox_partial, kBboxBlocks, b->n, occb, b->max_cells, b->sorted + b->n, b->h_want, pb} : g0;
-    // When every cloud of the call takes the one-pass bucket build, its blocks lay out the grid themselves (grid.h: k_bucket_onepass)
-    // and the k_make_grid launch is skipped. (bbox + grid layout in ONE launch, the last block folding the partials, was measured in
-    // round 2: 16.7 us against 8.1 + 4.9 us for the two launches; removed.)
-    static const bool grid_kernel = getenv("PCU_HIP_GRID_KERNEL") != nullptr;          // (always the separate k_make_grid launch)
-    const bool grid_in_onepass = !grid_kernel && a.bucketed && a.one_pass && (!b || (b->bucketed && b->one_pass));
-    // The one-pass build's second form (grid2.h): k_bucket_onepass3 -> k_bucket_sort2, while the bucket tables fit beside the scatter's stage.
-    // PCU_HIP_BUILD_V1=1 (and the diagnostics of the first form, PCU_HIP_GRID_KERNEL / PCU_HIP_PROF_BUILD) keep the round-3 chain below.
-    static const bool build_v1 = getenv("PCU_HIP_BUILD_V1") != nullptr || getenv("PCU_HIP_PROF_BUILD") != nullptr;
-    // A scatter block's (block, bucket) runs must stay long for the staged copies to pay: below ~12 records per run the padding to whole
-    // 8-record groups and the hole records the sort then reads cost more than the first form's per-record scatter (4M-point clouds:
-    // 0.40 ms against 0.285, config 3).
-    const int run_floor = 12 * std::max(a.nb_max, b ? b->nb_max : 0);
-    if (grid_in_onepass && !build_v1 && ctx && ctx->fill2 && a.xpartial && (!b || b->xpartial) && a.nb_max <= kStagedMaxBuckets && (!b || b->nb_max <= kStagedMaxBuckets) &&
-        kBkThreads * StagedPts<T>::n >= run_floor) {
-        unsigned long long* const fw = ctx->fill2 + (size_t)ctx->fill_parity * kFillWords;
-        unsigned long long* const fw_next = ctx->fill2 + (size_t)(ctx->fill_parity ^ 1) * kFillWords;
-        // points per thread of the scatter blocks: the most (longest runs per (block, bucket), fewest reservations)
-        int pts = StagedPts<T>::n;
-        {
-            const long long ntot = (long long)a.n + (b ? b->n : 0);
-            static const int n_cu = [] { hipDeviceProp_t pr; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&pr, d) == hipSuccess ? pr.multiProcessorCount : 256; }();
-            // (measured, profiles/r06_build_ab.txt: halving the blocks to get a block per CU -- or two per CU at 2 x 1M -- LOSES: every stage of a
-            // block takes as long with half the points, reservations and padding double; only launches of a handful of blocks are cut up)
-            while (pts > 2 && (ntot + (long long)kBkThreads * pts - 1) / ((long long)kBkThreads * pts) < n_cu / 16 && kBkThreads * (pts / 2) >= run_floor) pts /= 2;
-        }
-        const int bpts = kBkThreads * pts;
-        const int nbcap = (std::max(a.nb_max, b ? b->nb_max : 0) + 63) / 64 * 64;
-        auto side = [&](const GridIndex<T>& g, const T* p, double occ, int k) {
-            return Build2Side<T>{p, g.n, g.gp, g.shift, occ, g.max_cells, g.h_want, fw + (size_t)k * kStagedMaxBuckets, fw + 2 * kStagedMaxBuckets + k,
-                                 g.tmp, kLargeBucket, g.xpartial, (g.n + bpts - 1) / bpts, g.cell_start, g.sorted, g.lean ? 0 : 1, g.n_large,
-                                 k == 0 ? fw_next : nullptr, k == 0 ? kFillWords : 0, k == 0 ? (unsigned*)zero2 : nullptr, k == 0 ? n_zero2 : 0, nullptr,
-                                 p, g.n, nullptr, 0, g.n, nullptr, nullptr};
-        };
-        Build2Side<T> s0 = side(a, pa, occa, 0), s1 = b ? side(*b, pb, occb, 1) : s0;
-        // one grid for both clouds (GridIndex::shared_grid): same plan (index_alloc's n_plan), same occupancy, both at least a sample large
-        const bool shared = b && a.shared_grid && b->shared_grid && occa == occb && a.max_cells == b->max_cells && a.shift == b->shift && a.nb_max == b->nb_max &&
-                            a.h_want == b->h_want && a.n >= kPrepSamples && b->n >= kPrepSamples;
-        if (b) a.shared_grid = b->shared_grid = shared; else a.shared_grid = false;
-        if (shared) {
-            s0.spts0 = s1.spts0 = pa; s0.sn0 = s1.sn0 = a.n; s0.spts1 = s1.spts1 = pb; s0.sn1 = s1.sn1 = b->n;
-            s0.n_layout = s1.n_layout = std::max(a.n, b->n);
-        }
-        // The layout handed down from the context's previous call (grid2.h: GridGeo): two-sided fused calls only (their *_end knows how to restart a
-        // call whose layout was refused as stale). The key: everything grid_layout and the sample depend on besides the points themselves.
-        static const bool geo_off = getenv("PCU_HIP_NO_GEO_CACHE") != nullptr;
-        bool geo_arm = false;
-        if (keep_layout && b && !geo_off && ctx->geo.dev && a.n >= kPrepSamples && b->n >= kPrepSamples) {
-            pcu_hip_ctx::GeoCache& gc = ctx->geo;
-            const bool hit = gc.valid[0] && gc.valid[1] && gc.n[0] == a.n && gc.n[1] == b->n && gc.occ == occa && occa == occb && gc.h_want == a.h_want && a.h_want == b->h_want &&
-                             gc.max_cells == a.max_cells && a.max_cells == b->max_cells && gc.shared == shared && gc.n_layout == s0.n_layout && gc.tsize == (int)sizeof(T);
-            static_assert(sizeof(GridGeo<T>) <= 256, "two layouts fit the context's block");
-            GridGeo<T>* const g0 = reinterpret_cast<GridGeo<T>*>(gc.dev), *const g1 = reinterpret_cast<GridGeo<T>*>(gc.dev + 256);
-            s0.geo_out = g0; s1.geo_out = g1;
-            if (hit) { s0.geo_in = g0; s1.geo_in = g1; }
-            DEBUG_SKEW("[layout] handed down: %d (n %d %d, shared %d)\n", (int)hit, a.n, b->n, (int)shared);
-            // (valid again only when both launches are enqueued, below: a build that fails on the way leaves no claim on memory nobody wrote)
-            gc.valid[0] = gc.valid[1] = false;
-            geo_arm = occa == occb && a.h_want == b->h_want && a.max_cells == b->max_cells;
-            gc.n[0] = a.n; gc.n[1] = b->n; gc.occ = occa; gc.h_want = a.h_want; gc.max_cells = a.max_cells; gc.shared = shared; gc.n_layout = s0.n_layout; gc.tsize = (int)sizeof(T);
-        }
-        const int c0 = s0.n_xpart, c1 = b ? s1.n_xpart : 0;
-        static const bool do_prof2 = getenv("PCU_HIP_PROF_BUILD2") != nullptr;
-        static long long* prof2 = nullptr;
-        if (do_prof2) { if (!prof2) HIP_TRY(hipMalloc((void**)&prof2, 16 * sizeof(long long))); HIP_TRY(hipMemsetAsync(prof2, 0, 16 * sizeof(long long), s)); }
-        s0.prof = s1.prof = do_prof2 ? prof2 : nullptr;
-        static std::atomic<unsigned long long> attr_set2[2];
-        if (attr_unset_here(attr_set2[sizeof(T) == 4 ? 0 : 1])) {
-            if (StagedPts<T>::n >= 8) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bucket_onepass3<T, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)onepass3_lds_bytes<T>(8)));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bucket_onepass3<T, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)onepass3_lds_bytes<T>(4)));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bucket_onepass3<T, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)onepass3_lds_bytes<T>(2)));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bucket_sort2<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)bucket_sort_lds_bytes<T>(kBkMaxCellsPerBucket)));
-        }
-        Build2Args<T> sa; sa.a[0] = s0; sa.a[1] = s1;
-        const size_t lds1 = onepass3_lds_bytes<T>(pts, nbcap);
-        if (pts == 8) hipLaunchKernelGGL((k_bucket_onepass3<T, 8>), dim3(c0 + c1), dim3(kBkThreads), lds1, s, sa, c0, nbcap);
-        else if (pts == 4) hipLaunchKernelGGL((k_bucket_onepass3<T, 4>), dim3(c0 + c1), dim3(kBkThreads), lds1, s, sa, c0, nbcap);
-        else hipLaunchKernelGGL((k_bucket_onepass3<T, 2>), dim3(c0 + c1), dim3(kBkThreads), lds1, s, sa, c0, nbcap);
-        if (do_prof2) {
-            long long h[16]; HIP_TRY(hipMemcpyAsync(h, prof2, sizeof h, hipMemcpyDeviceToHost, s)); HIP_WAIT(s);
-            const double nb = h[15] > 0 ? (double)h[15] * 100.0 : 100.0;
-            fprintf(stderr, "[onepass3 prof] blocks %lld | mean us per block: layout %.2f  points in %.2f  keys+ranks %.2f  scan+reservations %.2f  staging %.2f  run copies %.2f  drain %.2f\n",
-                    h[15], h[0] / nb, h[1] / nb, h[2] / nb, h[3] / nb, h[4] / nb, h[5] / nb, h[6] / nb);
-        }
-        const int t0 = a.nb_max, t1 = b ? b->nb_max : 0;
-        const int cnt_cap = 1 << std::max(a.shift, b ? b->shift : 0);
-        if (do_prof2) { HIP_TRY(hipMemsetAsync(prof2, 0, 16 * sizeof(long long), s)); }
-        hipLaunchKernelGGL(k_bucket_sort2<T>, dim3(t0 + t1 + (b ? 2 : 1)), dim3(kSortThreads), bucket_sort_lds_bytes<T>(cnt_cap), s, sa, t0, t1, cnt_cap, b ? 2 : 1);
-        ctx->fill_parity ^= 1;        // only now: both launches are enqueued, so the other set WILL be zeroed for the next build (an error return above leaves the parity alone)
-        if (do_prof2) {
-            long long h[16]; HIP_TRY(hipMemcpyAsync(h, prof2, sizeof h, hipMemcpyDeviceToHost, s)); HIP_WAIT(s);
-            const double nb = h[7] > 0 ? (double)h[7] * 100.0 : 100.0;
-            fprintf(stderr, "[sort2 prof] blocks %lld | mean us per block: head %.2f  load+rank %.2f  scan %.2f  place %.2f  copies %.2f  drain %.2f\n",
-                    h[7], h[0] / nb, h[1] / nb, h[2] / nb, h[3] / nb, h[4] / nb, h[5] / nb);
-        }
-        HIP_TRY(hipGetLastError());
-        if (geo_arm) ctx->geo.valid[0] = ctx->geo.valid[1] = true;       // (the sort launch's first blocks will have written this call's layout before the next call's kernels run)
-        return 0;
-    }
-    a.lean = false; if (b) b->lean = false;            // (every other build writes the Pt4 records)
-    a.shared_grid = false; if (b) b->shared_grid = false;      // (... and lays every cloud over its own grid)
-    {
-        const BboxSide<T> s0{pa, a.n, a.bbox_partial, a.cell_start, a.n_zero, (unsigned*)zero2, n_zero2, a.gp};
-        const BboxSide<T> s1 = b ? BboxSide<T>{pb, b->n, b->bbox_partial, b->cell_start, b->n_zero, nullptr, 0, b->gp} : s0;
-        hipLaunchKernelGGL(k_bbox_partial<T>, dim3(b ? 2 * kBboxBlocks : kBboxBlocks), dim3(kBlock), 0, s, s0, s1, kBboxBlocks);
-        if (!grid_in_onepass) hipLaunchKernelGGL(k_make_grid<T>, dim3(b ? 2 : 1), dim3(kBlock), 0, s, g0, g1);
-    }
-    // bucketed sides share their launches; a side too small / too coarse for buckets takes the atomic passes
-    const GridIndex<T>* bs[2]; const T* bp[2]; int nbs = 0;
-    if (a.bucketed) { bs[nbs] = &a; bp[nbs] = pa; ++nbs; }
-    if (b && b->bucketed) { bs[nbs] = b; bp[nbs] = pb; ++nbs; }
-    if (nbs) {
-        const BucketSide<T> s0 = bucket_side(*bs[0], bp[0]), s1 = nbs > 1 ? bucket_side(*bs[1], bp[1]) : s0;
-        const int c0 = (bs[0]->n + kBkBlockPts - 1) / kBkBlockPts, c1 = nbs > 1 ? (bs[1]->n + kBkBlockPts - 1) / kBkBlockPts : 0;
-        static long long* prof = nullptr;       // PCU_HIP_PROF_BUILD: stage times of k_bucket_sort, printed per build (synchronises)
-        static const bool do_prof = getenv("PCU_HIP_PROF_BUILD") != nullptr;
-        if (do_prof && !prof) HIP_TRY(hipMalloc((void**)&prof, 8 * sizeof(long long)));
-        if (do_prof) HIP_TRY(hipMemsetAsync(prof, 0, 8 * sizeof(long long), s));
-        const bool one_pass = bs[0]->one_pass;
-        if (one_pass) {
-            static long long* prof1 = nullptr;
-            if (do_prof && !prof1) HIP_TRY(hipMalloc((void**)&prof1, 8 * sizeof(long long)));
-            if (do_prof) HIP_TRY(hipMemsetAsync(prof1, 0, 8 * sizeof(long long), s));
-            // (the grid sides in the order of the bucket sides: both clouds are bucketed whenever two are built this way)
-            hipLaunchKernelGGL(k_bucket_onepass<T>, dim3(c0 + c1), dim3(kBkThreads), 0, s, s0, s1, c0, do_prof ? prof1 : nullptr,
-                               bs[0] == &a ? g0 : g1, nbs > 1 ? g1 : (bs[0] == &a ? g0 : g1));
-            if (do_prof) {
-                long long h[8]; HIP_TRY(hipMemcpyAsync(h, prof1, sizeof h, hipMemcpyDeviceToHost, s)); HIP_WAIT(s);
-                const double nb = h[7] > 0 ? (double)h[7] : 1.0;
-                fprintf(stderr, "[onepass prof] blocks %lld | mean us per block: zero+loads %.2f  keys+LDS ranks %.2f  slot reservations %.2f  stores %.2f\n", h[7],
-                        h[0] / nb / 100.0, h[1] / nb / 100.0, h[2] / nb / 100.0, h[3] / nb / 100.0);
-            }
-        }
-        else {
-            hipLaunchKernelGGL(k_bucket_count<T>, dim3(c0 + c1), dim3(kBkThreads), 0, s, s0, s1, c0);
-            hipLaunchKernelGGL(k_bucket_scatter<T>, dim3(c0 + c1), dim3(kBkThreads), 0, s, s0, s1, c0);
-        }
-        const int t0 = bs[0]->nb_max, t1 = nbs > 1 ? bs[1]->nb_max : 0;
-        const int cnt_cap = 1 << std::max(bs[0]->shift, nbs > 1 ? bs[1]->shift : 0);
-        const size_t lds = bucket_sort_lds_bytes<T>(cnt_cap);
-        static std::atomic<unsigned long long> attr_set[2];
-        if (attr_unset_here(attr_set[sizeof(T) == 4 ? 0 : 1]))
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bucket_sort<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)bucket_sort_lds_bytes<T>(kBkMaxCellsPerBucket)));
-        // One launch for both clouds, like the other passes (1024 threads / 4096-point buckets: all blocks of both clouds are
-        // resident at once; measured 0.174 vs 0.186 ms per step against one launch per cloud).
-        hipLaunchKernelGGL(k_bucket_sort<T>, dim3(t0 + t1), dim3(kSortThreads), lds, s, s0, s1, t0, do_prof ? prof : nullptr, cnt_cap);
-        if (do_prof) {
-            long long h[8]; HIP_TRY(hipMemcpyAsync(h, prof, sizeof h, hipMemcpyDeviceToHost, s)); HIP_WAIT(s);
-            const double nb = h[7] > 0 ? (double)h[7] : 1.0;
-            fprintf(stderr, "[bucket_sort prof] blocks %lld | mean us per block: head %.2f  zero+sync %.2f  load+rank %.2f  scan %.2f  place %.2f\n", h[7],
-                    h[0] / nb / 100.0, h[1] / nb / 100.0, h[2] / nb / 100.0, h[3] / nb / 100.0, h[4] / nb / 100.0);
-        }
-        if (!defer_large && !one_pass) index_large_pass<T>(a, b, s);        // (a one-pass build has no over-full buckets: it overflows instead)
-    }
-    for (int side = 0; side < (b ? 2 : 1); ++side) {
-        GridIndex<T>& g = side ? *b : a;
-        if (g.bucketed) continue;
-        const T* d_pts = side ? pb : pa;
-        const int n = g.n, nb = (n + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(k_count<T>, dim3(nb), dim3(kBlock), 0, s, d_pts, n, g.gp, g.cell_of, g.rank, g.cell_start);
-        hipLaunchKernelGGL(k_scan_reduce<T>, dim3(g.scan_blocks), dim3(kBlock), 0, s, g.cell_start, g.gp, g.block_sums);
-        hipLaunchKernelGGL(k_scan_apply<T>, dim3(g.scan_blocks), dim3(kBlock), 0, s, g.cell_start, g.gp, g.block_sums, (unsigned)n);
-        hipLaunchKernelGGL(k_scatter<T>, dim3(nb), dim3(kBlock), 0, s, d_pts, n, g.cell_of, g.rank, g.cell_start, g.sorted);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-template <typename T>
-static int index_build(GridIndex<T>& g, const T* d_pts, double occ, hipStream_t s, bool defer_large = false, void* zero2 = nullptr, int n_zero2 = 0,
-                       pcu_hip_ctx* ctx = nullptr) {
-    return index_build_pair<T>(g, d_pts, occ, nullptr, nullptr, 0.0, s, defer_large, zero2, n_zero2, ctx);
-}
-
-// Refitted grids for unbalanced clouds (grid.h): core range of the cloud by three zooming histogram rounds, then
-// uniform grids of a chosen cell count over that range. Everything is enqueued on `s` (no host sync).
-template <typename T>
-static int core_range_enqueue(Arena& ar, const GridIndex<T>& base, const T* d_pts, hipStream_t s, QuantState<T>** out_qs) {
-    QuantState<T>* qs = nullptr; unsigned *partial = nullptr, *hist = nullptr;
-    if (aalloc(ar, &qs, 1) || aalloc(ar, &partial, (size_t)kHistBlocks * 3 * (kHistBins + 2)) || aalloc(ar, &hist, 3 * (kHistBins + 2))) return -1;
-    hipLaunchKernelGGL(k_quant_init<T>, dim3(1), dim3(64), 0, s, base.gp, qs);
-    for (int r = 0; r < 3; ++r) {
-        hipLaunchKernelGGL(k_hist_axis<T>, dim3(kHistBlocks), dim3(kBlock), 0, s, d_pts, base.n, qs, partial);
-        hipLaunchKernelGGL(k_hist_merge, dim3((3 * (kHistBins + 2) + kBlock - 1) / kBlock), dim3(kBlock), 0, s, partial, kHistBlocks, hist);
-        hipLaunchKernelGGL(k_quant_zoom<T>, dim3(3), dim3(64), 0, s, qs, hist, base.n);
-    }
-    HIP_TRY(hipGetLastError());
-    *out_qs = qs;
-    return 0;
-}
-template <typename T>
-static int index_build_refit(Arena& ar, GridIndex<T>& g, const GridIndex<T>& base, const T* d_pts, const QuantState<T>* qs,
-                             double target_cells, hipStream_t s, bool closed = false, const double* target_dev = nullptr) {
-    // closed: sub-box level (only the points inside the box are indexed); target_dev: cell count decided on the device
-    const int n = base.n;
-    if (target_cells < 1.0) target_cells = 1.0;
-    if (index_alloc(ar, g, n, (double)n / target_cells, false, /*allow_bucketed=*/false)) return -1;
-    const int nb = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_make_grid_refit<T>, dim3(1), dim3(64), 0, s, g.gp, base.gp, qs, target_cells, g.max_cells, g.sorted + n, n,
-                       closed ? 1 : 0, target_dev);
-    HIP_TRY(hipMemsetAsync(g.cell_start, 0, ((size_t)g.max_cells + 1) * 4, s));
-    hipLaunchKernelGGL(k_count<T>, dim3(nb), dim3(kBlock), 0, s, d_pts, n, g.gp, g.cell_of, g.rank, g.cell_start);
-    hipLaunchKernelGGL(k_scan_reduce<T>, dim3(g.scan_blocks), dim3(kBlock), 0, s, g.cell_start, g.gp, g.block_sums);
-    hipLaunchKernelGGL(k_scan_apply<T>, dim3(g.scan_blocks), dim3(kBlock), 0, s, g.cell_start, g.gp, g.block_sums, closed ? 0xffffffffu : (unsigned)n);
-    hipLaunchKernelGGL(k_scatter<T>, dim3(nb), dim3(kBlock), 0, s, d_pts, n, g.cell_of, g.rank, g.cell_start, g.sorted);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-// Sub-box level over the heavy cells of `parent` (cells holding more than `thresh` points): enqueue only.
-template <typename T>
-static int index_build_heavy(Arena& ar, GridIndex<T>& g, const GridIndex<T>& parent, const T* d_pts, double occ, unsigned thresh, hipStream_t s,
-                             const double** stats_dev = nullptr) {
-    // stats_dev: device pair {cell count chosen for the level, number of points in heavy cells of the parent}
-    QuantState<T>* qs = nullptr; T* pbox = nullptr; double *pcnt = nullptr, *target = nullptr;
-    if (aalloc(ar, &qs, 1) || aalloc(ar, &pbox, (size_t)kBboxBlocks * 6) || aalloc(ar, &pcnt, (size_t)kBboxBlocks * 2) || aalloc(ar, &target, 2)) return -1;
-    // (a bucketed parent keeps no per-point cell ids -- its cell_of storage is the row -> slot table -- the kernel recomputes them)
-    hipLaunchKernelGGL(k_heavy_partial<T>, dim3(kBboxBlocks), dim3(kBlock), 0, s, d_pts, parent.n, parent.gp, parent.bucketed ? nullptr : parent.cell_of,
-                       parent.cell_start, thresh, pbox, pcnt);
-    hipLaunchKernelGGL(k_heavy_finish<T>, dim3(1), dim3(64), 0, s, parent.gp, pbox, pcnt, kBboxBlocks, occ, 16.0 * 1024 * 1024, qs, target);
-    if (stats_dev) *stats_dev = target;
-    return index_build_refit(ar, g, parent, d_pts, qs, (double)parent.n / occ, s, /*closed=*/true, target);
-}
+#include "index_host.h"
 
 // ------------------------------------------------------------------------------------------------ search driver
 static double default_occupancy(int k) {
@@ -779,7 +441,7 @@ static bool shared_grid_wanted(const pcu_hip_ctx* c, int64_t nx, int64_t ny, dou
     return !off && occ_x == occ_y && std::min(nx, ny) >= kPrepSamples && std::max(nx, ny) <= 2 * std::min(nx, ny);
 }
 // whole-call index builds use the one-pass bucket scatter until a cloud of this context overflows a slot (PCU_HIP_TWO_PASS=1: never)
-static bool use_one_pass(const pcu_hip_ctx* c) { static const bool off = getenv("PCU_HIP_TWO_PASS") != nullptr; return !off && !c->two_pass; }
+static IndexFor whole_call_form(const pcu_hip_ctx* c) { static const bool off = getenv("PCU_HIP_TWO_PASS") != nullptr; return !off && !c->two_pass ? IndexFor::OnePass : IndexFor::TwoPass; }
 // The wave-per-query launch of a call finishes its stragglers itself (search.h: k_search_wave, box round -> ball round); PCU_HIP_NO_ESCALATE=1
 // leaves them to the host-driven passes of search_finish (radius 4 ... 16, then coarser grids), the pre-round-3 behaviour and still the
 // path of closed sub-box levels.
@@ -1596,7 +1258,7 @@ static int search_finish(pcu_hip_ctx* c, Arena& ar, hipStream_t s, SearchJob<T>&
         if (R >= (n_left > 4096 ? 4 : 16) && gmax > 8) {
             occ *= 512.0;
             GridIndex<T> coarse;
-            if (index_alloc(ar, coarse, ridx.n, occ, false, false)) return -1;
+            if (index_alloc(ar, coarse, ridx.n, occ, IndexFor::Atomic)) return -1;
             if (index_build(coarse, j.d_ref_pts, occ, s)) return -1;
             if (st) st->n_grid_builds++;
             ridx = coarse; R = 1;
@@ -1722,7 +1384,7 @@ static int knn_big_k(pcu_hip_ctx* c, const T* query, int64_t nq, const T* datase
         if (!on_dev) { if ((rc = aalloc(ar, &dd, (size_t)nq * k))) break; if ((rc = aalloc(ar, &di, (size_t)nq * k))) break; }
         GridIndex<T> gi;                          // only its exact bounding box is used (root of the kd-tree)
         if (pidx) gi = index_grid<T>(pidx);
-        else { if ((rc = index_alloc(ar, gi, nr, 2.0))) break; if ((rc = index_build(gi, dr, 2.0, s))) break; if (st) st->n_grid_builds = 1; }
+        else { if ((rc = index_alloc(ar, gi, nr, 2.0, IndexFor::TwoPass))) break; if ((rc = index_build(gi, dr, 2.0, s))) break; if (st) st->n_grid_builds = 1; }
         if ((rc = check_nonfinite<T>(gi.gp, kNfNaN | kNfBothInf, s))) break;
         KdBuild<T> b; int* err = nullptr; int levels = 0;
         if ((rc = kd_build_device(c, ar, s, dr, (int)nr, gi.gp, max_leaf > 0 ? max_leaf : 10, b, &err, &levels, nullptr))) break;
@@ -1817,8 +1479,8 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         // query -- 185 MB for a 12 MB result at 1M, k = 1 -- plus 37 MB of scattered row -> slot stores in the build. The scattered 4 / 8-byte
         // row stores cost 67 MB instead (profiles/r04_c2_ab.txt): config 2 0.184 -> 0.154 ms.)
         if (pidx) job.ridx = index_grid<T>(pidx);
-        else if ((rc = index_alloc(ar, job.ridx, nr, occ, true, use_one_pass(c), n_plan))) break;
-        if ((rc = index_alloc(ar, job.qidx, nq, occ_q, true, use_one_pass(c), n_plan))) break;
+        else if ((rc = index_alloc(ar, job.ridx, nr, occ, whole_call_form(c), PlanFor{n_plan}))) break;
+        if ((rc = index_alloc(ar, job.qidx, nq, occ_q, whole_call_form(c), PlanFor{n_plan}))) break;
         job.ridx.shared_grid = job.qidx.shared_grid = share;
         job.qidx.src = dq; job.qidx.occ_built = occ_q;
         if (!pidx) { job.ridx.src = dr; job.ridx.occ_built = occ; }
@@ -1836,8 +1498,9 @@ static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
             job.ridx.lean = job.qidx.lean = lean;
         }
         tm.mark(0);
-        if (pidx) { if ((rc = index_build<T>(job.qidx, dq, occ_q, s, /*defer_large=*/!c->eager_large, rb, (int)(sizeof(ResultBlock) / 4), c))) break; }
-        else if ((rc = index_build_pair<T>(job.ridx, dr, occ, &job.qidx, dq, occ_q, s, !c->eager_large, rb, (int)(sizeof(ResultBlock) / 4), c))) break;
+        BuildOpts bo; bo.defer_large = !c->eager_large; bo.zero2 = rb; bo.n_zero2 = (int)(sizeof(ResultBlock) / 4); bo.ctx = c;
+        if (pidx) { if ((rc = index_build<T>(job.qidx, dq, occ_q, s, bo))) break; }
+        else if ((rc = index_build_pair<T>(job.ridx, dr, occ, &job.qidx, dq, occ_q, s, bo))) break;
         if (st) st->n_grid_builds += pidx ? 1 : 2;
         tm.mark(1);
         const bool spec = kd_speculate_fork(c, s, job);
@@ -1923,7 +1586,7 @@ struct PendingPair {
 };
 template <typename T>
 static size_t pair_bytes(int64_t nx, int64_t ny, double occ_x, double occ_y, bool on_dev) {
-    // (index_bytes of the LARGER cloud for both: a shared grid is planned for it, index_alloc's n_plan)
+    // (index_bytes of the LARGER cloud for both: a shared grid is planned for it, index_alloc's PlanFor)
     size_t b = index_bytes<T>(std::max(nx, ny), occ_x) + index_bytes<T>(std::max(nx, ny), occ_y) + scratch_bytes<T>(nx) + scratch_bytes<T>(ny) +
                align_up((size_t)nx * sizeof(T), 256) + align_up((size_t)ny * sizeof(T), 256) +
                align_up((size_t)nx * 8, 256) + align_up((size_t)ny * 8, 256) +
@@ -1993,10 +1656,10 @@ static int pair_setup(pcu_hip_ctx* c, PendingPair<T>& pp, double occ_x, double o
     GridIndex<T> ix, iy;
     const bool share = two_sided && shared_grid_wanted(c, nx, ny, occ_x, occ_y);
     const int64_t n_plan = share ? std::max(nx, ny) : 0;
-    if (index_alloc(ar, ix, nx, occ_x, true, use_one_pass(c), n_plan) || index_alloc(ar, iy, ny, occ_y, true, use_one_pass(c), n_plan)) return -1;
+    if (index_alloc(ar, ix, nx, occ_x, whole_call_form(c), PlanFor{n_plan}) || index_alloc(ar, iy, ny, occ_y, whole_call_form(c), PlanFor{n_plan})) return -1;
     ix.shared_grid = iy.shared_grid = share;
     ix.src = P.dx; iy.src = P.dy; ix.occ_built = occ_x; iy.occ_built = occ_y;        // (the jobs below hold copies: what a rebuild after a slot overflow starts from)
-    if (ix.bucketed && iy.bucketed && ix.one_pass != iy.one_pass) ix.one_pass = iy.one_pass = false;
+    index_same_form(ix, iy);
     P.xy.qidx = ix; P.xy.ridx = iy; P.xy.d_ref_pts = P.dy;
     P.yx.qidx = iy; P.yx.ridx = ix; P.yx.d_ref_pts = P.dx;
     P.xy.occ = occ_y; P.yx.occ = occ_x;            // a direction's occupancy is its dataset's
@@ -2062,7 +1725,8 @@ static int pair_setup(pcu_hip_ctx* c, PendingPair<T>& pp, double occ_x, double o
     g_hprof.mark(1);
     // (the first build's first kernel also zeroes the call block: both directions' counters, the epilogue's ticket, the exact sums)
     // (defer_large: the placement of over-full buckets is launched only if a search reports them, see search_finish)
-    if (index_build_pair<T>(ix, P.dx, occ_x, &iy, P.dy, occ_y, s, /*defer_large=*/!c->eager_large, P.cb, (int)(sizeof(CallBlock) / 4), c, /*keep_layout=*/P.fuse != FUSE_NONE)) return -1;
+    BuildOpts bo; bo.defer_large = !c->eager_large; bo.zero2 = P.cb; bo.n_zero2 = (int)(sizeof(CallBlock) / 4); bo.ctx = c; bo.keep_layout = P.fuse != FUSE_NONE;
+    if (index_build_pair<T>(ix, P.dx, occ_x, &iy, P.dy, occ_y, s, bo)) return -1;
     P.xy.qidx.lean = P.yx.ridx.lean = ix.lean; P.xy.ridx.lean = P.yx.qidx.lean = iy.lean;      // (the build says what it wrote)
     P.xy.qidx.shared_grid = P.yx.ridx.shared_grid = ix.shared_grid; P.xy.ridx.shared_grid = P.yx.qidx.shared_grid = iy.shared_grid;
     if (P.fuse == FUSE_ARGMAX) for (int d = 0; d < (two_sided ? 2 : 1); ++d) {       // what the tail needs to resolve a winner: the direction's dataset index and query stream
@@ -2549,7 +2213,7 @@ static int normals_ball_impl(pcu_hip_ctx* c, const T* points, int64_t n, const T
         T* d_out = out_n; uint8_t* d_keep = out_keep;
         if (!on_dev) { if ((rc = aalloc(ar, &d_out, (size_t)n * 3))) break; if ((rc = aalloc(ar, &d_keep, (size_t)n))) break; }
         GridIndex<T> gi;
-        if ((rc = index_alloc(ar, gi, n, occ, false, /*allow_bucketed=*/false))) break;
+        if ((rc = index_alloc(ar, gi, n, occ, IndexFor::Atomic))) break;
         const T radius_t = (T)ball_radius;                          // RadiusResultSet<DistanceType = T>(radius, ...)
         gi.h_want = sqrt((double)radius_t) / 1.98;                  // cells of about half the true search radius: 5^3 cells per point
         if ((rc = index_build(gi, d_pts, occ, s))) break;
@@ -2677,7 +2341,7 @@ static int index_create_impl(pcu_hip_ctx* c, const T* dataset, int64_t nr, int k
         blk.base = static_cast<char*>(p->mem); blk.cap = bytes;
         Arena ar{&blk};
         GridIndex<T>& g = index_grid_mut<T>(p);
-        if ((rc = index_block_exit(blk, index_alloc(ar, g, nr, p->occ), "index"))) break;
+        if ((rc = index_block_exit(blk, index_alloc(ar, g, nr, p->occ, IndexFor::TwoPass), "index"))) break;
         if ((rc = index_build<T>(g, static_cast<const T*>(p->pts), p->occ, s))) break;
         if ((rc = check_nonfinite<T>(g.gp, kNfNaN | kNfBothInf, s))) break;
     } while (0);
@@ -2699,7 +2363,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
         const T* dp;
         if ((rc = stage_in(ar, pts, n, false, s, &dp))) break;
         GridIndex<T> gi;
-        if ((rc = index_alloc(ar, gi, n, 2.0))) break;
+        if ((rc = index_alloc(ar, gi, n, 2.0, IndexFor::TwoPass))) break;
         if ((rc = index_build(gi, dp, 2.0, s))) break;
         KdBuild<T> b; int* err = nullptr; int levels = 0, nn = 0;
         if ((rc = kd_build_device(c, ar, s, dp, (int)n, gi.gp, leaf_max > 0 ? leaf_max : 10, b, &err, &levels, &nn))) break;

@@ -102,7 +102,7 @@ static int poisson_disk_impl(pcu_hip_ctx* c, const T* pts, int64_t n, double rad
     R.seed = seed;
     do {
         if ((rc = stage_in(ar, pts, n, on_dev, s, &R.pts))) break;
-        if ((rc = index_alloc(ar, R.gi, n, kPdOccupancy, false, /*allow_bucketed=*/false))) break;
+        if ((rc = index_alloc(ar, R.gi, n, kPdOccupancy, IndexFor::Atomic))) break;
         PdArgs<T>& a = R.a;
         a.n = (int)n;
         if ((rc = aalloc(ar, &a.prio, N)) || (rc = aalloc(ar, &a.state, N)) || (rc = aalloc(ar, &a.cell, N)) || (rc = aalloc(ar, &a.slist, N)) ||
