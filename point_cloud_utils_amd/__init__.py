@@ -33,6 +33,7 @@ __all__ = ["k_nearest_neighbors", "one_sided_hausdorff_distance", "hausdorff_dis
            "pairwise_distances", "sinkhorn", "earth_movers_distance", "closest_points_on_mesh", "MeshIndex",
            "ray_mesh_intersection", "RayMeshIntersector", "interpolate_barycentric_coords",
            "triangle_soup_fast_winding_number", "signed_distance_to_mesh",
+           "mesh_face_areas", "sample_mesh_random", "sample_mesh_poisson_disk",
            "last_stats", "set_timing", "set_cell_occupancy", "device_count", "DatasetIndex", "cancel"]
 
 _last_stats = [None]      # the Stats struct of the most recent call (turned into a dict on demand)
@@ -441,3 +442,4 @@ from ._sinkhorn import pairwise_distances, sinkhorn, earth_movers_distance  # no
 from ._poisson import downsample_point_cloud_poisson_disk  # noqa: E402,F401
 from ._mesh import (closest_points_on_mesh, MeshIndex, ray_mesh_intersection, RayMeshIntersector,  # noqa: E402,F401
                     interpolate_barycentric_coords, triangle_soup_fast_winding_number, signed_distance_to_mesh)
+from ._mesh_sample import mesh_face_areas, sample_mesh_random, sample_mesh_poisson_disk  # noqa: E402,F401

@@ -38,6 +38,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "poisson.h"
 #include "mesh.h"
 #include "mesh_winding.h"
+#include "mesh_sample.h"
 
 using namespace pcu;
 
@@ -2378,6 +2379,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "voxel_host.h"
 #include "poisson_host.h"
 #include "mesh_host.h"
+#include "mesh_sample_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2644,6 +2646,23 @@ int pcu_hip_mesh_index_signed_distance_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_
     return abi_rc(mesh_call<T>(c, nullptr, ix, MeshSdfOp<T>{{p}, lower, upper, beta}, np, out_s, out_fi, out_bc, flags, stream, st)); }
 PCU_MESH_WIND(f32, float) PCU_MESH_WIND(f64, double)
 #undef PCU_MESH_WIND
+// mesh_face_areas, sample_mesh_random and sample_mesh_poisson_disk (mesh_sample.h, mesh_sample_host.h)
+#define PCU_MESH_SAMPLE(SUF, T)                                                                                                                       \
+int pcu_hip_mesh_face_areas_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, T* out_areas, unsigned flags,       \
+                                  void* stream, pcu_hip_stats* st) {                                                                                 \
+    CallGuard dg(c); return abi_rc(mesh_face_areas_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, out_areas, flags, stream, st)); }                  \
+int pcu_hip_sample_mesh_random_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, int64_t num_samples,             \
+                                     uint32_t seed, int64_t* out_fi, T* out_bc, unsigned flags, void* stream, pcu_hip_stats* st) {                   \
+    CallGuard dg(c);                                                                                                                                 \
+    return abi_rc(sample_mesh_random_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, num_samples, seed, out_fi, out_bc, flags, stream, st)); }        \
+int pcu_hip_sample_mesh_poisson_disk_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, int64_t num_samples,       \
+                                           double radius, uint32_t seed, double tol, double oversampling, int64_t capacity, int64_t* out_fi,         \
+                                           T* out_bc, int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {                         \
+    CallGuard dg(c);                                                                                                                                 \
+    return abi_rc(sample_mesh_poisson_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, num_samples, radius, seed, tol, oversampling, capacity, out_fi, \
+                                              out_bc, out_count, flags, stream, st)); }
+PCU_MESH_SAMPLE(f32, float) PCU_MESH_SAMPLE(f64, double)
+#undef PCU_MESH_SAMPLE
 int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }
 void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) {
     if (!ix) return;

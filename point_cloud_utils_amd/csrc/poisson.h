@@ -26,12 +26,14 @@
 
 namespace pcu {
 
-__host__ __device__ __forceinline__ unsigned long long pd_priority(unsigned seed, unsigned long long row) {
-    unsigned long long z = ((unsigned long long)seed << 32) ^ row;
+__host__ __device__ __forceinline__ unsigned long long pd_mix(unsigned long long z) {        // the splitmix64 finalizer
     z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
     z ^= z >> 27; z *= 0x94D049BB133111EBull;
     z ^= z >> 31;
     return z;
+}
+__host__ __device__ __forceinline__ unsigned long long pd_priority(unsigned seed, unsigned long long row) {
+    return pd_mix(((unsigned long long)seed << 32) ^ row);
 }
 
 constexpr unsigned char kPdUndecided = 0, kPdSample = 1, kPdRemoved = 2, kPdStateMask = 3;

@@ -60,6 +60,93 @@ static int pd_run(PdRun<T>& R, T r, hipStream_t s, int64_t* count) {
     return 0;
 }
 
+// The argument checks of downsample_point_cloud_poisson_disk (src/sample_point_cloud.cpp:253-273), in its order; *tol: the tolerance as the
+// reference's float argument.
+static int pd_check_args(int64_t n, double radius, int64_t target, double tolerance, float* tol) {
+    if (target <= 0 && radius <= 0.0) return fail(PCU_HIP_ERR_INVALID, "Cannot have both num_samples <= 0 and radius <= 0");
+    if (target <= 0 && std::isnan(radius)) return fail(PCU_HIP_ERR_INVALID, "radius must not be NaN");
+    *tol = (float)tolerance;                                   // (npe_default_arg(sample_num_tolerance, float, 0.04))
+    if (!(*tol > 0.0f && *tol <= 1.0f)) return fail(PCU_HIP_ERR_INVALID, "sample_num_tolerance must be in (0, 1]");
+    if (n <= 0) return fail(PCU_HIP_ERR_INVALID, "Invalid point set with zero elements: v must have shape (n, 3) with n > 0.");
+    if (n > 0x07fffff0ll) return fail(PCU_HIP_ERR_INVALID, "point clouds with more than 2^27-16 rows are not supported");
+    return 0;
+}
+// What pd_body takes from the arena for n device-resident rows (target >= n > 0 returns every row: no index, no rounds).
+template <typename T>
+static size_t pd_body_bytes(int64_t n, int64_t target) {
+    if (target > 0 && target >= n) return 4096;
+    const size_t N = (size_t)n;
+    const int mc = max_cells_for(n, kPdOccupancy);
+    return index_bytes<T>(n, kPdOccupancy) + align_up(N * 8, 256) + align_up(N, 256) + 5 * align_up(N * 4, 256) +
+           align_up((size_t)mc * 12 + 64, 256) + align_up((N / kScTile + 2) * 4, 256) + 65536;
+}
+// The greedy and its radius search (:275-329) over device-resident rows, in an arena the caller has begun: d_out (room for n int32, on the
+// device) receives the samples' rows in ascending order, *count their number. The compaction is enqueued on s, not waited for.
+template <typename T>
+static int pd_body(Arena& ar, hipStream_t s, const T* d_pts, int64_t n, double radius, int64_t target, unsigned seed, float tol, int32_t* d_out,
+                   int64_t* count, PdRun<T>& R) {
+    const size_t N = (size_t)n;
+    const int nb = (int)((n + kBlock - 1) / kBlock);
+    if (target > 0 && target >= n) {                           // :275-279
+        hipLaunchKernelGGL(k_pd_iota, dim3(nb), dim3(kBlock), 0, s, (int)n, d_out);
+        HIP_TRY(hipGetLastError());
+        *count = n;
+        return 0;
+    }
+    int rc = 0;
+    R.seed = seed; R.pts = d_pts;
+    if ((rc = index_alloc(ar, R.gi, n, kPdOccupancy, IndexFor::Atomic))) return rc;
+    PdArgs<T>& a = R.a;
+    a.n = (int)n;
+    if ((rc = aalloc(ar, &a.prio, N)) || (rc = aalloc(ar, &a.state, N)) || (rc = aalloc(ar, &a.cell, N)) || (rc = aalloc(ar, &a.slist, N)) ||
+        (rc = aalloc(ar, &a.cellmin, (size_t)R.gi.max_cells)) || (rc = aalloc(ar, &a.nsamp, (size_t)R.gi.max_cells)) || (rc = aalloc(ar, &a.counters, 16))) return rc;
+    // the bounding box (target mode) and the non-finite check: a first build, read back
+    GridParams<T> hg;
+    if ((rc = pd_build(R, 0.0, s, &hg))) return rc;
+    if (hg.nonfinite) return fail(PCU_HIP_ERR_INVALID, "v must not contain NaN or infinite coordinates");
+    int64_t cnt = 0;
+    if (target <= 0) {
+        if ((rc = pd_run(R, (T)radius, s, &cnt))) return rc;
+    } else {
+        // :281-329, step for step in T
+        const size_t nmin = (size_t)(int)((T)target * (T)(1.0f - tol)), nmax = (size_t)(int)((T)target * (T)(1.0f + tol));
+        T e[3];
+        for (int j = 0; j < 3; ++j) e[j] = hg.gmax[j] - hg.gmin[j];
+        const T bbsize = std::sqrt(((e[0] * e[0]) + (e[1] * e[1])) + (e[2] * e[2]));
+        if (!std::isfinite(bbsize)) return fail(PCU_HIP_ERR_INVALID, "the bounding box diagonal of v overflows its scalar type");
+        if (bbsize == (T)0) {
+            // all rows equal: the reference's doubling loop never ends (every radius is 0). One run at r = inf: the row of lowest priority.
+            if ((rc = pd_run(R, std::numeric_limits<T>::infinity(), s, &cnt))) return rc;
+        } else {
+            T rmin = (T)((double)bbsize / 50.0), rmax = rmin;
+            do {
+                rmin = (T)((double)rmin / 2.0);
+                if ((rc = pd_run(R, rmin, s, &cnt))) return rc;
+            } while (cnt < target);
+            // (stops also once r * r is infinite in T: a larger radius could not change the result)
+            do {
+                rmax = (T)((double)rmax * 2.0);
+                if ((rc = pd_run(R, rmax, s, &cnt))) return rc;
+            } while (cnt > target && std::isfinite(rmax * rmax));
+            for (int it = 0; it < 20 && ((size_t)cnt < nmin || (size_t)cnt > nmax); ++it) {
+                const T cur = (T)((double)(rmin + rmax) / 2.0);
+                if ((rc = pd_run(R, cur, s, &cnt))) return rc;
+                if (cnt > target) rmin = cur;
+                if (cnt < target) rmax = cur;
+            }
+        }
+    }
+    // compaction of the last run: flags by row, inclusive scan, rows in ascending order
+    unsigned *flag = nullptr, *scan = nullptr;
+    if ((rc = aalloc(ar, &flag, N)) || (rc = aalloc(ar, &scan, N))) return rc;
+    hipLaunchKernelGGL(k_pd_flags<T>, dim3(nb), dim3(kBlock), 0, s, R.gi.sorted, a.state, (int)n, flag);
+    if ((rc = own_inclusive_scan(ar, s, flag, scan, N))) return rc;
+    hipLaunchKernelGGL(k_pd_compact, dim3(nb), dim3(kBlock), 0, s, flag, scan, (int)n, d_out);
+    HIP_TRY(hipGetLastError());
+    *count = cnt;
+    return 0;
+}
+
 // downsample_point_cloud_poisson_disk (src/sample_point_cloud.cpp:253-333). out_idx: room for n int32; *out_count entries are written.
 template <typename T>
 static int poisson_disk_impl(pcu_hip_ctx* c, const T* pts, int64_t n, double radius, int64_t target, unsigned seed, double tolerance,
@@ -67,98 +154,29 @@ static int poisson_disk_impl(pcu_hip_ctx* c, const T* pts, int64_t n, double rad
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
     if (st) memset(st, 0, sizeof *st);
     *out_count = 0;
-    if (target <= 0 && radius <= 0.0) return fail(PCU_HIP_ERR_INVALID, "Cannot have both num_samples <= 0 and radius <= 0");
-    if (target <= 0 && std::isnan(radius)) return fail(PCU_HIP_ERR_INVALID, "radius must not be NaN");
-    const float tol = (float)tolerance;                        // (npe_default_arg(sample_num_tolerance, float, 0.04))
-    if (!(tol > 0.0f && tol <= 1.0f)) return fail(PCU_HIP_ERR_INVALID, "sample_num_tolerance must be in (0, 1]");
-    if (n <= 0) return fail(PCU_HIP_ERR_INVALID, "Invalid point set with zero elements: v must have shape (n, 3) with n > 0.");
-    if (n > 0x07fffff0ll) return fail(PCU_HIP_ERR_INVALID, "point clouds with more than 2^27-16 rows are not supported");
+    float tol = 0.0f;
+    if (int rc = pd_check_args(n, radius, target, tolerance, &tol)) return rc;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
     hipStream_t s = pick_stream(c, flags, stream);
     const size_t N = (size_t)n;
-    const int nb = (int)((n + kBlock - 1) / kBlock);
-    if (target > 0 && target >= n) {                           // :275-279
-        if (ctx_begin(c, on_dev ? 4096 : align_up(N * 4, 256) + 4096)) return PCU_HIP_ERR_RUNTIME;
-        Arena ar{c};
-        int32_t* d_out = out_idx;
-        if (!on_dev && aalloc(ar, &d_out, N)) { ctx_end(c); return PCU_HIP_ERR_RUNTIME; }
-        hipLaunchKernelGGL(k_pd_iota, dim3(nb), dim3(kBlock), 0, s, (int)n, d_out);
-        if (hipGetLastError() != hipSuccess) { ctx_end(c); return fail(PCU_HIP_ERR_RUNTIME, "k_pd_iota launch failed"); }
-        if (!on_dev && hipMemcpyAsync(out_idx, d_out, N * 4, hipMemcpyDeviceToHost, s) != hipSuccess) { ctx_end(c); return fail(PCU_HIP_ERR_RUNTIME, "copy of the indices failed"); }
-        const int w = wait_stream(s);
-        ctx_end(c);
-        if (w) return w;
-        *out_count = n;
-        return 0;
-    }
-    const int mc = max_cells_for(n, kPdOccupancy);
-    size_t need = index_bytes<T>(n, kPdOccupancy) + align_up(N * 8, 256) + align_up(N, 256) + 5 * align_up(N * 4, 256) +
-                  align_up((size_t)mc * 12 + 64, 256) + align_up((N / kScTile + 2) * 4, 256) + 65536;
-    if (!on_dev) need += align_up(N * 3 * sizeof(T), 256) + align_up(N * 4, 256);
+    const bool all_rows = target > 0 && target >= n;
+    size_t need = pd_body_bytes<T>(n, target);
+    if (!on_dev) need += (all_rows ? 0 : align_up(N * 3 * sizeof(T), 256)) + align_up(N * 4, 256);
     if (ctx_begin(c, need)) return PCU_HIP_ERR_RUNTIME;
     Arena ar{c};
     int rc = 0;
     PdRun<T> R;
-    R.seed = seed;
     do {
-        if ((rc = stage_in(ar, pts, n, on_dev, s, &R.pts))) break;
-        if ((rc = index_alloc(ar, R.gi, n, kPdOccupancy, IndexFor::Atomic))) break;
-        PdArgs<T>& a = R.a;
-        a.n = (int)n;
-        if ((rc = aalloc(ar, &a.prio, N)) || (rc = aalloc(ar, &a.state, N)) || (rc = aalloc(ar, &a.cell, N)) || (rc = aalloc(ar, &a.slist, N)) ||
-            (rc = aalloc(ar, &a.cellmin, (size_t)R.gi.max_cells)) || (rc = aalloc(ar, &a.nsamp, (size_t)R.gi.max_cells)) || (rc = aalloc(ar, &a.counters, 16))) break;
-        // the bounding box (target mode) and the non-finite check: a first build, read back
-        GridParams<T> hg;
-        if ((rc = pd_build(R, 0.0, s, &hg))) break;
-        if (hg.nonfinite) { rc = fail(PCU_HIP_ERR_INVALID, "v must not contain NaN or infinite coordinates"); break; }
-        int64_t cnt = 0;
-        if (target <= 0) {
-            if ((rc = pd_run(R, (T)radius, s, &cnt))) break;
-        } else {
-            // :281-329, step for step in T
-            const size_t nmin = (size_t)(int)((T)target * (T)(1.0f - tol)), nmax = (size_t)(int)((T)target * (T)(1.0f + tol));
-            T e[3];
-            for (int j = 0; j < 3; ++j) e[j] = hg.gmax[j] - hg.gmin[j];
-            const T bbsize = std::sqrt(((e[0] * e[0]) + (e[1] * e[1])) + (e[2] * e[2]));
-            if (!std::isfinite(bbsize)) { rc = fail(PCU_HIP_ERR_INVALID, "the bounding box diagonal of v overflows its scalar type"); break; }
-            if (bbsize == (T)0) {
-                // all rows equal: the reference's doubling loop never ends (every radius is 0). One run at r = inf: the row of lowest priority.
-                if ((rc = pd_run(R, std::numeric_limits<T>::infinity(), s, &cnt))) break;
-            } else {
-                T rmin = (T)((double)bbsize / 50.0), rmax = rmin;
-                do {
-                    rmin = (T)((double)rmin / 2.0);
-                    if ((rc = pd_run(R, rmin, s, &cnt))) break;
-                } while (cnt < target);
-                if (rc) break;
-                // (stops also once r * r is infinite in T: a larger radius could not change the result)
-                do {
-                    rmax = (T)((double)rmax * 2.0);
-                    if ((rc = pd_run(R, rmax, s, &cnt))) break;
-                } while (cnt > target && std::isfinite(rmax * rmax));
-                if (rc) break;
-                for (int it = 0; it < 20 && ((size_t)cnt < nmin || (size_t)cnt > nmax); ++it) {
-                    const T cur = (T)((double)(rmin + rmax) / 2.0);
-                    if ((rc = pd_run(R, cur, s, &cnt))) break;
-                    if (cnt > target) rmin = cur;
-                    if (cnt < target) rmax = cur;
-                }
-                if (rc) break;
-            }
-        }
-        // compaction of the last run: flags by row, inclusive scan, rows in ascending order
-        unsigned *flag = nullptr, *scan = nullptr;
+        const T* d_pts = nullptr;
+        if (!all_rows && (rc = stage_in(ar, pts, n, on_dev, s, &d_pts))) break;
         int32_t* d_out = out_idx;
-        if ((rc = aalloc(ar, &flag, N)) || (rc = aalloc(ar, &scan, N))) break;
         if (!on_dev && (rc = aalloc(ar, &d_out, N))) break;
-        hipLaunchKernelGGL(k_pd_flags<T>, dim3(nb), dim3(kBlock), 0, s, R.gi.sorted, a.state, (int)n, flag);
-        if ((rc = own_inclusive_scan(ar, s, flag, scan, N))) break;
-        hipLaunchKernelGGL(k_pd_compact, dim3(nb), dim3(kBlock), 0, s, flag, scan, (int)n, d_out);
-        HIP_TRY(hipGetLastError());
+        int64_t cnt = 0;
+        if ((rc = pd_body<T>(ar, s, d_pts, n, radius, target, seed, tol, d_out, &cnt, R))) break;
         if (!on_dev && cnt > 0) HIP_TRY(hipMemcpyAsync(out_idx, d_out, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         *out_count = cnt;
-        if (st) { st->n_queries = n; st->n_passes = R.rounds; st->n_grid_builds = R.radii; }
+        if (st && !all_rows) { st->n_queries = n; st->n_passes = R.rounds; st->n_grid_builds = R.radii; }
     } while (0);
     ctx_end(c);
     return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;

@@ -172,52 +172,55 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_scatter(const unsigned long l
     }
 }
 
-// ---- inclusive scan of n unsigned values: tiles of 4096, one block for the tile sums, add
+// ---- inclusive scan of n unsigned values (U: 32 or 64 bits wide): tiles of 4096, one block for the tile sums, add
 constexpr int kScTile = 4096;
-__global__ __launch_bounds__(1024) void k_sc_tiles(const unsigned* __restrict__ in, unsigned* __restrict__ out, int n, unsigned* __restrict__ tile_sum) {
-    __shared__ unsigned s_w[16];
+template <typename U>
+__global__ __launch_bounds__(1024) void k_sc_tiles(const U* __restrict__ in, U* __restrict__ out, int n, U* __restrict__ tile_sum) {
+    __shared__ U s_w[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long i0 = (long long)blockIdx.x * kScTile + 4ll * tid;
-    unsigned v[4], s = 0;
+    U v[4], s = 0;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { v[q] = i0 + q < n ? in[i0 + q] : 0u; s += v[q]; v[q] = s; }
-    unsigned inc = s;
+    for (int q = 0; q < 4; ++q) { v[q] = i0 + q < n ? in[i0 + q] : (U)0; s += v[q]; v[q] = s; }
+    U inc = s;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned u = (unsigned)__shfl_up((int)inc, o, 64); if (lane >= o) inc += u; }
+    for (int o = 1; o < 64; o <<= 1) { const U u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
     if (lane == 63) s_w[wave] = inc;
     __syncthreads();
-    unsigned wb = 0;
+    U wb = 0;
     for (int w = 0; w < wave; ++w) wb += s_w[w];
-    const unsigned ex = wb + inc - s;
+    const U ex = wb + inc - s;
 #pragma unroll
     for (int q = 0; q < 4; ++q) if (i0 + q < n) out[i0 + q] = ex + v[q];
     if (tid == 1023) tile_sum[blockIdx.x] = wb + inc;
 }
-__global__ __launch_bounds__(1024) void k_sc_sums(unsigned* __restrict__ tile_sum, int nt) {       // exclusive scan in place (one block)
-    __shared__ unsigned s_w[16];
-    __shared__ unsigned s_carry;
+template <typename U>
+__global__ __launch_bounds__(1024) void k_sc_sums(U* __restrict__ tile_sum, int nt) {       // exclusive scan in place (one block)
+    __shared__ U s_w[16];
+    __shared__ U s_carry;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry = 0u;
+    if (tid == 0) s_carry = 0;
     __syncthreads();
     for (int c0 = 0; c0 < nt; c0 += 1024) {
         const int i = c0 + tid;
-        const unsigned v = i < nt ? tile_sum[i] : 0u;
-        unsigned inc = v;
+        const U v = i < nt ? tile_sum[i] : (U)0;
+        U inc = v;
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned u = (unsigned)__shfl_up((int)inc, o, 64); if (lane >= o) inc += u; }
+        for (int o = 1; o < 64; o <<= 1) { const U u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
         if (lane == 63) s_w[wave] = inc;
         __syncthreads();
-        unsigned wb = 0;
+        U wb = 0;
         for (int w = 0; w < wave; ++w) wb += s_w[w];
-        const unsigned carry = s_carry;
+        const U carry = s_carry;
         if (i < nt) tile_sum[i] = carry + wb + inc - v;
         __syncthreads();
         if (tid == 1023) s_carry = carry + wb + inc;
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(1024) void k_sc_add(unsigned* __restrict__ out, int n, const unsigned* __restrict__ tile_sum) {
-    const unsigned add = tile_sum[blockIdx.x];
+template <typename U>
+__global__ __launch_bounds__(1024) void k_sc_add(U* __restrict__ out, int n, const U* __restrict__ tile_sum) {
+    const U add = tile_sum[blockIdx.x];
     const long long i0 = (long long)blockIdx.x * kScTile + 4ll * threadIdx.x;
 #pragma unroll
     for (int q = 0; q < 4; ++q) if (i0 + q < n) out[i0 + q] += add;

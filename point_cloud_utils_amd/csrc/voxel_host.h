@@ -72,15 +72,16 @@ static int morton_knn_impl(pcu_hip_ctx* c, const C* codes, int64_t n, const C* q
 }
 
 // ---------------------------------------------------------------------------------------------------- sort by a key triple
-// inclusive scan of n unsigned values (radix.h: tiles, one block over the tile sums, add)
-static int own_inclusive_scan(Arena& ar, hipStream_t s, const unsigned* in, unsigned* out, size_t n) {
+// inclusive scan of n unsigned values, 32 or 64 bits wide (radix.h: tiles, one block over the tile sums, add)
+template <typename U>
+static int own_inclusive_scan(Arena& ar, hipStream_t s, const U* in, U* out, size_t n) {
     const int nt = (int)((n + kScTile - 1) / kScTile);
-    unsigned* sums = nullptr;
+    U* sums = nullptr;
     if (aalloc(ar, &sums, (size_t)nt + 1)) return -1;
-    hipLaunchKernelGGL(k_sc_tiles, dim3(nt), dim3(1024), 0, s, in, out, (int)n, sums);
+    hipLaunchKernelGGL(k_sc_tiles<U>, dim3(nt), dim3(1024), 0, s, in, out, (int)n, sums);
     if (nt > 1) {
-        hipLaunchKernelGGL(k_sc_sums, dim3(1), dim3(1024), 0, s, sums, nt);
-        hipLaunchKernelGGL(k_sc_add, dim3(nt), dim3(1024), 0, s, out, (int)n, sums);
+        hipLaunchKernelGGL(k_sc_sums<U>, dim3(1), dim3(1024), 0, s, sums, nt);
+        hipLaunchKernelGGL(k_sc_add<U>, dim3(nt), dim3(1024), 0, s, out, (int)n, sums);
     }
     HIP_TRY(hipGetLastError());
     return 0;
