@@ -49,12 +49,12 @@ struct MeshHead {
 template <typename T>
 struct MeshIdx {                                // device pointers of one index
     MeshHead<T>* head = nullptr;
-    T* tri = nullptr;                           // (nf, 9): the faces' corners in Morton order
-    unsigned* face = nullptr;                   // (nf): face index of every sorted position
+    T* tri = nullptr;                           // (nf, 9): the faces' corners in Morton order (pc_winding.h: (nf, 6), a point and its dipole)
+    unsigned* face = nullptr;                   // (nf): face index of every sorted position (pc_winding.h: null)
     T* box = nullptr;                           // (2P - 1, 6): lo[3], hi[3] of every node
     T* ctr = nullptr;                           // (2P - 1, 4): centre and radius of every node's expansion (mesh_winding.h); null unless asked for
     T* mom = nullptr;                           // (2P - 1, 30): its moments; null unless asked for
-    int nf = 0, P = 0;
+    int nf = 0, P = 0;                          // elements (faces; pc_winding.h: points) and leaves, padded to a power of two
 };
 
 // ---------------------------------------------------------------------------------------------------- build
@@ -271,16 +271,24 @@ struct MeshQuery {
 // row and its best so far:
 //   node(box, key) -> whether the node can still hold the winner (the operator's "Pruning" rule, against the best of that moment), and the key
 //                     that orders two children (the lower one is taken first);
-//   face(a, b, c, id) evaluates one face and keeps it if it beats the best; `id` points at its face index.
+//   kLeaf             the elements of one leaf: sorted positions [kLeaf j, kLeaf (j + 1)) lie below leaf j;
+//   element(ix, s)    evaluates the element at sorted position s. The mesh visitors fetch a face there (mesh_face_at) and hand it to their
+//                     face(a, b, c, id), which keeps it if it beats the best; `id` points at its face index.
 // The child with the lower key is taken first and the other pushed if it passes too: at most one entry per level, so the stack (LDS, one column
 // per lane: a runtime-indexed private array would live in scratch memory) holds kMeshStack node ids. A popped node is tested again, against the
 // best of that moment. `live` says whether the lane walks at all (the root is not tested here). Returns true if the call was cancelled: the
 // caller then returns without writing its row. The leaf loop stays rolled: unrolled, it is a four times larger kernel for the point visitor.
+// The element of the three mesh visitors: the face at sorted position s, 9 scalars, and its index.
+template <typename T, typename Visitor>
+__device__ __forceinline__ void mesh_face_at(Visitor& vis, const MeshIdx<T>& ix, long long s) {
+    const T* __restrict__ tr = ix.tri + 9 * (size_t)s;
+    const T fa[3] = {tr[0], tr[1], tr[2]}, fb[3] = {tr[3], tr[4], tr[5]}, fc[3] = {tr[6], tr[7], tr[8]};
+    vis.face(fa, fb, fc, ix.face + s);
+}
 template <typename T, typename Visitor>
 __device__ __forceinline__ bool mesh_walk(const MeshIdx<T>& ix, Visitor& vis, bool live, const unsigned* cancel_word, unsigned cancel_gen) {
     __shared__ int s_stack[kMeshStack][kMeshBlock];
     const T* __restrict__ box = ix.box;
-    const T* __restrict__ tri = ix.tri;
     const int first_leaf = ix.P - 1, nf = ix.nf;
     int sp = 0, node = 0;
     unsigned steps = 0;
@@ -289,14 +297,12 @@ __device__ __forceinline__ bool mesh_walk(const MeshIdx<T>& ix, Visitor& vis, bo
         if ((++steps & 63u) == 0u) { const long long t_now = wall_clock64(); if (t_now - t_poll > 20000ll) { t_poll = t_now; if (cancel_seen(cancel_word, cancel_gen)) return true; } }
         bool descend = false;
         if (node >= first_leaf) {
-            const long long s0 = (long long)kMeshLeaf * (node - first_leaf);
+            const long long s0 = (long long)Visitor::kLeaf * (node - first_leaf);
 #pragma unroll 1
-            for (int t = 0; t < kMeshLeaf; ++t) {
+            for (int t = 0; t < Visitor::kLeaf; ++t) {
                 const long long s = s0 + t;
                 if (s >= nf) break;
-                const T* tr = tri + 9 * (size_t)s;
-                const T fa[3] = {tr[0], tr[1], tr[2]}, fb[3] = {tr[3], tr[4], tr[5]}, fc[3] = {tr[6], tr[7], tr[8]};
-                vis.face(fa, fb, fc, ix.face + s);
+                vis.element(ix, s);
             }
         } else {
             const int c0 = 2 * node + 1;
@@ -330,6 +336,8 @@ struct MeshBest { T best = (T)INFINITY, bv = (T)0, bw = (T)0; unsigned bf = 0xff
 template <typename T>
 struct MeshPointVisitor : MeshBest<T> {         // lexicographic (d2, face); a node whose bound EQUALS the best is visited
     T q[3];
+    static constexpr int kLeaf = kMeshLeaf;
+    __device__ __forceinline__ void element(const MeshIdx<T>& ix, long long s) { mesh_face_at(*this, ix, s); }
     __device__ __forceinline__ bool node(const T* __restrict__ bx, T& key) const { key = mesh_bound(bx, q); return key <= this->best; }
     __device__ __forceinline__ void face(const T a[3], const T b[3], const T c[3], const unsigned* __restrict__ pid) {
         T d2, v, w;
@@ -501,6 +509,8 @@ struct MeshRays {
 template <typename T>
 struct MeshRayVisitor : MeshBest<T> {           // the smallest accepted t, the lowest face among equal t; a node whose t_in EQUALS the best is visited
     MeshRay<T> r;
+    static constexpr int kLeaf = kMeshLeaf;
+    __device__ __forceinline__ void element(const MeshIdx<T>& ix, long long s) { mesh_face_at(*this, ix, s); }
     __device__ __forceinline__ bool node(const T* __restrict__ bx, T& key) const { return mesh_ray_node(r, bx, this->best, key); }
     __device__ __forceinline__ void face(const T a[3], const T b[3], const T c[3], const unsigned* __restrict__ pid) {
         T t, b1, b2;

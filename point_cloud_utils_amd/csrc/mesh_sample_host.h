@@ -16,20 +16,30 @@ static size_t ms_mesh_bytes(const MeshGiven<T>& m, bool on_dev) {
     if (!on_dev) b += align_up((size_t)m.nv * 3 * sizeof(T), 256) + align_up(NF * 3 * mesh_face_bytes(m.f_kind), 256);
     return b;
 }
-// Enqueues staging, the checks of v and f, the areas (into d_area if given) and, with `weights`, the weights and their scan. No wait.
+// Enqueues staging and the checks of v and f (the range-checked faces, the flag word). No wait.
 template <typename T>
-static int ms_mesh_enqueue(Arena& ar, hipStream_t s, const MeshGiven<T>& m, bool on_dev, bool weights, T* d_area, MsMesh<T>& M) {
+static int ms_mesh_stage(Arena& ar, hipStream_t s, const MeshGiven<T>& m, bool on_dev, MsMesh<T>& M) {
     const char* df = nullptr;
     if (stage_in(ar, m.v, m.nv, on_dev, s, &M.v) ||
         stage_any(ar, static_cast<const char*>(m.f), (size_t)m.nf * 3 * mesh_face_bytes(m.f_kind), on_dev, s, &df)) return -1;
-    M.nf = (int)m.nf; M.area = d_area;
-    if (aalloc(ar, &M.head, 1) || aalloc(ar, &M.mh, 1) || aalloc(ar, &M.fidx, (size_t)m.nf * 3) || (!M.area && aalloc(ar, &M.area, (size_t)m.nf))) return -1;
-    const int nbf = (int)((m.nf + kBlock - 1) / kBlock);
+    M.nf = (int)m.nf;
+    if (aalloc(ar, &M.head, 1) || aalloc(ar, &M.fidx, (size_t)m.nf * 3)) return -1;
     hipLaunchKernelGGL(k_mesh_head_init<T>, dim3(1), dim3(64), 0, s, M.head);
-    HIP_TRY(hipMemsetAsync(M.mh, 0, sizeof(MsHead<T>), s));
     int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
     hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3((unsigned)((m.nv * 3 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, M.v, (long long)m.nv * 3, d_bad, kMeshBadVertex);
-    hipLaunchKernelGGL(k_mesh_faces<T>, dim3(nbf), dim3(kBlock), 0, s, (const void*)df, m.f_kind, (int)m.nf, (int)m.nv, M.v, M.fidx, M.head);
+    hipLaunchKernelGGL(k_mesh_faces<T>, dim3((unsigned)((m.nf + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, (const void*)df, m.f_kind, (int)m.nf, (int)m.nv, M.v,
+                       M.fidx, M.head);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// ms_mesh_stage, then the areas (into d_area if given) and, with `weights`, the weights and their scan. No wait.
+template <typename T>
+static int ms_mesh_enqueue(Arena& ar, hipStream_t s, const MeshGiven<T>& m, bool on_dev, bool weights, T* d_area, MsMesh<T>& M) {
+    if (ms_mesh_stage(ar, s, m, on_dev, M)) return -1;
+    M.area = d_area;
+    if (aalloc(ar, &M.mh, 1) || (!M.area && aalloc(ar, &M.area, (size_t)m.nf))) return -1;
+    const int nbf = (int)((m.nf + kBlock - 1) / kBlock);
+    HIP_TRY(hipMemsetAsync(M.mh, 0, sizeof(MsHead<T>), s));
     hipLaunchKernelGGL(k_mesh_areas<T>, dim3(nbf), dim3(kBlock), 0, s, M.v, (const int*)M.fidx, (int)m.nf, M.area, M.mh);
     if (weights) {
         unsigned long long* w = nullptr;

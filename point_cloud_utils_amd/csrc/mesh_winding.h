@@ -245,7 +245,7 @@ __device__ __forceinline__ T mesh_wind_far(const T* __restrict__ m, const T R[3]
 // pops it. That adds nothing twice: the test is a pure function of query and node, only nodes that pass (are to be opened) are pushed, and a
 // node that passes adds nothing.
 template <typename T>
-struct MeshWindVisitor {
+struct MeshWindNodes {                          // the node rule and the sum, shared with the dipole tree of pc_winding.h
     T q[3], beta, acc = (T)0;
     const T* box0; const T* ctr; const T* mom;
     __device__ __forceinline__ bool node(const T* __restrict__ bx, T& key) {
@@ -260,7 +260,12 @@ struct MeshWindVisitor {
         acc += mesh_wind_far(mom + 30 * n, R, d);
         return false;
     }
-    __device__ __forceinline__ void face(const T a[3], const T b[3], const T c[3], const unsigned* __restrict__) { acc += mesh_wind_face(q, a, b, c); }
+};
+template <typename T>
+struct MeshWindVisitor : MeshWindNodes<T> {
+    static constexpr int kLeaf = kMeshLeaf;
+    __device__ __forceinline__ void element(const MeshIdx<T>& ix, long long s) { mesh_face_at(*this, ix, s); }
+    __device__ __forceinline__ void face(const T a[3], const T b[3], const T c[3], const unsigned* __restrict__) { this->acc += mesh_wind_face(this->q, a, b, c); }
 };
 
 template <typename T>
@@ -273,9 +278,9 @@ struct MeshSigned {                             // the rows of both operators; t
 };
 
 // w of one query (the root is tested before the walk: it may be far as a whole). Returns true if the call was cancelled.
-template <typename T>
+template <typename T, typename Visitor = MeshWindVisitor<T>>
 __device__ __forceinline__ bool mesh_wind_query(const MeshSigned<T>& a, const T q[3], bool finite, T& w) {
-    MeshWindVisitor<T> vis;
+    Visitor vis;
     vis.q[0] = q[0]; vis.q[1] = q[1]; vis.q[2] = q[2]; vis.beta = a.beta;
     vis.box0 = a.ix.box; vis.ctr = a.ix.ctr; vis.mom = a.ix.mom;
     T key;

@@ -39,6 +39,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "mesh.h"
 #include "mesh_winding.h"
 #include "mesh_sample.h"
+#include "pc_winding.h"
 
 using namespace pcu;
 
@@ -2380,6 +2381,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "poisson_host.h"
 #include "mesh_host.h"
 #include "mesh_sample_host.h"
+#include "pc_winding_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2663,6 +2665,32 @@ int pcu_hip_sample_mesh_poisson_disk_##SUF(pcu_hip_ctx* c, const T* v, int64_t n
                                               out_bc, out_count, flags, stream, st)); }
 PCU_MESH_SAMPLE(f32, float) PCU_MESH_SAMPLE(f64, double)
 #undef PCU_MESH_SAMPLE
+// point_cloud_fast_winding_number and estimate_mesh_face_normals (pc_winding.h, pc_winding_host.h)
+#define PCU_PC_WIND(SUF, T)                                                                                                                           \
+int pcu_hip_point_cloud_fast_winding_number_##SUF(pcu_hip_ctx* c, const T* p, const T* n, const T* a, int64_t np, const T* q, int64_t nq, double beta, \
+                                                  T* out_w, unsigned flags, void* stream, pcu_hip_stats* st) {                                       \
+    CallGuard dg(c); const PcGiven<T> pc{p, n, a, np};                                                                                               \
+    return abi_rc(pc_call<T>(c, &pc, nullptr, q, nq, beta, out_w, flags, stream, st)); }                                                             \
+int pcu_hip_pc_winding_index_create_##SUF(pcu_hip_ctx* c, const T* p, const T* n, const T* a, int64_t np, unsigned flags, void* stream,              \
+                                          pcu_hip_pc_winding_index** out) {                                                                          \
+    CallGuard dg(c);                                                                                                                                 \
+    const int rc = abi_rc(pc_index_create_impl<T>(c, p, n, a, np, flags, stream, out));                                                              \
+    if (rc && out && *out) { DeviceGuard g(c->device); (void)hipDeviceSynchronize(); pc_index_free(*out); *out = nullptr; }                          \
+    return rc; }                                                                                                                                     \
+int pcu_hip_pc_winding_index_query_##SUF(pcu_hip_ctx* c, const pcu_hip_pc_winding_index* ix, const T* q, int64_t nq, double beta, T* out_w,          \
+                                         unsigned flags, void* stream, pcu_hip_stats* st) {                                                          \
+    CallGuard dg(c); return abi_rc(pc_call<T>(c, nullptr, ix, q, nq, beta, out_w, flags, stream, st)); }                                             \
+int pcu_hip_estimate_mesh_face_normals_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, T* out_n, unsigned flags, \
+                                             void* stream, pcu_hip_stats* st) {                                                                      \
+    CallGuard dg(c); return abi_rc(mesh_face_normals_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, out_n, flags, stream, st)); }
+PCU_PC_WIND(f32, float) PCU_PC_WIND(f64, double)
+#undef PCU_PC_WIND
+void pcu_hip_pc_winding_index_destroy(pcu_hip_pc_winding_index* ix) {
+    if (!ix) return;
+    DeviceGuard dg(ix->device);
+    (void)hipDeviceSynchronize();
+    pc_index_free(ix);
+}
 int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }
 void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) {
     if (!ix) return;
