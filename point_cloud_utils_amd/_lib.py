@@ -41,7 +41,8 @@ _COMPUTE_ENTRY_POINTS = [f"pcu_hip_{op}_{suf}" for suf in ("f32", "f64") for op 
     "normals_ball", "dedup", "pairwise", "sinkhorn", "dot", "debug_kd_tree", "poisson_disk", "closest_points_on_mesh", "mesh_index_create",
     "mesh_index_closest", "ray_mesh_intersection", "mesh_index_rays", "triangle_soup_fast_winding_number", "signed_distance_to_mesh",
     "mesh_index_winding", "mesh_index_signed_distance", "mesh_face_areas", "sample_mesh_random", "sample_mesh_poisson_disk",
-    "point_cloud_fast_winding_number", "pc_winding_index_create", "pc_winding_index_query", "estimate_mesh_face_normals")] + [
+    "point_cloud_fast_winding_number", "pc_winding_index_create", "pc_winding_index_query", "estimate_mesh_face_normals",
+    "surfel_geometry", "surfel_rays", "surfel_index_create", "surfel_index_rays")] + [
     "pcu_hip_morton_encode", "pcu_hip_morton_decode", "pcu_hip_morton_addsub", "pcu_hip_morton_knn"] + [
     f"pcu_hip_voxel_downsample_{sp}_{sa}" for sp in ("f32", "f64") for sa in ("f32", "f64")]
 
@@ -137,6 +138,10 @@ def lib():
             getattr(L, "pcu_hip_pc_winding_index_create_" + sp).argtypes = [vp, vp, vp, vp, i64, u, vp, ctypes.POINTER(ctypes.c_void_p)]
             getattr(L, "pcu_hip_pc_winding_index_query_" + sp).argtypes = [vp, vp, vp, i64, dbl, vp, u, vp, vp]
             getattr(L, "pcu_hip_estimate_mesh_face_normals_" + sp).argtypes = [vp, vp, i64, vp, i64, ci, vp, u, vp, vp]
+            getattr(L, "pcu_hip_surfel_geometry_" + sp).argtypes = [vp, vp, vp, vp, i64, ci, vp, vp, u, vp, vp]
+            getattr(L, "pcu_hip_surfel_rays_" + sp).argtypes = [vp, vp, vp, vp, i64, ci, vp, i64, vp, i64, dbl, dbl, vp, vp, u, vp, vp]
+            getattr(L, "pcu_hip_surfel_index_create_" + sp).argtypes = [vp, vp, vp, vp, i64, ci, u, vp, ctypes.POINTER(ctypes.c_void_p)]
+            getattr(L, "pcu_hip_surfel_index_rays_" + sp).argtypes = [vp, vp, vp, i64, vp, i64, dbl, dbl, vp, vp, u, vp, vp]
         for sp in ("f32", "f64"):
             getattr(L, "pcu_hip_pairwise_" + sp).argtypes = [vp, vp, vp, i64, i64, i64, i64, ctypes.c_double, vp, u, vp]
             getattr(L, "pcu_hip_sinkhorn_" + sp).argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_double, ci, ctypes.c_double, vp, vp, u, vp]
@@ -152,6 +157,10 @@ def lib():
         L.pcu_hip_mesh_index_destroy.restype = None
         L.pcu_hip_pc_winding_index_destroy.argtypes = [vp]
         L.pcu_hip_pc_winding_index_destroy.restype = None
+        L.pcu_hip_surfel_index_size.restype = ctypes.c_int64
+        L.pcu_hip_surfel_index_size.argtypes = [vp]
+        L.pcu_hip_surfel_index_destroy.argtypes = [vp]
+        L.pcu_hip_surfel_index_destroy.restype = None
         L.pcu_hip_cancel.restype = None
         L.pcu_hip_watch_sigint.argtypes = [ci]
         L.pcu_hip_cancel_source.restype = ci

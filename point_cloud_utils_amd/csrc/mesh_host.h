@@ -108,7 +108,8 @@ static int mesh_build(Arena& ari, Arena& ar, hipStream_t s, const T* v, int64_t 
 }
 
 // ---------------------------------------------------------------------------------------------------- the operators
-// All answer, per row, with one T (distance / t / w / s) and, unless kFaces is false, one int64 face and three T barycentrics. What differs is
+// All answer, per row, with one T (distance / t / w / s) and, unless kFaces is false, one int64 id (a face; surfel_host.h: a point) and,
+// unless kBary is false too, three T barycentrics. What differs is
 // an Op: its inputs, how many (n,3) arrays a call with host arrays stages (kRows3, inputs and barycentrics), whether it needs the moments of
 // mesh_winding.h (kMoments), its checks ahead of the mesh's, the kernel and the bits of the sort key, the walk kernel with its parameters and
 // the message of each bit of the flag word.
@@ -117,7 +118,7 @@ struct MeshPointsOp {                           // closest_points_on_mesh (src/c
     const T* p;
     using Params = MeshQuery<T>;
     static constexpr int kRows3 = 2, kKeyBits = 30;
-    static constexpr bool kMoments = false, kFaces = true;
+    static constexpr bool kMoments = false, kFaces = true, kBary = true;
     int validate(int64_t) const { return 0; }
     int stage(Arena& ar, hipStream_t s, int64_t n, bool on_dev) { return stage_in(ar, p, n, on_dev, s, &p); }
     void keys(hipStream_t s, int64_t n, const MeshHead<T>* h, unsigned long long* k, int* d_bad) const {
@@ -134,7 +135,7 @@ struct MeshRaysOp {                             // ray_mesh_intersection (src/ra
     const T* o; int64_t o_rows; const T* d; double ray_near, ray_far;
     using Params = MeshRays<T>;
     static constexpr int kRows3 = 3, kKeyBits = kMeshRayKeyBits;
-    static constexpr bool kMoments = false, kFaces = true;
+    static constexpr bool kMoments = false, kFaces = true, kBary = true;
     int validate(int64_t n) const {
         if (n < 0) return fail(PCU_HIP_ERR_INVALID, "negative number of rays");
         if (n > kMeshMaxRows) return mesh_row_limit();
@@ -199,7 +200,7 @@ static int mesh_run(Arena& ar, hipStream_t s, const MeshIdx<T>& M, Op op, int64_
     unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
     if (aalloc(ar, &d_bad, 1) || aalloc(ar, &ka, (size_t)n) || aalloc(ar, &kb, (size_t)n) || aalloc(ar, &ia, (size_t)n) || aalloc(ar, &ib, (size_t)n)) return -1;
     T *d_val = out_val, *d_bc = out_bc; long long* d_fi = reinterpret_cast<long long*>(out_fi);
-    if (!on_dev && (aalloc(ar, &d_val, (size_t)n) || (Op::kFaces && (aalloc(ar, &d_fi, (size_t)n) || aalloc(ar, &d_bc, (size_t)n * 3))))) return -1;
+    if (!on_dev && (aalloc(ar, &d_val, (size_t)n) || (Op::kFaces && (aalloc(ar, &d_fi, (size_t)n) || (Op::kBary && aalloc(ar, &d_bc, (size_t)n * 3)))))) return -1;
     HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
     op.keys(s, n, M.head, ka, d_bad);
     if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)n, Op::kKeyBits)) return -1;
@@ -215,7 +216,7 @@ static int mesh_run(Arena& ar, hipStream_t s, const MeshIdx<T>& M, Op op, int64_
         HIP_TRY(hipMemcpyAsync(out_val, d_val, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, s));
         if (Op::kFaces) {
             HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)n * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+            if (Op::kBary) HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)n * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
         }
     }
     HIP_WAIT(s);

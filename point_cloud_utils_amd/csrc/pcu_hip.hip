@@ -40,6 +40,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "mesh_winding.h"
 #include "mesh_sample.h"
 #include "pc_winding.h"
+#include "surfel.h"
 
 using namespace pcu;
 
@@ -2382,6 +2383,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "mesh_host.h"
 #include "mesh_sample_host.h"
 #include "pc_winding_host.h"
+#include "surfel_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2690,6 +2692,35 @@ void pcu_hip_pc_winding_index_destroy(pcu_hip_pc_winding_index* ix) {
     DeviceGuard dg(ix->device);
     (void)hipDeviceSynchronize();
     pc_index_free(ix);
+}
+// ray_surfel_intersection and pointcloud_surfel_geometry (surfel.h, surfel_host.h)
+#define PCU_SURFEL(SUF, T)                                                                                                                            \
+int pcu_hip_surfel_geometry_##SUF(pcu_hip_ctx* c, const T* p, const T* n, const T* r, int64_t np, int subdivs, T* out_v, int32_t* out_f,             \
+                                  unsigned flags, void* stream, pcu_hip_stats* st) {                                                                 \
+    CallGuard dg(c); return abi_rc(surfel_geometry_impl<T>(c, p, n, r, np, subdivs, out_v, out_f, flags, stream, st)); }                             \
+int pcu_hip_surfel_rays_##SUF(pcu_hip_ctx* c, const T* p, const T* n, const T* r, int64_t np, int subdivs, const T* ray_o, int64_t o_rows,           \
+                              const T* ray_d, int64_t n_rays, double ray_near, double ray_far, int64_t* out_pid, T* out_t, unsigned flags,           \
+                              void* stream, pcu_hip_stats* st) {                                                                                     \
+    CallGuard dg(c); const SurfelGiven<T> sf{p, n, r, np, subdivs};                                                                                  \
+    return abi_rc(surfel_call<T>(c, &sf, nullptr, ray_o, o_rows, ray_d, n_rays, ray_near, ray_far, out_pid, out_t, flags, stream, st)); }            \
+int pcu_hip_surfel_index_create_##SUF(pcu_hip_ctx* c, const T* p, const T* n, const T* r, int64_t np, int subdivs, unsigned flags, void* stream,     \
+                                      pcu_hip_surfel_index** out) {                                                                                  \
+    CallGuard dg(c);                                                                                                                                 \
+    const int rc = abi_rc(surfel_index_create_impl<T>(c, p, n, r, np, subdivs, flags, stream, out));                                                 \
+    if (rc && out && *out) { DeviceGuard g(c->device); (void)hipDeviceSynchronize(); surfel_index_free(*out); *out = nullptr; }                      \
+    return rc; }                                                                                                                                     \
+int pcu_hip_surfel_index_rays_##SUF(pcu_hip_ctx* c, const pcu_hip_surfel_index* ix, const T* ray_o, int64_t o_rows, const T* ray_d, int64_t n_rays,  \
+                                    double ray_near, double ray_far, int64_t* out_pid, T* out_t, unsigned flags, void* stream, pcu_hip_stats* st) { \
+    CallGuard dg(c);                                                                                                                                 \
+    return abi_rc(surfel_call<T>(c, nullptr, ix, ray_o, o_rows, ray_d, n_rays, ray_near, ray_far, out_pid, out_t, flags, stream, st)); }
+PCU_SURFEL(f32, float) PCU_SURFEL(f64, double)
+#undef PCU_SURFEL
+int64_t pcu_hip_surfel_index_size(const pcu_hip_surfel_index* ix) { return ix ? ix->np : 0; }
+void pcu_hip_surfel_index_destroy(pcu_hip_surfel_index* ix) {
+    if (!ix) return;
+    DeviceGuard dg(ix->device);
+    (void)hipDeviceSynchronize();
+    surfel_index_free(ix);
 }
 int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }
 void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) {

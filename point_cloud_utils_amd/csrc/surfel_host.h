@@ -1,0 +1,215 @@
+// csrc/surfel_host.h -- host orchestration of ray_surfel_intersection, RaySurfelIntersector and pointcloud_surfel_geometry (kernels and
+// contract: surfel.h). The surfel tree is a MeshIdx whose elements are points (rows (p, A, B)); the rays go through mesh_run like the mesh's.
+// Included by pcu_hip.hip after pc_winding_host.h.
+#pragma once
+
+// An oriented point cloud with radii kept on the GPU as its surfel tree (pcu_hip_surfel_index_*): one block owned by the object.
+struct pcu_hip_surfel_index {
+    int elem_size = 0;            // 4: float, 8: double
+    int device = 0;
+    int64_t np = 0;
+    int subdivs = 0;
+    void* mem = nullptr;
+    const void* table = nullptr;  // (subdivs, 2): cos, sin in the scalar type, inside mem
+    MeshIdx<float> m32; MeshIdx<double> m64;
+};
+template <typename T> static const MeshIdx<T>& surfel_idx(const pcu_hip_surfel_index* p);
+template <> const MeshIdx<float>& surfel_idx<float>(const pcu_hip_surfel_index* p) { return p->m32; }
+template <> const MeshIdx<double>& surfel_idx<double>(const pcu_hip_surfel_index* p) { return p->m64; }
+static void surfel_index_free(pcu_hip_surfel_index* p) {
+    if (!p) return;
+    if (p->mem) (void)hipFree(p->mem);
+    delete p;
+}
+static int surfel_leaves_pow2(int64_t np) {
+    const int64_t leaves = (np + kSurfelLeaf - 1) / kSurfelLeaf;
+    int P = 1;
+    while (P < leaves) P <<= 1;
+    return P;
+}
+template <typename T> static size_t surfel_table_bytes(int subdivs) { return align_up((size_t)subdivs * 2 * sizeof(T), 256); }
+// head, table, 9 T and a row per point, a box per node
+template <typename T>
+static size_t surfel_index_bytes(int64_t np, int subdivs) {
+    const size_t N = (size_t)np, P = (size_t)surfel_leaves_pow2(np);
+    return align_up(sizeof(MeshHead<T>), 256) + surfel_table_bytes<T>(subdivs) + align_up(N * 9 * sizeof(T), 256) + align_up(N * 4, 256) +
+           align_up(2 * P * 6 * sizeof(T), 256) + 1024;
+}
+// the sort and, for host arrays, p, n and r staged
+template <typename T>
+static size_t surfel_build_bytes(int64_t np, bool on_dev) {
+    size_t b = mesh_sort_bytes(np) + 4096;
+    if (!on_dev) b += 2 * align_up((size_t)np * 3 * sizeof(T), 256) + align_up((size_t)np * sizeof(T), 256);
+    return b;
+}
+static int surfel_validate(int64_t np, int subdivs) {
+    if (subdivs < 4) return fail(PCU_HIP_ERR_INVALID, "Invalid geometry_subdivisions_1 is less than or equal to 4.");     // (the reference's text)
+    if (np < 0) return fail(PCU_HIP_ERR_INVALID, "negative number of points");
+    return np > kMeshMaxRows ? mesh_row_limit() : 0;
+}
+static int surfel_refuse(int bad) {
+    if (bad & kSurfelBadP) return fail(PCU_HIP_ERR_INVALID, "p must not contain NaN or infinite coordinates");
+    if (bad & kSurfelBadN) return fail(PCU_HIP_ERR_INVALID, "n must not contain NaN or infinite coordinates");
+    if (bad & kSurfelBadR) return fail(PCU_HIP_ERR_INVALID, "r must not contain NaN or infinite values");
+    if (bad & kSurfelBadL) return fail(PCU_HIP_ERR_INVALID, "the length of a normal overflows the scalar type of p");
+    if (bad & kSurfelBadV) return fail(PCU_HIP_ERR_INVALID, "surfel vertices overflow the scalar type of p");
+    return 0;
+}
+// The table of the contract, rounded to T once. Waits for the copy: the host array goes with this function.
+template <typename T>
+static int surfel_table(Arena& ar, hipStream_t s, int subdivs, const T** out) {
+    std::vector<T> host((size_t)subdivs * 2);
+    for (int j = 0; j < subdivs; ++j) {
+        const double a = 6.283185307179586 * j / subdivs;
+        host[2 * (size_t)j] = (T)cos(a); host[2 * (size_t)j + 1] = (T)sin(a);
+    }
+    T* d = nullptr;
+    if (aalloc(ar, &d, host.size())) return -1;
+    HIP_TRY(hipMemcpyAsync(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    HIP_WAIT(s);
+    *out = d;
+    return 0;
+}
+
+// Enqueues the build on s and waits once (the validity flags). `ari` gives the buffers of the index, `ar` the temporaries.
+template <typename T>
+static int surfel_build(Arena& ari, Arena& ar, hipStream_t s, const T* p, const T* n, const T* r, int64_t np, int subdivs, bool on_dev, MeshIdx<T>& M,
+                        const T** table) {
+    const T *dp = nullptr, *dn = nullptr, *dr = nullptr;
+    if (stage_in(ar, p, np, on_dev, s, &dp) || stage_in(ar, n, np, on_dev, s, &dn) || stage_any(ar, r, (size_t)np, on_dev, s, &dr)) return -1;
+    M.nf = (int)np; M.P = surfel_leaves_pow2(np);
+    unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
+    if (aalloc(ari, &M.head, 1) || surfel_table<T>(ari, s, subdivs, table) || aalloc(ari, &M.tri, (size_t)np * 9) || aalloc(ari, &M.face, (size_t)np) ||
+        aalloc(ari, &M.box, (size_t)M.P * 12) ||
+        aalloc(ar, &ka, (size_t)np) || aalloc(ar, &kb, (size_t)np) || aalloc(ar, &ia, (size_t)np) || aalloc(ar, &ib, (size_t)np)) return -1;
+    const int nbp = (int)((np + kBlock - 1) / kBlock), nbl = (M.P + kBlock - 1) / kBlock;
+    int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
+    hipLaunchKernelGGL(k_mesh_head_init<T>, dim3(1), dim3(64), 0, s, M.head);
+    if (np > 0) hipLaunchKernelGGL(k_surfel_check<T>, dim3(nbp), dim3(kBlock), 0, s, dp, dn, dr, (int)np, subdivs, *table, M.head);
+    else hipLaunchKernelGGL(k_surfel_head_empty<T>, dim3(1), dim3(64), 0, s, M.head);
+    hipLaunchKernelGGL(k_mesh_frame<T>, dim3(1), dim3(64), 0, s, M.head);
+    HIP_TRY(hipGetLastError());
+    if (np > 0) {
+        hipLaunchKernelGGL(k_pc_codes<T>, dim3(nbp), dim3(kBlock), 0, s, dp, (int)np, (const MeshHead<T>*)M.head, ka);
+        HIP_TRY(hipGetLastError());
+        if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)np, 63)) return -1;
+        hipLaunchKernelGGL(k_surfel_gather<T>, dim3(nbp), dim3(kBlock), 0, s, dp, dn, dr, (const unsigned*)ia, (int)np, M.tri, M.face);
+    }
+    hipLaunchKernelGGL(k_surfel_leaves<T>, dim3(nbl), dim3(kBlock), 0, s, (const T*)M.tri, (int)np, M.P, subdivs, *table, (const MeshHead<T>*)M.head, M.box);
+    for (int m = M.P / 2; m >= 1; m /= 2) hipLaunchKernelGGL(k_mesh_refit<T>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, M.box, m);
+    HIP_TRY(hipGetLastError());
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_WAIT(s);
+    return surfel_refuse(bad);
+}
+
+template <typename T>
+struct SurfelRaysOp : MeshRaysOp<T> {           // ray_surfel_intersection (src/ray_point_cloud_intersection.cpp:343-384): a point id and t per row
+    const T* table; int subdivs;
+    using Params = SurfelRays<T>;
+    static constexpr int kRows3 = 2;
+    static constexpr bool kBary = false;
+    void walk(hipStream_t s, SurfelRays<T> a, T* val, int64_t n) const {
+        a.o = this->o; a.o_stride = this->o_stride(n); a.d = this->d; a.n = (int)n; a.near = (T)this->ray_near; a.far = (T)this->ray_far; a.out_t = val;
+        a.table = table; a.subdivs = subdivs;
+        hipLaunchKernelGGL(k_surfel_rays<T>, dim3((unsigned)((n + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0, s, a);
+    }
+};
+
+// One call. Cloud given (`sf`): tree, rows and temporaries in the call's arena; index given (`ix`): rows and temporaries.
+template <typename T> struct SurfelGiven { const T* p; const T* n; const T* r; int64_t np; int subdivs; };
+template <typename T>
+static int surfel_call(pcu_hip_ctx* c, const SurfelGiven<T>* sf, const pcu_hip_surfel_index* ix, const T* ray_o, int64_t o_rows, const T* ray_d, int64_t n,
+                       double ray_near, double ray_far, int64_t* out_pid, T* out_t, unsigned flags, void* stream, pcu_hip_stats* st) {
+    if (sf ? !c : (!c || !ix)) return fail(PCU_HIP_ERR_INVALID, sf ? "null context" : "null context / surfel index");
+    if (st) memset(st, 0, sizeof *st);
+    if (!sf) {
+        if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the surfel index was built for the other scalar type");
+        if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the surfel index lives on another device than the context");
+    }
+    SurfelRaysOp<T> op{{ray_o, o_rows, ray_d, ray_near, ray_far}, sf ? nullptr : static_cast<const T*>(ix->table), sf ? sf->subdivs : ix->subdivs};
+    if (sf) { if (int rc = surfel_validate(sf->np, sf->subdivs)) return rc; }
+    if (int rc = op.validate(n)) return rc;
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
+    hipStream_t s = pick_stream(c, flags, stream);
+    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
+    size_t bytes = mesh_run_bytes<T>(n, SurfelRaysOp<T>::kRows3, on_dev);
+    if (sf) bytes += surfel_index_bytes<T>(sf->np, sf->subdivs) + surfel_build_bytes<T>(sf->np, on_dev);
+    if (ctx_begin(c, bytes)) return PCU_HIP_ERR_RUNTIME;
+    Arena ar{c};
+    Timer tm{c, s, st};
+    MeshIdx<T> built;
+    int rc = 0;
+    if (sf) { tm.mark(0); rc = surfel_build<T>(ar, ar, s, sf->p, sf->n, sf->r, sf->np, sf->subdivs, on_dev, built, &op.table); }
+    if (!rc) rc = mesh_run<T>(ar, s, sf ? built : surfel_idx<T>(ix), op, n, on_dev, out_t, out_pid, nullptr, tm);
+    if (!rc) mesh_stats(st, tm, n, sf != nullptr);
+    return attempt_exit(c, rc);
+}
+
+template <typename T>
+static int surfel_index_create_impl(pcu_hip_ctx* c, const T* p, const T* n, const T* r, int64_t np, int subdivs, unsigned flags, void* stream,
+                                    pcu_hip_surfel_index** out) {
+    if (!c || !out) return fail(PCU_HIP_ERR_INVALID, "null context / output");
+    *out = nullptr;
+    if (int rc = surfel_validate(np, subdivs)) return rc;
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
+    hipStream_t s = pick_stream(c, flags, stream);
+    pcu_hip_surfel_index* h = new pcu_hip_surfel_index();
+    h->elem_size = (int)sizeof(T); h->device = c->device; h->np = np; h->subdivs = subdivs;
+    const size_t bytes = surfel_index_bytes<T>(np, subdivs);
+    if (hipMalloc(&h->mem, bytes) != hipSuccess) { h->mem = nullptr; surfel_index_free(h); return fail(PCU_HIP_ERR_RUNTIME, "out of device memory for the surfel index"); }
+    if (ctx_begin(c, surfel_build_bytes<T>(np, on_dev))) { surfel_index_free(h); return PCU_HIP_ERR_RUNTIME; }
+    ArenaState blk;                                 // a bump allocator over the index's own block
+    blk.base = static_cast<char*>(h->mem); blk.cap = bytes;
+    Arena ari{&blk}, ar{c};
+    const T* table = nullptr;
+    int rc = surfel_build<T>(ari, ar, s, p, n, r, np, subdivs, on_dev, const_cast<MeshIdx<T>&>(surfel_idx<T>(h)), &table);
+    h->table = table;
+    if (!rc) rc = wait_stream(s);                   // (the temporaries go back to the context with this call)
+    rc = attempt_exit(c, index_block_exit(blk, rc, "surfel index"));
+    if (rc) { (void)hipStreamSynchronize(s); surfel_index_free(h); return rc; }
+    *out = h;
+    return 0;
+}
+
+// pointcloud_surfel_geometry (src/ray_point_cloud_intersection.cpp:321-340): (np (subdivs + 1), 3) vertices in T, (np subdivs, 3) int32 faces
+template <typename T>
+static int surfel_geometry_impl(pcu_hip_ctx* c, const T* p, const T* n, const T* r, int64_t np, int subdivs, T* out_v, int32_t* out_f, unsigned flags,
+                                void* stream, pcu_hip_stats* st) {
+    if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
+    if (st) memset(st, 0, sizeof *st);
+    if (int rc = surfel_validate(np, subdivs)) return rc;
+    if (np * ((int64_t)subdivs + 1) > 0x7fffffffll)
+        return fail(PCU_HIP_ERR_INVALID, "surfel geometry with more than 2^31-1 vertices does not fit the int32 faces");
+    if (np == 0) return 0;
+    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
+    hipStream_t s = pick_stream(c, flags, stream);
+    const size_t nv = (size_t)np * ((size_t)subdivs + 1), nf = (size_t)np * (size_t)subdivs;
+    size_t bytes = surfel_table_bytes<T>(subdivs) + 4096;
+    if (!on_dev) bytes += surfel_build_bytes<T>(np, false) + align_up(nv * 3 * sizeof(T), 256) + align_up(nf * 12, 256);
+    c->time_phases = false; c->time_kernels = false;
+    if (ctx_begin(c, bytes)) return PCU_HIP_ERR_RUNTIME;
+    Arena ar{c};
+    auto run = [&]() -> int {
+        const T *dp = nullptr, *dn = nullptr, *dr = nullptr, *table = nullptr;
+        if (stage_in(ar, p, np, on_dev, s, &dp) || stage_in(ar, n, np, on_dev, s, &dn) || stage_any(ar, r, (size_t)np, on_dev, s, &dr) ||
+            surfel_table<T>(ar, s, subdivs, &table)) return -1;
+        T* d_v = out_v; int* d_f = out_f; int* d_bad = nullptr;
+        if (aalloc(ar, &d_bad, 1) || (!on_dev && (aalloc(ar, &d_v, nv * 3) || aalloc(ar, &d_f, nf * 3)))) return -1;
+        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_surfel_geometry<T>, dim3((unsigned)((np + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, dp, dn, dr, (int)np, subdivs, table, d_v, d_f, d_bad);
+        HIP_TRY(hipGetLastError());
+        int bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+        if (!on_dev) {
+            HIP_TRY(hipMemcpyAsync(out_v, d_v, nv * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(out_f, d_f, nf * 12, hipMemcpyDeviceToHost, s));
+        }
+        HIP_WAIT(s);
+        if (int rc = surfel_refuse(bad)) return rc;
+        if (st) { st->n_queries = np; st->n_passes = 1; }
+        return 0;
+    };
+    return attempt_exit(c, run());
+}
