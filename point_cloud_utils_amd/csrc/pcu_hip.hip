@@ -2287,11 +2287,12 @@ static int batch_run(pcu_hip_ctx* c, int n_pairs, unsigned flags, void* stream, 
         if (cur[lane] >= 0) {
             Outcome out = Outcome::Clean;
             int r = end(c->lanes[lane], pend[lane], cur[lane], out);
-            for (int restarts = 1; out == Outcome::Restart; ++restarts) {         // occupancy rescale: the lane's context has a new scale
+            // (a restart -- occupancy rescale, stale handed-down layout: the lane's context has changed -- reports into the lane's own statistics, as
+            // with_restarts does for a single call: pair_begin keeps the builds of the abandoned attempts, the attempt that ends the pair sets the rest)
+            for (int restarts = 1; out == Outcome::Restart; ++restarts) {
                 pend[lane] = PendingPair<T>(); pend[lane].restarts = restarts;
-                pcu_hip_stats again;
                 out = Outcome::Clean;
-                r = begin(c->lanes[lane], pend[lane], cur[lane], lflags, &again);
+                r = begin(c->lanes[lane], pend[lane], cur[lane], lflags, &lst[lane]);
                 if (!r) r = end(c->lanes[lane], pend[lane], cur[lane], out);
             }
             if (r && !rc) { rc = r; err = g_err; }
