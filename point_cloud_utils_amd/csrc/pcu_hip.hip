@@ -41,6 +41,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "mesh_sample.h"
 #include "pc_winding.h"
 #include "surfel.h"
+#include "voxelize.h"
 
 using namespace pcu;
 
@@ -250,6 +251,7 @@ struct pcu_hip_ctx {
                                                                  // fill_parity -- left zeroed by its predecessor -- and zeroes the other one for its successor
     char* aux = nullptr; size_t aux_cap = 0;  // grow-only block for operators that run a search as a sub-step (normals): survives the
                                               // sub-call's use of the arena
+    int64_t vox_rows = -1;                    // rows of a voxelization parked in `aux` for pcu_hip_voxelize_take (voxelize_host.h); -1: none
     // grid2.h: GridGeo -- the layout of this context's last two-sided fused build, per cloud, on the device; what it was computed for, on the host
     struct GeoCache { char* dev = nullptr; bool valid[2] = {false, false}; int n[2] = {0, 0}; double occ = 0, h_want = 0; int max_cells = 0, n_layout = 0, tsize = 0; bool shared = false; } geo;
     unsigned cancel_epoch = 0;                // g_cancel_epoch at this context's last call (ctx_begin: reset of the cross-call device state after an abandoned call)
@@ -2135,6 +2137,7 @@ static int chamfer_impl(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int6
 
 // ------------------------------------------------------------------------------------------------ normals
 static int aux_reserve(pcu_hip_ctx* c, size_t bytes) {
+    c->vox_rows = -1;                           // (whatever was parked in the block goes with its new use)
     if (bytes > c->aux_cap) {
         if (c->aux) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->aux)); c->aux = nullptr; c->aux_cap = 0; }
         const size_t cap = align_up(bytes + (bytes >> 3), 1 << 20);
@@ -2385,6 +2388,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "mesh_sample_host.h"
 #include "pc_winding_host.h"
 #include "surfel_host.h"
+#include "voxelize_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2723,6 +2727,20 @@ void pcu_hip_surfel_index_destroy(pcu_hip_surfel_index* ix) {
     (void)hipDeviceSynchronize();
     surfel_index_free(ix);
 }
+// voxelize_triangle_mesh, sparse_voxel_grid_boundary and voxel_grid_geometry (voxelize.h, voxelize_host.h)
+#define PCU_VOXELIZE(SUF, T)                                                                                                                          \
+int pcu_hip_voxelize_triangle_mesh_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const double* voxel_size,    \
+                                         const double* voxel_origin, int64_t* out_rows, unsigned flags, void* stream, pcu_hip_stats* st) {           \
+    CallGuard dg(c); return abi_rc(voxelize_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, voxel_size, voxel_origin, out_rows, flags, stream, st)); }
+PCU_VOXELIZE(f32, float) PCU_VOXELIZE(f64, double)
+#undef PCU_VOXELIZE
+int pcu_hip_voxelize_take(pcu_hip_ctx* c, int64_t rows, int32_t* out_ijk, unsigned flags, void* stream) {
+    CallGuard dg(c); return abi_rc(voxelize_take_impl(c, rows, out_ijk, flags, stream)); }
+int pcu_hip_sparse_voxel_grid_boundary(pcu_hip_ctx* c, const void* ijk, int64_t n, int kind, int64_t* out_idx, int64_t* out_count, unsigned flags, void* stream) {
+    CallGuard dg(c); return abi_rc(voxel_boundary_impl(c, ijk, n, kind, out_idx, out_count, flags, stream)); }
+int pcu_hip_voxel_grid_geometry(pcu_hip_ctx* c, const void* ijk, int64_t n, int kind, const double* voxel_size, const double* voxel_origin, double gap_fraction,
+                                float* out_v, int32_t* out_f, unsigned flags, void* stream) {
+    CallGuard dg(c); return abi_rc(voxel_geometry_impl(c, ijk, n, kind, voxel_size, voxel_origin, gap_fraction, out_v, out_f, flags, stream)); }
 int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }
 void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) {
     if (!ix) return;
