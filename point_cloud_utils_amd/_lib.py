@@ -44,7 +44,8 @@ _COMPUTE_ENTRY_POINTS = [f"pcu_hip_{op}_{suf}" for suf in ("f32", "f64") for op 
     "point_cloud_fast_winding_number", "pc_winding_index_create", "pc_winding_index_query", "estimate_mesh_face_normals",
     "surfel_geometry", "surfel_rays", "surfel_index_create", "surfel_index_rays", "voxelize_triangle_mesh")] + [
     "pcu_hip_morton_encode", "pcu_hip_morton_decode", "pcu_hip_morton_addsub", "pcu_hip_morton_knn",
-    "pcu_hip_voxelize_take", "pcu_hip_sparse_voxel_grid_boundary", "pcu_hip_voxel_grid_geometry"] + [
+    "pcu_hip_voxelize_take", "pcu_hip_sparse_voxel_grid_boundary", "pcu_hip_voxel_grid_geometry",
+    "pcu_hip_connected_components", "pcu_hip_flood_fill_3d"] + [
     f"pcu_hip_voxel_downsample_{sp}_{sa}" for sp in ("f32", "f64") for sa in ("f32", "f64")]
 
 
@@ -147,6 +148,8 @@ def lib():
         L.pcu_hip_voxelize_take.argtypes = [vp, i64, vp, u, vp]
         L.pcu_hip_sparse_voxel_grid_boundary.argtypes = [vp, vp, i64, ci, vp, vp, u, vp]
         L.pcu_hip_voxel_grid_geometry.argtypes = [vp, vp, i64, ci, vp, vp, ctypes.c_double, vp, vp, u, vp]
+        L.pcu_hip_connected_components.argtypes = [vp, vp, i64, ci, i64, vp, vp, vp, vp, vp, u, vp, vp]
+        L.pcu_hip_flood_fill_3d.argtypes = [vp, vp, vp, i64, i64, i64, vp, ci, ctypes.c_double, vp, u, vp, vp]
         for sp in ("f32", "f64"):
             getattr(L, "pcu_hip_pairwise_" + sp).argtypes = [vp, vp, vp, i64, i64, i64, i64, ctypes.c_double, vp, u, vp]
             getattr(L, "pcu_hip_sinkhorn_" + sp).argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_double, ci, ctypes.c_double, vp, vp, u, vp]

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <chrono>
 #include <atomic>
@@ -42,6 +43,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "pc_winding.h"
 #include "surfel.h"
 #include "voxelize.h"
+#include "components.h"
 
 using namespace pcu;
 
@@ -2389,6 +2391,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "pc_winding_host.h"
 #include "surfel_host.h"
 #include "voxelize_host.h"
+#include "components_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2741,6 +2744,13 @@ int pcu_hip_sparse_voxel_grid_boundary(pcu_hip_ctx* c, const void* ijk, int64_t 
 int pcu_hip_voxel_grid_geometry(pcu_hip_ctx* c, const void* ijk, int64_t n, int kind, const double* voxel_size, const double* voxel_origin, double gap_fraction,
                                 float* out_v, int32_t* out_f, unsigned flags, void* stream) {
     CallGuard dg(c); return abi_rc(voxel_geometry_impl(c, ijk, n, kind, voxel_size, voxel_origin, gap_fraction, out_v, out_f, flags, stream)); }
+// connected_components and flood_fill_3d (components.h, components_host.h)
+int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
+                                 int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
+    CallGuard dg(c); return abi_rc(connected_components_impl(c, f, nf, f_kind, nv, out_cv, out_cf, out_nv, out_nf, out_count, flags, stream, st)); }
+int pcu_hip_flood_fill_3d(pcu_hip_ctx* c, const void* grid, void* out, int64_t sx, int64_t sy, int64_t sz, const int64_t* seed3, int kind, double fill_value,
+                          int64_t* out_filled, unsigned flags, void* stream, pcu_hip_stats* st) {
+    CallGuard dg(c); return abi_rc(flood_fill_impl(c, grid, out, sx, sy, sz, seed3, kind, fill_value, out_filled, flags, stream, st)); }
 int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }
 void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) {
     if (!ix) return;
