@@ -1,7 +1,8 @@
 """Plain numpy / Python restatements of the connected_components and flood_fill_3d contracts: what the GPU tests are held
 to, bit for bit. components() is the reference's loop (src/connected_components.cpp:11-66, :99-105) over an adjacency built from the faces;
 flood_fill() walks the grid from the seed, with true 6-connectivity by default and with the reference's offset arithmetic
-(src/flood_fill_3d.cpp:31-49) on request."""
+(src/flood_fill_3d.cpp:31-49) on request. components_fast() and flood_fill_fast() state the same two contracts over scipy's labelling, for
+inputs of millions of elements; tests/test_components_contract.py holds them to the plain ones."""
 import os
 from collections import deque
 
@@ -55,6 +56,24 @@ def components(nv, f):
     return cv, np.array(counts, dtype=np.int64), cf, np.bincount(cf, minlength=len(counts)).astype(np.int64)
 
 
+def components_fast(nv, f):
+    """components() for meshes of a million faces: scipy's labelling of the undirected graph of the edges (f0, f1) and (f1, f2) of every face (the
+    third edge joins nothing new), relabelled by rank of each component's smallest vertex."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    f = np.asarray(f).astype(np.int64).reshape(-1, 3)
+    src, dst = np.concatenate([f[:, 0], f[:, 1]]), np.concatenate([f[:, 1], f[:, 2]])
+    graph = coo_matrix((np.ones(src.size, dtype=np.int64), (src, dst)), shape=(nv, nv))     # (int64: a repeated edge sums, and must not wrap to 0)
+    count, label = connected_components(graph, directed=False)
+    smallest = np.full(count, nv, dtype=np.int64)
+    np.minimum.at(smallest, label, np.arange(nv, dtype=np.int64))
+    rank = np.empty(count, dtype=np.int64)
+    rank[np.argsort(smallest)] = np.arange(count, dtype=np.int64)
+    cv = rank[label]
+    cf = cv[f[:, 0]]
+    return cv, np.bincount(cv, minlength=count).astype(np.int64), cf, np.bincount(cf, minlength=count).astype(np.int64)
+
+
 def fill_scalar(fill_value, dtype):
     """float(fill_value) to double, then to the grid's dtype: the reference's `(npe_Scalar_grid) flood_value`."""
     return np.array(float(fill_value), dtype=np.float64).astype(dtype)[()]
@@ -92,3 +111,37 @@ def flood_fill(grid, seed, fill_value, reference_offsets=False):
         front = o
     flat[seen] = fill_scalar(fill_value, grid.dtype)
     return flat.reshape(w, h, d)
+
+
+def flood_fill_fast(grid, seed, fill_value):
+    """flood_fill() (true 6-connectivity) for grids of millions of cells: scipy's labelling of the cells that == the seed's value -- its default
+    structure is the six face neighbours --, and the fill value wherever the label is the seed's. A NaN seed equals nothing: no label, no change."""
+    from scipy import ndimage
+    grid = np.ascontiguousarray(grid)
+    seed = tuple(int(c) for c in seed)
+    if len(seed) != 3 or not all(0 <= c < s for c, s in zip(seed, grid.shape)):
+        raise ValueError("seed point must be inside grid")
+    out = grid.copy()
+    label, _ = ndimage.label(grid == grid[seed])
+    if label[seed] != 0:
+        out[label == label[seed]] = fill_scalar(fill_value, grid.dtype)
+    return out
+
+
+def serpentine(n):
+    """A corridor one cell wide through an n x n x n grid of walls (0), as one walk from (0, 0, 0): along z on every second y row of every
+    second x slab, back and forth, each row joined to the next at the end the walk arrives at, the y order reversed from slab to slab.
+    Returns (grid, first cell, number of corridor cells): the last cell is that many steps less one from the first."""
+    g = np.zeros((n, n, n), dtype=np.int32)
+    k = 0                                                          # rows walked so far: an even one runs towards +z
+    for xi, x in enumerate(range(0, n, 2)):
+        ys = list(range(0, n, 2))[::-1 if xi % 2 else 1]
+        for yi, y in enumerate(ys):
+            g[x, y, :] = 1
+            end = n - 1 if k % 2 == 0 else 0
+            k += 1
+            if yi + 1 < len(ys):
+                g[x, (y + ys[yi + 1]) // 2, end] = 1
+            elif x + 2 < n:
+                g[x + 1, y, end] = 1
+    return g, (0, 0, 0), int(g.sum())

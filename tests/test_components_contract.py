@@ -82,6 +82,118 @@ def test_the_fill_value_goes_through_double():
     assert cc.flood_fill(g.astype(np.int32), (0, 0, 0), 2.9).tolist() == [[[2, 2]]]
 
 
+# ---- the fast restatements (scipy's labelling) are held to the plain ones, on inputs small enough for the plain ones
+def same_components(nv, f):
+    want, got = cc.components(nv, f), cc.components_fast(nv, f)
+    for w, g, name in zip(want, got, ("cv", "nv", "cf", "nf")):
+        assert g.dtype == np.int64 and g.ndim == 1 and np.array_equal(g, w), name
+    return got
+
+
+@pytest.mark.parametrize("nv", [7, 300, 2000, 5000])
+def test_components_fast_on_random_face_soups(nv):
+    f = np.random.default_rng(nv).integers(0, nv, (max(nv // 2, 1), 3))
+    cv, cnv, cf, cnf = same_components(nv, f)
+    assert cnv.sum() == nv and cnf.sum() == len(f) and 1 < len(cnv) < nv
+
+
+def test_components_fast_on_the_rule_cases_and_the_doubled_bunny():
+    same_components(10, np.array([[7, 8, 9], [4, 6, 1], [5, 0, 5], [3, 4, 3]]))
+    same_components(5, np.array([[0, 1, 2], [2, 3, 4]]))
+    same_components(6, np.array([[3, 4, 5], [0, 1, 2]]))
+    v, f = cc.doubled(*cc.golden_mesh("bunny"))
+    rng = np.random.default_rng(2)
+    cv, cnv, cf, cnf = same_components(len(v), f)
+    assert cnv.tolist() == [len(v) // 2] * 2 and cnf.tolist() == [len(f) // 2] * 2
+    same_components(len(v), rng.permutation(len(v))[f][rng.permutation(len(f))])
+
+
+def test_components_fast_with_unreferenced_vertices_at_both_ends():
+    cv, cnv, cf, cnf = same_components(12, np.array([[2, 3, 4], [7, 8, 9], [4, 2, 3]]))
+    assert cv.tolist() == [0, 1, 2, 2, 2, 3, 4, 5, 5, 5, 6, 7] and cnf.tolist() == [0, 0, 2, 0, 0, 1, 0, 0]
+    same_components(7, np.array([[1, 2, 4]]))
+    f = np.random.default_rng(3).integers(40, 160, (50, 3))
+    cv, cnv, cf, cnf = same_components(200, f)
+    assert (cnv[:40] == 1).all() and (cnv[-40:] == 1).all() and (cnf[:40] == 0).all()
+
+
+def test_components_fast_with_repeated_indices_and_repeated_faces():
+    same_components(4, np.array([[1, 1, 3], [2, 2, 2], [0, 3, 0]]))
+    same_components(3, np.array([[0, 0, 0]]))
+    same_components(6, np.array([[4, 4, 5], [5, 4, 4], [1, 2, 1]]))
+    cv, cnv, cf, cnf = same_components(9, np.tile([[7, 8, 3]], (1000, 1)))        # one edge a thousand times: its weight must not wrap to none
+    assert cnv.tolist() == [1, 1, 1, 3, 1, 1, 1] and cnf.tolist() == [0, 0, 0, 1000, 0, 0, 0]
+
+
+def same_fill(grid, seed, fill):
+    before = grid.copy()
+    want, got = cc.flood_fill(grid, seed, fill), cc.flood_fill_fast(grid, seed, fill)
+    assert got.dtype == grid.dtype and got.shape == grid.shape and got is not grid
+    assert want.tobytes() == got.tobytes()                       # (bytes: signed zeros and NaNs included)
+    assert grid.tobytes() == before.tobytes()
+    return got
+
+
+def test_flood_fill_fast_on_the_grids_of_the_tests_above():
+    assert same_fill(WITNESS, (0, 0, 1), 7).tolist() == [[[1, 7], [0, 1]]]
+    for seed in ((0, 0, 0), (0, 1, 0), (0, 1, 1)):
+        same_fill(WITNESS, seed, 7)
+    g = (np.random.default_rng(11).random((9, 8, 7)) < 0.6).astype(np.int64)
+    g[:, :, 0] = 5
+    g[:, :, -1] = 5
+    for value in (0, 1, 5):
+        same_fill(g, tuple(int(c) for c in np.argwhere(g == value)[0]), -3)
+    g = np.arange(24, dtype=np.float32).reshape(2, 3, 4) % 3
+    assert np.array_equal(same_fill(g, (1, 1, 1), g[1, 1, 1]), g)
+    same_fill(g, (1, 1, 1), 8.5)
+    g = np.zeros((1, 1, 2), dtype=np.int64)
+    assert same_fill(g, (0, 0, 0), 2 ** 53 + 1).tolist() == [[[2 ** 53, 2 ** 53]]]
+    assert same_fill(g.astype(np.int32), (0, 0, 0), 2.9).tolist() == [[[2, 2]]]
+    with pytest.raises(ValueError, match="^seed point must be inside grid$"):
+        cc.flood_fill_fast(g, (0, 0, 2), 1)
+
+
+@pytest.mark.parametrize("p", [0.3, 0.5, 0.7])
+def test_flood_fill_fast_on_random_grids_seeded_in_both_values(p):
+    g = (np.random.default_rng(int(p * 10)).random((24, 24, 24)) < p).astype(np.int32)
+    rng = np.random.default_rng(1)
+    for value in (1, 0):
+        cells = np.argwhere(g == value)
+        for seed in (cells[0], cells[-1], cells[rng.integers(len(cells))]):
+            out = same_fill(g, seed.tolist(), 2)
+            assert 0 < (out == 2).sum() <= len(cells)
+
+
+@pytest.mark.parametrize("dtype", [np.int32, np.int64, np.float32, np.float64])
+def test_flood_fill_fast_in_every_dtype(dtype):
+    g = (np.random.default_rng(5).random((9, 10, 11)) < 0.7).astype(dtype) * 3
+    same_fill(g, np.argwhere(g == 3)[0].tolist(), -2)
+    same_fill(g, np.argwhere(g == 0)[0].tolist(), 2.75)         # (truncated towards zero for the integer types)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_flood_fill_fast_with_signed_zeros_and_a_nan_seed(dtype):
+    g = np.zeros((3, 4, 9), dtype=dtype)
+    g[:, :, ::3] = -0.0
+    g[1, 2, 4] = np.nan
+    g[2, :, :] = 1.0
+    out = same_fill(g, (0, 0, 0), 5.0)                           # -0.0 == 0.0: one region around the NaN
+    assert (out == 5.0).sum() == 2 * 4 * 9 - 1 and np.isnan(out[1, 2, 4])
+    out = same_fill(g, (0, 0, 1), 5.0)
+    assert (out == 5.0).sum() == 2 * 4 * 9 - 1
+    out = same_fill(g, (1, 2, 4), 5.0)                           # a NaN equals nothing: the copy comes back
+    assert out.tobytes() == g.tobytes()
+
+
+def test_the_serpentine_is_one_path():
+    g, seed, cells = cc.serpentine(9)
+    assert seed == (0, 0, 0) and cells == int(g.sum())
+    out = same_fill(g, seed, 2)
+    assert (out == 2).sum() == cells and not (out == 1).any()
+    g[4, 4, 4] = 0
+    assert 0 < (same_fill(g, seed, 2) == 2).sum() < cells
+
+
 # ---- host-side checks of the package: no GPU is touched
 @pytest.fixture(scope="module")
 def pcu():

@@ -1,5 +1,7 @@
 """GPU tests of connected_components: exact equality with the restatement of tests/components_contract.py on small meshes that
-exercise every path of the union-find -- one block and many, long chains and contended hooks, root scans across tiles, every face dtype."""
+take every path of the code -- one block and up to 45, permuted strips of 4,096 triangles, root scans across one tile boundary, every face
+dtype. Nothing here is contended: the largest launch is 45 workgroups. Hooks from every CU onto one word, and a million faces per call, are in
+tests/test_gpu_components_scale.py."""
 import functools
 
 import numpy as np

@@ -99,27 +99,8 @@ def test_a_uniform_grid_changes_every_cell(pcu):
     assert st["n_queries"] == 130 ** 3 and st["n_escalated"] == 130 ** 3
 
 
-def serpentine(n):
-    """A corridor one cell wide through an n x n x n grid of walls (0), as one walk from (0, 0, 0): along z on every second y row of every
-    second x slab, back and forth, each row joined to the next at the end the walk arrives at, the y order reversed from slab to slab.
-    Returns (grid, first cell, number of corridor cells): the last cell is that many steps less one from the first."""
-    g = np.zeros((n, n, n), dtype=np.int32)
-    k = 0                                                          # rows walked so far: an even one runs towards +z
-    for xi, x in enumerate(range(0, n, 2)):
-        ys = list(range(0, n, 2))[::-1 if xi % 2 else 1]
-        for yi, y in enumerate(ys):
-            g[x, y, :] = 1
-            end = n - 1 if k % 2 == 0 else 0
-            k += 1
-            if yi + 1 < len(ys):
-                g[x, (y + ys[yi + 1]) // 2, end] = 1
-            elif x + 2 < n:
-                g[x + 1, y, end] = 1
-    return g, (0, 0, 0), int(g.sum())
-
-
 def test_a_serpentine_corridor_takes_a_fixed_number_of_launches(pcu):
-    g, seed, cells = serpentine(33)
+    g, seed, cells = cc.serpentine(33)
     assert cells > 9000
     want = cc.flood_fill(g, seed, 2)
     assert (want == 2).sum() == cells and not (want == 1).any()          # one region: the corridor is connected end to end
