@@ -44,6 +44,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "surfel.h"
 #include "voxelize.h"
 #include "components.h"
+#include "marching_cubes.h"
 
 using namespace pcu;
 
@@ -254,6 +255,8 @@ struct pcu_hip_ctx {
     char* aux = nullptr; size_t aux_cap = 0;  // grow-only block for operators that run a search as a sub-step (normals): survives the
                                               // sub-call's use of the arena
     int64_t vox_rows = -1;                    // rows of a voxelization parked in `aux` for pcu_hip_voxelize_take (voxelize_host.h); -1: none
+    int64_t mc_nv = -1, mc_nf = -1; int mc_vsize = 0, mc_isize = 0;   // a surface parked there for pcu_hip_marching_cubes_take (marching_cubes_host.h)
+    int64_t hx_nv = -1, hx_k = -1; int hx_vsize = 0;                  // a hex mesh parked there for pcu_hip_sparse_voxel_grid_to_hex_mesh_take
     // grid2.h: GridGeo -- the layout of this context's last two-sided fused build, per cloud, on the device; what it was computed for, on the host
     struct GeoCache { char* dev = nullptr; bool valid[2] = {false, false}; int n[2] = {0, 0}; double occ = 0, h_want = 0; int max_cells = 0, n_layout = 0, tsize = 0; bool shared = false; } geo;
     unsigned cancel_epoch = 0;                // g_cancel_epoch at this context's last call (ctx_begin: reset of the cross-call device state after an abandoned call)
@@ -2140,6 +2143,7 @@ static int chamfer_impl(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int6
 // ------------------------------------------------------------------------------------------------ normals
 static int aux_reserve(pcu_hip_ctx* c, size_t bytes) {
     c->vox_rows = -1;                           // (whatever was parked in the block goes with its new use)
+    c->mc_nv = c->mc_nf = -1; c->hx_nv = c->hx_k = -1;
     if (bytes > c->aux_cap) {
         if (c->aux) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->aux)); c->aux = nullptr; c->aux_cap = 0; }
         const size_t cap = align_up(bytes + (bytes >> 3), 1 << 20);
@@ -2392,6 +2396,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "surfel_host.h"
 #include "voxelize_host.h"
 #include "components_host.h"
+#include "marching_cubes_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2744,6 +2749,21 @@ int pcu_hip_sparse_voxel_grid_boundary(pcu_hip_ctx* c, const void* ijk, int64_t 
 int pcu_hip_voxel_grid_geometry(pcu_hip_ctx* c, const void* ijk, int64_t n, int kind, const double* voxel_size, const double* voxel_origin, double gap_fraction,
                                 float* out_v, int32_t* out_f, unsigned flags, void* stream) {
     CallGuard dg(c); return abi_rc(voxel_geometry_impl(c, ijk, n, kind, voxel_size, voxel_origin, gap_fraction, out_v, out_f, flags, stream)); }
+// marching_cubes_sparse_voxel_grid and sparse_voxel_grid_to_hex_mesh (marching_cubes.h, marching_cubes_host.h)
+#define PCU_MC_ABI(SUF, T)                                                                                                                            \
+int pcu_hip_marching_cubes_##SUF(pcu_hip_ctx* c, const T* grid_scalars, const T* grid_coordinates, int64_t n, const void* cube_indices, int64_t m,   \
+                                 int kind, double isovalue, int64_t* out_counts, unsigned flags, void* stream, pcu_hip_stats* st) {                   \
+    CallGuard dg(c); return abi_rc(marching_cubes_impl<T>(c, grid_scalars, grid_coordinates, n, cube_indices, m, kind, isovalue, out_counts, flags, stream, st)); }
+PCU_MC_ABI(f32, float)
+PCU_MC_ABI(f64, double)
+#undef PCU_MC_ABI
+int pcu_hip_marching_cubes_take(pcu_hip_ctx* c, int64_t nv, int64_t nf, void* out_v, void* out_f, unsigned flags, void* stream) {
+    CallGuard dg(c); return abi_rc(marching_cubes_take_impl(c, nv, nf, out_v, out_f, flags, stream)); }
+int pcu_hip_sparse_voxel_grid_to_hex_mesh(pcu_hip_ctx* c, const void* ijk, int64_t k, int kind, const double* voxel_size, const double* origin, int out_f64,
+                                          int64_t* out_nv, unsigned flags, void* stream, pcu_hip_stats* st) {
+    CallGuard dg(c); return abi_rc(hex_mesh_impl(c, ijk, k, kind, voxel_size, origin, out_f64, out_nv, flags, stream, st)); }
+int pcu_hip_sparse_voxel_grid_to_hex_mesh_take(pcu_hip_ctx* c, int64_t nv, int64_t k, void* out_v, int64_t* out_cubes, unsigned flags, void* stream) {
+    CallGuard dg(c); return abi_rc(hex_mesh_take_impl(c, nv, k, out_v, out_cubes, flags, stream)); }
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
