@@ -45,6 +45,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "voxelize.h"
 #include "components.h"
 #include "marching_cubes.h"
+#include "mesh_smooth.h"
 
 using namespace pcu;
 
@@ -257,6 +258,7 @@ struct pcu_hip_ctx {
     int64_t vox_rows = -1;                    // rows of a voxelization parked in `aux` for pcu_hip_voxelize_take (voxelize_host.h); -1: none
     int64_t mc_nv = -1, mc_nf = -1; int mc_vsize = 0, mc_isize = 0;   // a surface parked there for pcu_hip_marching_cubes_take (marching_cubes_host.h)
     int64_t hx_nv = -1, hx_k = -1; int hx_vsize = 0;                  // a hex mesh parked there for pcu_hip_sparse_voxel_grid_to_hex_mesh_take
+    int64_t adj_nv = -1, adj_count = -1; int adj_isize = 0;           // a vertex adjacency parked there for pcu_hip_mesh_adjacency_take (mesh_smooth_host.h)
     // grid2.h: GridGeo -- the layout of this context's last two-sided fused build, per cloud, on the device; what it was computed for, on the host
     struct GeoCache { char* dev = nullptr; bool valid[2] = {false, false}; int n[2] = {0, 0}; double occ = 0, h_want = 0; int max_cells = 0, n_layout = 0, tsize = 0; bool shared = false; } geo;
     unsigned cancel_epoch = 0;                // g_cancel_epoch at this context's last call (ctx_begin: reset of the cross-call device state after an abandoned call)
@@ -2143,7 +2145,7 @@ static int chamfer_impl(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int6
 // ------------------------------------------------------------------------------------------------ normals
 static int aux_reserve(pcu_hip_ctx* c, size_t bytes) {
     c->vox_rows = -1;                           // (whatever was parked in the block goes with its new use)
-    c->mc_nv = c->mc_nf = -1; c->hx_nv = c->hx_k = -1;
+    c->mc_nv = c->mc_nf = -1; c->hx_nv = c->hx_k = -1; c->adj_nv = c->adj_count = -1;
     if (bytes > c->aux_cap) {
         if (c->aux) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->aux)); c->aux = nullptr; c->aux_cap = 0; }
         const size_t cap = align_up(bytes + (bytes >> 3), 1 << 20);
@@ -2397,6 +2399,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "voxelize_host.h"
 #include "components_host.h"
 #include "marching_cubes_host.h"
+#include "mesh_smooth_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2764,6 +2767,21 @@ int pcu_hip_sparse_voxel_grid_to_hex_mesh(pcu_hip_ctx* c, const void* ijk, int64
     CallGuard dg(c); return abi_rc(hex_mesh_impl(c, ijk, k, kind, voxel_size, origin, out_f64, out_nv, flags, stream, st)); }
 int pcu_hip_sparse_voxel_grid_to_hex_mesh_take(pcu_hip_ctx* c, int64_t nv, int64_t k, void* out_v, int64_t* out_cubes, unsigned flags, void* stream) {
     CallGuard dg(c); return abi_rc(hex_mesh_take_impl(c, nv, k, out_v, out_cubes, flags, stream)); }
+// mesh_vertex_adjacency, estimate_mesh_vertex_normals and laplacian_smooth_mesh (mesh_smooth.h, mesh_smooth_host.h)
+int pcu_hip_mesh_adjacency(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
+    CallGuard dg(c); return abi_rc(mesh_adjacency_impl(c, f, nf, f_kind, nv, out_count, flags, stream, st)); }
+int pcu_hip_mesh_adjacency_take(pcu_hip_ctx* c, int64_t nv, int64_t count, int64_t* out_offsets, void* out_neighbours, unsigned flags, void* stream) {
+    CallGuard dg(c); return abi_rc(mesh_adjacency_take_impl(c, nv, count, out_offsets, out_neighbours, flags, stream)); }
+#define PCU_MS_ABI(SUF, T)                                                                                                                            \
+int pcu_hip_mesh_vertex_normals_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, int weighting, T* out_n,        \
+                                      unsigned flags, void* stream, pcu_hip_stats* st) {                                                             \
+    CallGuard dg(c); return abi_rc(mesh_vertex_normals_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, weighting, out_n, flags, stream, st)); }       \
+int pcu_hip_laplacian_smooth_mesh_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, int num_iters,                \
+                                        double step_size, int use_cotan_weights, T* out_v, unsigned flags, void* stream, pcu_hip_stats* st) {        \
+    CallGuard dg(c); return abi_rc(laplacian_smooth_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, num_iters, step_size, use_cotan_weights, out_v, flags, stream, st)); }
+PCU_MS_ABI(f32, float)
+PCU_MS_ABI(f64, double)
+#undef PCU_MS_ABI
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
