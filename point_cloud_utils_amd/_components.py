@@ -6,21 +6,11 @@ import operator
 
 import numpy as np
 
-from ._mesh import _FACE_KINDS, _check_mesh, _face_dtype_name, _faces_for
-from ._voxelize import _int_out
+from ._call import _FACE_KINDS, _call, _int_out
+from ._mesh import _check_mesh, _face_dtype_name, _faces_for
 
 _MAX_CELLS = 2 ** 31 - 16
 _GRID_KINDS = {"int32": 0, "int64": 1, "float32": 2, "float64": 3}
-
-
-def _run(name, d, *args):
-    """An entry point without a scalar suffix: raises what it refuses, records its statistics."""
-    from . import _lib, _record, Stats
-    st = Stats()
-    rc = getattr(_lib.lib(), "pcu_hip_" + name)(d.ctx, *args, d.flags, d.stream, ctypes.addressof(st))
-    if rc:
-        _lib.check(rc)
-    _record(st)
 
 
 def connected_components(v, f):
@@ -61,8 +51,8 @@ def connected_components(v, f):
     name = _face_dtype_name(ff)
     cv, cf, cnv, cnf = (_int_out(d, (n,), np.dtype(name)) for n in (nv, nf, nv, nv))
     count = ctypes.c_int64(0)
-    _run("connected_components", d, _Dev.ptr(ff), nf, _FACE_KINDS[name], nv, _Dev.ptr(cv), _Dev.ptr(cf), _Dev.ptr(cnv), _Dev.ptr(cnf),
-         ctypes.addressof(count))
+    _call("connected_components", d, _Dev.ptr(ff), nf, _FACE_KINDS[name], nv, _Dev.ptr(cv), _Dev.ptr(cf), _Dev.ptr(cnv), _Dev.ptr(cnf),
+          ctypes.addressof(count), suffix=False)
     m = int(count.value)
     cnv, cnf = cnv[:m], cnf[:m]
     if nv > 2 * m:                                         # (do not keep #v rows alive behind a few counts)
@@ -140,5 +130,6 @@ def flood_fill_3d(grid, start_coord, fill_value):
         out = np.empty(sizes, dtype=grid.dtype)
     seed3 = (ctypes.c_int64 * 3)(*seed)
     filled = ctypes.c_int64(0)
-    _run("flood_fill_3d", d, d.pa, _Dev.ptr(out), sizes[0], sizes[1], sizes[2], ctypes.addressof(seed3), _GRID_KINDS[dn], fill, ctypes.addressof(filled))
+    _call("flood_fill_3d", d, d.pa, _Dev.ptr(out), sizes[0], sizes[1], sizes[2], ctypes.addressof(seed3), _GRID_KINDS[dn], fill, ctypes.addressof(filled),
+          suffix=False)
     return out

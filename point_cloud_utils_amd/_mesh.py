@@ -6,8 +6,9 @@ import ctypes
 
 import numpy as np
 
+from ._call import _FACE_KINDS, _call
+
 _MAX_ROWS = 2 ** 27 - 16
-_FACE_KINDS = {"int32": 0, "int64": 1, "uint32": 2, "uint64": 3}
 
 
 def _face_dtype_name(f):
@@ -117,16 +118,6 @@ def _finish(val, fi, bc, like, n, order):
         val, fi, bc = val.reshape(()), fi.reshape(()), bc.reshape(3)
     res = (val, fi, bc)
     return tuple(res[i] for i in order)
-
-
-def _call(name, d, *args):
-    """The library's `name` for the arrays `d` resolved: raises what it refuses, records its statistics."""
-    from . import _lib, _fn, _record, Stats
-    st = Stats()
-    rc = _fn(name, d.suffix)(d.ctx, *args, d.flags, d.stream, ctypes.addressof(st))
-    if rc:
-        _lib.check(rc)
-    _record(st)
 
 
 def closest_points_on_mesh(p, v, f):

@@ -8,7 +8,8 @@ import time
 
 import numpy as np
 
-from ._mesh import (_FACE_KINDS, _MAX_ROWS, _call, _check_mesh, _face_dtype_name, _faces_for, _host_mesh_checks)
+from ._call import _FACE_KINDS, _call
+from ._mesh import (_MAX_ROWS, _check_mesh, _face_dtype_name, _faces_for, _host_mesh_checks)
 
 _ROW_LIMIT = "meshes and point clouds with more than 2^27-16 rows are not supported"
 

@@ -7,10 +7,9 @@ import math
 
 import numpy as np
 
-from ._components import _run
-from ._mesh import _FACE_KINDS, _MAX_ROWS, _call, _check_mesh, _face_dtype_name, _faces_for
+from ._call import _FACE_KINDS, _call, _take
+from ._mesh import _MAX_ROWS, _check_mesh, _face_dtype_name, _faces_for
 from ._mesh_sample import _mesh_args, _resolve
-from ._voxelize import _int_out, _plain
 
 _WEIGHTINGS = {"uniform": 0, "area": 1, "angle": 2}
 
@@ -71,10 +70,9 @@ def mesh_vertex_adjacency(f, num_vertices=None):
     ff = _faces_for(d, f)
     name = _face_dtype_name(ff)
     count = ctypes.c_int64(0)
-    _run("mesh_adjacency", d, _Dev.ptr(ff), nf, _FACE_KINDS[name], nv, ctypes.addressof(count))
+    _call("mesh_adjacency", d, _Dev.ptr(ff), nf, _FACE_KINDS[name], nv, ctypes.addressof(count), suffix=False)
     ne = int(count.value)
-    offsets, neighbours = _int_out(d, (nv + 1,), np.int64), _int_out(d, (ne,), np.dtype(name))
-    _plain("mesh_adjacency_take", d.ctx, nv, ne, _Dev.ptr(offsets), _Dev.ptr(neighbours), d.flags, d.stream)
+    offsets, neighbours = _take("mesh_adjacency", d, [((nv + 1,), np.int64), ((ne,), np.dtype(name))], nv, ne)
     return offsets, neighbours
 
 

@@ -6,7 +6,8 @@ import ctypes
 
 import numpy as np
 
-from ._mesh import _call, _check_mesh, _check_rows, _scalar_rows
+from ._call import _call
+from ._mesh import _check_mesh, _check_rows, _scalar_rows
 from ._mesh_sample import _mesh_args, _resolve
 
 _SAME_DEVICE = "torch inputs must all be CUDA/HIP tensors on the same device"

@@ -6,7 +6,8 @@ import ctypes
 
 import numpy as np
 
-from ._mesh import _call, _check_ray_limits, _check_rays, _check_rows, _host_ray_checks, _origins_for, _scalar_rows
+from ._call import _call
+from ._mesh import _check_ray_limits, _check_rays, _check_rows, _host_ray_checks, _origins_for, _scalar_rows
 from ._pc_winding import _beside, _host_finite, _match
 
 _INT32_MAX = 2 ** 31 - 1

@@ -6,7 +6,8 @@ import ctypes
 
 import numpy as np
 
-from ._mesh import _FACE_KINDS, _call, _check_mesh
+from ._call import _FACE_KINDS, _call, _int_out, _plain, _take
+from ._mesh import _check_mesh
 from ._mesh_sample import _mesh_args, _resolve
 
 _RANGE = 2 ** 20                       # voxel coordinates live in [-2^20, 2^20): the 21 bits per axis of a 64-bit Morton code
@@ -60,21 +61,6 @@ def _check_ijk(ijk, name, zero_text, shape_text):
     return _FACE_KINDS[dn], sh[0]
 
 
-def _int_out(d, shape, np_dtype):
-    if d.torch:
-        import torch
-        return torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=d.tdev)
-    return np.empty(shape, dtype=np_dtype)
-
-
-def _plain(name, *args):
-    """An entry point without a scalar suffix and without statistics."""
-    from . import _lib
-    rc = getattr(_lib.lib(), "pcu_hip_" + name)(*args)
-    if rc:
-        _lib.check(rc)
-
-
 def voxelize_triangle_mesh(v, f, voxel_size, voxel_origin):
     """
     Return ijk coordinates of voxels which intersect the given mesh.
@@ -101,7 +87,6 @@ def voxelize_triangle_mesh(v, f, voxel_size, voxel_origin):
         that is not > 0 ("Invalid voxel size") or not finite; a candidate coordinate outside [-2**20, 2**20); more than 2**32 candidates in
         all (a chosen cap, so that one huge face on a fine grid cannot hold the GPU for minutes).
     """
-    from . import _Dev
     origin = _coord3d(voxel_origin)
     size = _number_or_coord3d(voxel_size)
     _check_mesh(v, f)
@@ -111,9 +96,7 @@ def voxelize_triangle_mesh(v, f, voxel_size, voxel_origin):
     rows = ctypes.c_int64(0)
     _call("voxelize_triangle_mesh", d, *_mesh_args(d, ff, nv, nf), ctypes.addressof(cs), ctypes.addressof(co), ctypes.addressof(rows))
     m = int(rows.value)
-    ijk = _int_out(d, (m, 3), np.int32)
-    _plain("voxelize_take", d.ctx, m, _Dev.ptr(ijk), d.flags, d.stream)
-    return ijk
+    return _take("voxelize", d, [((m, 3), np.int32)], m)[0]
 
 
 def sparse_voxel_grid_boundary(grid_coordinates):

@@ -1,5 +1,5 @@
 // csrc/components_host.h -- host orchestration of connected_components and flood_fill_3d (kernels and contract: components.h). Included by
-// pcu_hip.hip after mesh_sample_host.h (ms_begin, mesh_validate) and voxel_host.h (stage_any, the scan).
+// pcu_hip.hip after the operator frame (op_run, stage_any), voxel_host.h (the scan) and mesh_host.h (mesh_validate, int_kind_bytes).
 #pragma once
 
 static unsigned cc_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
@@ -13,15 +13,11 @@ static int connected_components_impl(pcu_hip_ctx* c, const void* f, int64_t nf, 
     if (int rc = mesh_validate(nv, nf, 0, f_kind)) return rc;
     if (!f || !out_cv || !out_cf || !out_nv || !out_nf) return fail(PCU_HIP_ERR_INVALID, "null f / out_cv / out_cf / out_nv / out_nf");
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    const size_t NV = (size_t)nv, NF = (size_t)nf, kb = (size_t)mesh_face_bytes(f_kind);
+    const size_t NV = (size_t)nv, NF = (size_t)nf, kb = (size_t)int_kind_bytes(f_kind);
     size_t bytes = 5 * align_up(NV * 4, 256) + align_up((NV / kScTile + 2) * 4, 256) + 8192;
     if (!on_dev) bytes += align_up(NF * 3 * kb, 256) + 3 * align_up(NV * kb, 256) + align_up(NF * kb, 256);
-    if (int rc = ms_begin(c, st, bytes)) return rc;
-    c->time_phases = flags & PCU_HIP_TIME_PHASES;
-    Arena ar{c};
-    Timer tm{c, s, st};             // marks 0-1: union, 1-2: flatten and rank, 3-4: labels and counts
-    auto run = [&]() -> int {
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: union, 1-2: flatten and rank, 3-4: labels and counts
         const char* d_f = nullptr;
         if (stage_any(ar, static_cast<const char*>(f), NF * 3 * kb, on_dev, s, &d_f)) return -1;
         unsigned *parent = nullptr, *flag = nullptr, *scan = nullptr, *cnt_v = nullptr, *cnt_f = nullptr; int* d_bad = nullptr;
@@ -65,8 +61,7 @@ static int connected_components_impl(pcu_hip_ctx* c, const void* f, int64_t nf, 
             st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_tie = tm.span(3, 4); st->ms_total = tm.span(0, 4);
         }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }
 
 // The fill value as the reference's `(npe_Scalar_grid) flood_value` gives it wherever that cast is defined; a double outside an integer
@@ -88,12 +83,9 @@ template <typename V>
 static int flood_fill_typed(pcu_hip_ctx* c, const void* grid, void* out, size_t N, unsigned h, unsigned d, unsigned seed, double fill_value, int64_t* out_filled,
                             unsigned flags, void* stream, pcu_hip_stats* st) {
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    if (int rc = ms_begin(c, st, align_up(N * 4, 256) + (on_dev ? 0 : 2 * align_up(N * sizeof(V), 256)) + 8192)) return rc;
-    c->time_phases = flags & PCU_HIP_TIME_PHASES;
-    Arena ar{c};
-    Timer tm{c, s, st};             // marks 0-1: runs and unions, 1-2: flatten, 2-3: the filled copy
-    auto run = [&]() -> int {
+    const size_t bytes = align_up(N * 4, 256) + (on_dev ? 0 : 2 * align_up(N * sizeof(V), 256)) + 8192;
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: runs and unions, 1-2: flatten, 2-3: the filled copy
         const V* d_in = nullptr; V* d_out = static_cast<V*>(out);
         if (stage_any(ar, static_cast<const V*>(grid), N, on_dev, s, &d_in) || (!on_dev && aalloc(ar, &d_out, N))) return -1;
         unsigned* parent = nullptr; unsigned long long* d_cnt = nullptr;
@@ -119,8 +111,7 @@ static int flood_fill_typed(pcu_hip_ctx* c, const void* grid, void* out, size_t 
             st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_tie = tm.span(2, 3); st->ms_total = tm.span(0, 3);
         }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }
 static int flood_fill_impl(pcu_hip_ctx* c, const void* grid, void* out, int64_t sx, int64_t sy, int64_t sz, const int64_t* seed3, int kind, double fill_value,
                            int64_t* out_filled, unsigned flags, void* stream, pcu_hip_stats* st) {

@@ -1,6 +1,6 @@
 // csrc/mesh_host.h -- host orchestration of closest_points_on_mesh, ray_mesh_intersection (kernels, contracts and index layout: mesh.h),
-// triangle_soup_fast_winding_number and signed_distance_to_mesh (mesh_winding.h). Included by pcu_hip.hip after the arena, staging and
-// radix-sort helpers.
+// triangle_soup_fast_winding_number and signed_distance_to_mesh (mesh_winding.h). Included by pcu_hip.hip after the operator frame (op_run,
+// stage_any) and voxel_host.h (sort_bytes, the radix sort).
 #pragma once
 
 // A mesh kept on the GPU as its search index (pcu_hip_mesh_index_*): one block owned by the object, not by a call's arena.
@@ -26,10 +26,6 @@ static int mesh_leaves_pow2(int64_t nf) {
     while (P < leaves) P <<= 1;
     return P;
 }
-static size_t mesh_sort_bytes(int64_t n) {
-    const size_t N = (size_t)n, nwt = (N + kRsWaveTile - 1) / kRsWaveTile;
-    return 2 * align_up(N * 8, 256) + 2 * align_up(N * 4, 256) + align_up(256 * nwt * 4, 256) + 1024;
-}
 // `moments`: with the centres, radii and moments of mesh_winding.h (34 more T per node, about 17 per face)
 template <typename T>
 static size_t mesh_index_bytes(int64_t nf, bool moments) {
@@ -38,18 +34,22 @@ static size_t mesh_index_bytes(int64_t nf, bool moments) {
     if (moments) b += align_up(2 * P * 4 * sizeof(T), 256) + align_up(2 * P * 30 * sizeof(T), 256);
     return b;
 }
-static int mesh_face_bytes(int f_kind) { return (f_kind == 0 || f_kind == 2) ? 4 : 8; }
+// the integer types of faces, cubes and grid coordinates: PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64
+static int int_kind_bytes(int kind) { return (kind == 0 || kind == 2) ? 4 : 8; }
+static int int_kind_check(int kind) {
+    return (kind < 0 || kind > 3) ? fail(PCU_HIP_ERR_INVALID, "kind must be one of PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64") : 0;
+}
 template <typename T>
 static size_t mesh_build_bytes(int64_t nv, int64_t nf, int f_kind, bool on_dev, bool moments) {
-    size_t b = mesh_sort_bytes(nf) + align_up((size_t)nf * 12, 256) + 4096;
+    size_t b = sort_bytes((size_t)nf) + align_up((size_t)nf * 12, 256) + 4096;
     if (moments) b += align_up(2 * (size_t)mesh_leaves_pow2(nf) * sizeof(double), 256);      // (the nodes' areas)
-    if (!on_dev) b += align_up((size_t)nv * 3 * sizeof(T), 256) + align_up((size_t)nf * 3 * mesh_face_bytes(f_kind), 256);
+    if (!on_dev) b += align_up((size_t)nv * 3 * sizeof(T), 256) + align_up((size_t)nf * 3 * int_kind_bytes(f_kind), 256);
     return b;
 }
 // the query phase: the sort, the result staging of host output and rows3 staged (n,3) arrays (inputs and barycentrics)
 template <typename T>
 static size_t mesh_run_bytes(int64_t n, int rows3, bool on_dev) {
-    size_t b = mesh_sort_bytes(n) + 4096;
+    size_t b = sort_bytes((size_t)n) + 4096;
     if (!on_dev) b += rows3 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n * sizeof(T), 256) + align_up((size_t)n * 8, 256);
     return b;
 }
@@ -72,7 +72,7 @@ template <typename T>
 static int mesh_build(Arena& ari, Arena& ar, hipStream_t s, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, bool on_dev, bool moments,
                       MeshIdx<T>& M) {
     const T* dv = nullptr; const char* df = nullptr;
-    if (stage_in(ar, v, nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(f), (size_t)nf * 3 * mesh_face_bytes(f_kind), on_dev, s, &df)) return -1;
+    if (stage_in(ar, v, nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(f), (size_t)nf * 3 * int_kind_bytes(f_kind), on_dev, s, &df)) return -1;
     M.nf = (int)nf; M.P = mesh_leaves_pow2(nf);
     int* fidx = nullptr;
     if (aalloc(ari, &M.head, 1) || aalloc(ari, &M.tri, (size_t)nf * 9) || aalloc(ari, &M.face, (size_t)nf) || aalloc(ari, &M.box, (size_t)M.P * 12) ||
@@ -247,19 +247,16 @@ static int mesh_call(pcu_hip_ctx* c, const MeshGiven<T>* mesh, const pcu_hip_mes
     if (mesh) { if (int rc = mesh_validate(mesh->nv, mesh->nf, n, mesh->f_kind)) return rc; }
     else if (n < 0 || n > kMeshMaxRows) return mesh_row_limit();
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
     size_t bytes = mesh_run_bytes<T>(n, Op::kRows3, on_dev);
     if (mesh) bytes += mesh_index_bytes<T>(mesh->nf, Op::kMoments) + mesh_build_bytes<T>(mesh->nv, mesh->nf, mesh->f_kind, on_dev, Op::kMoments);
-    if (ctx_begin(c, bytes)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    Timer tm{c, s, st};
-    MeshIdx<T> built;
-    int rc = 0;
-    if (mesh) { tm.mark(0); rc = mesh_build<T>(ar, ar, s, mesh->v, mesh->nv, mesh->f, mesh->nf, mesh->f_kind, on_dev, Op::kMoments, built); }
-    if (!rc) rc = mesh_run<T>(ar, s, mesh ? built : mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)), op, n, on_dev, out_val, out_fi, out_bc, tm);
-    if (!rc) mesh_stats(st, tm, n, mesh != nullptr);
-    return attempt_exit(c, rc);
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
+        MeshIdx<T> built;
+        if (mesh) { tm.mark(0); if (int rc = mesh_build<T>(ar, ar, s, mesh->v, mesh->nv, mesh->f, mesh->nf, mesh->f_kind, on_dev, Op::kMoments, built)) return rc; }
+        if (int rc = mesh_run<T>(ar, s, mesh ? built : mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)), op, n, on_dev, out_val, out_fi, out_bc, tm)) return rc;
+        mesh_stats(st, tm, n, mesh != nullptr);
+        return 0;
+    });
 }
 
 template <typename T>

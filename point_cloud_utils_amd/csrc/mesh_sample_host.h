@@ -1,5 +1,6 @@
 // csrc/mesh_sample_host.h -- host orchestration of mesh_face_areas, sample_mesh_random and sample_mesh_poisson_disk (kernels and contract:
-// mesh_sample.h; the greedy: poisson_host.h). Included by pcu_hip.hip after mesh_host.h.
+// mesh_sample.h; the greedy: poisson_host.h). Included by pcu_hip.hip after the operator frame, voxel_host.h (the scan), poisson_host.h and
+// mesh_host.h (mesh_validate, MeshGiven, int_kind_bytes).
 #pragma once
 
 // The mesh side of one call on the device: staged vertices, range-checked faces, areas, the scan of the weights.
@@ -13,7 +14,7 @@ template <typename T>
 static size_t ms_mesh_bytes(const MeshGiven<T>& m, bool on_dev) {
     const size_t NF = (size_t)m.nf;
     size_t b = align_up(NF * 12, 256) + align_up(NF * sizeof(T), 256) + 2 * align_up(NF * 8, 256) + align_up((NF / kScTile + 2) * 8, 256) + 8192;
-    if (!on_dev) b += align_up((size_t)m.nv * 3 * sizeof(T), 256) + align_up(NF * 3 * mesh_face_bytes(m.f_kind), 256);
+    if (!on_dev) b += align_up((size_t)m.nv * 3 * sizeof(T), 256) + align_up(NF * 3 * int_kind_bytes(m.f_kind), 256);
     return b;
 }
 // Enqueues staging and the checks of v and f (the range-checked faces, the flag word). No wait.
@@ -21,7 +22,7 @@ template <typename T>
 static int ms_mesh_stage(Arena& ar, hipStream_t s, const MeshGiven<T>& m, bool on_dev, MsMesh<T>& M) {
     const char* df = nullptr;
     if (stage_in(ar, m.v, m.nv, on_dev, s, &M.v) ||
-        stage_any(ar, static_cast<const char*>(m.f), (size_t)m.nf * 3 * mesh_face_bytes(m.f_kind), on_dev, s, &df)) return -1;
+        stage_any(ar, static_cast<const char*>(m.f), (size_t)m.nf * 3 * int_kind_bytes(m.f_kind), on_dev, s, &df)) return -1;
     M.nf = (int)m.nf;
     if (aalloc(ar, &M.head, 1) || aalloc(ar, &M.fidx, (size_t)m.nf * 3)) return -1;
     hipLaunchKernelGGL(k_mesh_head_init<T>, dim3(1), dim3(64), 0, s, M.head);
@@ -74,11 +75,6 @@ static int ms_mesh_refuse(const MsSeen<T>& h, int64_t nv, bool weights) {
     if (h.amax == (T)0) return fail(PCU_HIP_ERR_INVALID, "Mesh has zero area");
     return 0;
 }
-static int ms_begin(pcu_hip_ctx* c, pcu_hip_stats* st, size_t bytes) {
-    if (st) memset(st, 0, sizeof *st);
-    c->time_phases = false; c->time_kernels = false;
-    return ctx_begin(c, bytes) ? PCU_HIP_ERR_RUNTIME : 0;
-}
 
 // mesh_face_areas (src/face_areas.cpp:17-79)
 template <typename T>
@@ -86,10 +82,8 @@ static int mesh_face_areas_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, T* out_ar
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
     if (int rc = mesh_validate(m.nv, m.nf, 0, m.f_kind)) return rc;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    if (int rc = ms_begin(c, st, ms_mesh_bytes(m, on_dev))) return rc;
-    Arena ar{c};
-    auto run = [&]() -> int {
+    return op_run(c, flags, stream, st, ms_mesh_bytes(m, on_dev), [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         MsMesh<T> M; MsSeen<T> seen;
         if (ms_mesh_enqueue<T>(ar, s, m, on_dev, false, on_dev ? out_area : nullptr, M) || ms_mesh_readback(s, M, false, &seen)) return -1;
         if (!on_dev) HIP_TRY(hipMemcpyAsync(out_area, M.area, (size_t)m.nf * sizeof(T), hipMemcpyDeviceToHost, s));
@@ -97,8 +91,7 @@ static int mesh_face_areas_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, T* out_ar
         if (int rc = ms_mesh_refuse(seen, m.nv, false)) return rc;
         if (st) { st->n_queries = m.nf; st->n_passes = 1; }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }
 
 // sample_mesh_random (src/sample_mesh.cpp:91-115)
@@ -115,11 +108,9 @@ static int sample_mesh_random_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64_
     if (n <= 0) return fail(PCU_HIP_ERR_INVALID, "num_samples must be positive");
     if (n > kMeshMaxRows) return mesh_row_limit();
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t out_bytes = on_dev ? 0 : align_up((size_t)n * 8, 256) + align_up((size_t)n * 3 * sizeof(T), 256);
-    if (int rc = ms_begin(c, st, ms_mesh_bytes(m, on_dev) + out_bytes)) return rc;
-    Arena ar{c};
-    auto run = [&]() -> int {
+    return op_run(c, flags, stream, st, ms_mesh_bytes(m, on_dev) + out_bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         MsMesh<T> M; MsSeen<T> seen;
         if (ms_mesh_enqueue<T>(ar, s, m, on_dev, true, nullptr, M)) return -1;
         long long* d_fi = reinterpret_cast<long long*>(out_fi); T* d_bc = out_bc;
@@ -135,8 +126,7 @@ static int sample_mesh_random_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64_
         if (int rc = ms_mesh_refuse(seen, m.nv, true)) return rc;
         if (st) { st->n_queries = n; st->n_passes = 1; }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }
 
 // sample_mesh_poisson_disk (src/sample_mesh.cpp:34-75): N_c candidates of sample_mesh_random, their positions, the greedy of poisson.h over
@@ -163,16 +153,14 @@ static int sample_mesh_poisson_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64
     const bool by_radius = radius > 0.0;
     const int64_t target = by_radius ? 0 : num_samples;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     // the arena for the candidate count known here (without the radius' estimate: the caller's capacity stands in for it)
     const double guess = ms_candidates((double)of, num_samples, 0.0, 0.0, 0.0);
     const int64_t ng = std::max<int64_t>(guess <= (double)kMeshMaxRows ? (int64_t)guess : 0, std::min<int64_t>(std::max<int64_t>(capacity, 0), kMeshMaxRows));
     size_t bytes = ms_mesh_bytes(m, on_dev);
     if (out_fi) bytes += (on_dev ? 1 : 2) * (align_up((size_t)ng * 8, 256) + align_up((size_t)ng * 3 * sizeof(T), 256)) + align_up((size_t)ng * 3 * sizeof(T), 256) +
                          align_up((size_t)ng * 4, 256) + pd_body_bytes<T>(ng, target);
-    if (int rc = ms_begin(c, st, bytes)) return rc;
-    Arena ar{c};
-    auto run = [&]() -> int {
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         MsMesh<T> M; MsSeen<T> seen;
         if (ms_mesh_enqueue<T>(ar, s, m, on_dev, true, nullptr, M) || ms_mesh_readback(s, M, true, &seen)) return -1;
         HIP_WAIT(s);
@@ -207,6 +195,5 @@ static int sample_mesh_poisson_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64
         *out_count = cnt;
         if (st) { st->n_queries = nc; st->n_passes = R.rounds; st->n_grid_builds = R.radii; }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }

@@ -1,21 +1,17 @@
 // csrc/mesh_smooth_host.h -- host orchestration of mesh_vertex_adjacency / adjacency_list, estimate_mesh_vertex_normals and
-// laplacian_smooth_mesh (kernels and contract: mesh_smooth.h). Included by pcu_hip.hip after marching_cubes_host.h.
+// laplacian_smooth_mesh (kernels and contract: mesh_smooth.h). Included by pcu_hip.hip after the operator frame and the parking functions,
+// voxel_host.h (sort_bytes, scan_bytes, sort_keys, rank_flags) and mesh_host.h (mesh_validate, MeshGiven, int_kind_bytes).
 #pragma once
 
 constexpr int kMsCgMaxIters = 4096;             // a chosen cap that nobody has timed
 constexpr int kMsCgPoll = 8;                    // the host reads the solver's flag word every so many iterations
 
 static unsigned ms_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-// what one stable sort of n (key, id) pairs takes: both key and id buffers and the histograms
-static size_t ms_sort_bytes(size_t n) {
-    return 2 * align_up(n * 8, 256) + 2 * align_up(n * 4, 256) + align_up(256 * ((n + kRsWaveTile - 1) / kRsWaveTile) * 4, 256) + 4096;
-}
-static size_t ms_scan_bytes(size_t n) { return align_up(((n + kScTile - 1) / kScTile + 1) * 8, 256); }
 // faces and incidence
-static size_t ms_incidence_bytes(size_t nv, size_t nf) { return align_up(nf * 12, 256) + ms_sort_bytes(3 * nf) + align_up((nv + 1) * 4, 256) + 4096; }
+static size_t ms_incidence_bytes(size_t nv, size_t nf) { return align_up(nf * 12, 256) + sort_bytes(3 * nf) + align_up((nv + 1) * 4, 256) + 4096; }
 // the pair sort and the CSR (with room for every pair to be an entry)
 static size_t ms_adjacency_bytes(size_t nv, size_t nf) {
-    return ms_sort_bytes(6 * nf) + 4 * align_up(6 * nf * 4, 256) + ms_scan_bytes(6 * nf) + 2 * align_up((nv + 1) * 4, 256) + 4096;
+    return sort_bytes(6 * nf) + 4 * align_up(6 * nf * 4, 256) + scan_bytes(6 * nf) + 2 * align_up((nv + 1) * 4, 256) + 4096;
 }
 
 struct MsStructure {
@@ -31,7 +27,7 @@ struct MsStructure {
 // Stages f, checks its range and writes the corner keys. No wait.
 static int ms_faces(Arena& ar, hipStream_t s, const void* f, int64_t nf, int f_kind, int64_t nv, bool on_dev, MsStructure& S) {
     const char* d_f = nullptr;
-    if (stage_any(ar, static_cast<const char*>(f), (size_t)nf * 3 * mesh_face_bytes(f_kind), on_dev, s, &d_f)) return -1;
+    if (stage_any(ar, static_cast<const char*>(f), (size_t)nf * 3 * int_kind_bytes(f_kind), on_dev, s, &d_f)) return -1;
     if (aalloc(ar, &S.fidx, (size_t)nf * 3) || aalloc(ar, &S.ckeys, (size_t)nf * 3) || aalloc(ar, &S.d_bad, 1)) return -1;
     HIP_TRY(hipMemsetAsync(S.d_bad, 0, sizeof(int), s));
     S.hb = bits_of((unsigned long long)(nv - 1));
@@ -42,10 +38,9 @@ static int ms_faces(Arena& ar, hipStream_t s, const void* f, int64_t nf, int f_k
 // The incidence: one stable sort of the corner keys, one binary search per vertex. No wait.
 static int ms_incidence(Arena& ar, hipStream_t s, int64_t nf, int64_t nv, MsStructure& S) {
     const int C = (int)(3 * nf);
-    unsigned long long* kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
-    if (aalloc(ar, &kb, (size_t)C) || aalloc(ar, &ia, (size_t)C) || aalloc(ar, &ib, (size_t)C) || aalloc(ar, &S.inc_pos, (size_t)nv + 1)) return -1;
-    if (own_radix_sort(ar, s, &S.ckeys, &kb, &ia, &ib, /*ids_identity=*/true, C, std::max(S.hb, 1))) return -1;
-    S.inc_ids = ia;
+    SortedRuns r; r.keys = S.ckeys;
+    if (aalloc(ar, &S.inc_pos, (size_t)nv + 1) || sort_keys(ar, s, r, C, std::max(S.hb, 1))) return -1;
+    S.ckeys = r.keys; S.inc_ids = r.ids;
     hipLaunchKernelGGL(k_ms_row_starts, dim3(ms_blocks((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned long long*)S.ckeys, C, 0, (int)nv, S.inc_pos);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -54,20 +49,20 @@ static int ms_incidence(Arena& ar, hipStream_t s, int64_t nf, int64_t nv, MsStru
 static int ms_adjacency(Arena& ar, hipStream_t s, int64_t nf, int64_t nv, MsStructure& S) {
     const int K = (int)(6 * nf);
     S.K = K;
-    unsigned long long* kb = nullptr; unsigned *ia = nullptr, *ib = nullptr, *flag = nullptr, *scan = nullptr, *pos = nullptr;
-    if (aalloc(ar, &S.pkeys, (size_t)K) || aalloc(ar, &kb, (size_t)K) || aalloc(ar, &ia, (size_t)K) || aalloc(ar, &ib, (size_t)K) || aalloc(ar, &flag, (size_t)K) ||
-        aalloc(ar, &scan, (size_t)K) || aalloc(ar, &pos, (size_t)nv + 1) || aalloc(ar, &S.off, (size_t)nv + 1)) return -1;
-    hipLaunchKernelGGL(k_ms_pairs, dim3(ms_blocks((size_t)K / 2)), dim3(kBlock), 0, s, (const int*)S.fidx, K / 2, S.hb, S.pkeys);
-    if (own_radix_sort(ar, s, &S.pkeys, &kb, &ia, &ib, /*ids_identity=*/true, K, std::max(2 * S.hb, 1))) return -1;
-    S.pids = ia;
-    hipLaunchKernelGGL(k_ms_pair_heads, dim3(ms_blocks((size_t)K)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, K, S.hb, flag);
-    if (own_inclusive_scan(ar, s, (const unsigned*)flag, scan, (size_t)K)) return -1;
+    SortedRuns r; unsigned* pos = nullptr;
+    if (aalloc(ar, &r.keys, (size_t)K) || aalloc(ar, &pos, (size_t)nv + 1) || aalloc(ar, &S.off, (size_t)nv + 1)) return -1;
+    hipLaunchKernelGGL(k_ms_pairs, dim3(ms_blocks((size_t)K / 2)), dim3(kBlock), 0, s, (const int*)S.fidx, K / 2, S.hb, r.keys);
+    if (sort_keys(ar, s, r, K, std::max(2 * S.hb, 1))) return -1;
+    S.pkeys = r.keys; S.pids = r.ids;
+    if (rank_flags(ar, s, r, K, [&](unsigned* flag) {
+            hipLaunchKernelGGL(k_ms_pair_heads, dim3(ms_blocks((size_t)K)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, K, S.hb, flag);
+        })) return -1;
+    unsigned *flag = r.flag, *scan = r.scan;
     hipLaunchKernelGGL(k_ms_row_starts, dim3(ms_blocks((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, K, S.hb, (int)nv, pos);
     hipLaunchKernelGGL(k_ms_offsets, dim3(ms_blocks((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned*)pos, (const unsigned*)scan, (int)nv, S.off);
     HIP_TRY(hipGetLastError());
     int bad = 0; unsigned ne = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, S.d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&ne, scan + (K - 1), 4, hipMemcpyDeviceToHost, s));
+    if (read_flag_and_last(s, S.d_bad, scan, (size_t)K, &bad, &ne)) return -1;
     HIP_WAIT(s);
     if (bad & kMeshBadVertex) return fail(PCU_HIP_ERR_INVALID, "v must not contain NaN or infinite coordinates");
     if (bad & kMeshBadFace) return fail(PCU_HIP_ERR_INVALID, "f must hold row indices of v: found a face index outside [0, %lld)", (long long)nv);
@@ -81,54 +76,42 @@ static int ms_adjacency(Arena& ar, hipStream_t s, int64_t nf, int64_t nv, MsStru
     return 0;
 }
 
-// mesh_vertex_adjacency. The CSR waits in the context's `aux` block for pcu_hip_mesh_adjacency_take: (nv + 1) int64 offsets, then *out_count
+// mesh_vertex_adjacency. The CSR is parked for pcu_hip_mesh_adjacency_take: (nv + 1) int64 offsets, then *out_count
 // neighbours in the faces' integer type.
 static int mesh_adjacency_impl(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
     if (!c || !out_count) return fail(PCU_HIP_ERR_INVALID, "null context / out_count");
     *out_count = 0;
-    c->adj_nv = c->adj_count = -1;
+    c->parked = ParkedResult();
     if (int rc = mesh_validate(nv, nf, 0, f_kind)) return rc;
     if (!f) return fail(PCU_HIP_ERR_INVALID, "null f");
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    const size_t NV = (size_t)nv, NF = (size_t)nf, kb = (size_t)mesh_face_bytes(f_kind);
-    if (int rc = ms_begin(c, st, (on_dev ? 0 : align_up(NF * 3 * kb, 256)) + align_up(NF * 12, 256) + align_up(NF * 24, 256) + ms_adjacency_bytes(NV, NF) + 8192)) return rc;
-    c->time_phases = flags & PCU_HIP_TIME_PHASES;
-    Arena ar{c};
-    Timer tm{c, s, st};             // marks 0-1: faces, keys, sort, heads, scan, offsets and the wait, 1-2: entries and the parked copy
-    auto run = [&]() -> int {
+    const size_t NV = (size_t)nv, NF = (size_t)nf, kb = (size_t)int_kind_bytes(f_kind);
+    const size_t bytes = (on_dev ? 0 : align_up(NF * 3 * kb, 256)) + align_up(NF * 12, 256) + align_up(NF * 24, 256) + ms_adjacency_bytes(NV, NF) + 8192;
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: faces, keys, sort, heads, scan, offsets and the wait, 1-2: entries and the parked copy
         MsStructure S;
         tm.mark(0);
         if (ms_faces(ar, s, f, nf, f_kind, nv, on_dev, S)) return -1;
         if (int rc = ms_adjacency(ar, s, nf, nv, S)) return rc;
         tm.mark(1);
-        const size_t obytes = align_up((NV + 1) * 8, 256);
-        if (aux_reserve(c, obytes + (size_t)S.ne * kb + 256)) return -1;
+        char *d_off = nullptr, *d_nbr = nullptr;
+        if (park_reserve(c, (NV + 1) * 8, (size_t)S.ne * kb, &d_off, &d_nbr)) return -1;
         hipLaunchKernelGGL(k_ms_adj_out, dim3(ms_blocks(std::max(NV + 1, (size_t)S.ne))), dim3(kBlock), 0, s, (const unsigned*)S.off, (int)nv, (const int*)S.col, S.ne, f_kind,
-                           reinterpret_cast<long long*>(c->aux), (void*)(c->aux + obytes));
+                           reinterpret_cast<long long*>(d_off), (void*)d_nbr);
         HIP_TRY(hipGetLastError());
         tm.mark(2);
         HIP_WAIT(s);
-        c->adj_nv = nv; c->adj_count = (int64_t)S.ne; c->adj_isize = (int)kb;
+        park_commit(c, Parked::Adjacency, nv, (int64_t)S.ne);
         *out_count = (int64_t)S.ne;
         if (st) { st->n_queries = nf; st->n_escalated = (int64_t)S.ne; st->n_passes = 1; st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_total = tm.span(0, 2); }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }
 // The result of this context's last pcu_hip_mesh_adjacency. Once.
 static int mesh_adjacency_take_impl(pcu_hip_ctx* c, int64_t nv, int64_t count, int64_t* out_offsets, void* out_neighbours, unsigned flags, void* stream) {
     if (!c || !out_offsets || (!out_neighbours && count > 0)) return fail(PCU_HIP_ERR_INVALID, "null context / out_offsets / out_neighbours");
-    if (c->adj_nv < 0 || nv != c->adj_nv || count != c->adj_count)
-        return fail(PCU_HIP_ERR_INVALID, "pcu_hip_mesh_adjacency_take: this context holds no adjacency of %lld vertices and %lld entries", (long long)nv, (long long)count);
-    hipStream_t s = pick_stream(c, flags, stream);
-    const hipMemcpyKind dir = (flags & PCU_HIP_PTRS_ON_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const size_t ob = ((size_t)nv + 1) * 8;
-    HIP_TRY(hipMemcpyAsync(out_offsets, c->aux, ob, dir, s));
-    if (count > 0) HIP_TRY(hipMemcpyAsync(out_neighbours, c->aux + align_up(ob, 256), (size_t)count * (size_t)c->adj_isize, dir, s));
-    HIP_WAIT(s);
-    c->adj_nv = c->adj_count = -1;
-    return 0;
+    return park_take(c, Parked::Adjacency, nv, count, out_offsets, out_neighbours, flags, stream,
+                     "pcu_hip_mesh_adjacency_take: this context holds no adjacency of %lld vertices and %lld entries");
 }
 
 // estimate_mesh_vertex_normals (src/mesh_normals.cpp:24-50). weighting: 0 uniform, 1 area, 2 angle.
@@ -139,15 +122,11 @@ static int mesh_vertex_normals_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int w
     if (weighting < 0 || weighting > 2) return fail(PCU_HIP_ERR_INVALID, "weighting must be 0 (uniform), 1 (area) or 2 (angle)");
     if (!m.v || !m.f || !out_n) return fail(PCU_HIP_ERR_INVALID, "null v / f / out_n");
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t NV = (size_t)m.nv, NF = (size_t)m.nf;
     size_t bytes = ms_incidence_bytes(NV, NF) + align_up(NF * 24, 256) + 2 * align_up(NF * 3 * sizeof(T), 256) + 8192;
-    if (!on_dev) bytes += 2 * align_up(NV * 3 * sizeof(T), 256) + align_up(NF * 3 * mesh_face_bytes(m.f_kind), 256);
-    if (int rc = ms_begin(c, st, bytes)) return rc;
-    c->time_phases = flags & PCU_HIP_TIME_PHASES;
-    Arena ar{c};
-    Timer tm{c, s, st};             // marks 0-1: checks and incidence, 1-2: per-face vectors and the gather
-    auto run = [&]() -> int {
+    if (!on_dev) bytes += 2 * align_up(NV * 3 * sizeof(T), 256) + align_up(NF * 3 * int_kind_bytes(m.f_kind), 256);
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: checks and incidence, 1-2: per-face vectors and the gather
         MsStructure S;
         const T* dv = nullptr;
         tm.mark(0);
@@ -171,8 +150,7 @@ static int mesh_vertex_normals_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int w
         if (bad & kMeshBadNormal) return fail(PCU_HIP_ERR_INVALID, "vertex normals overflow the scalar type of v");
         if (st) { st->n_queries = m.nv; st->n_passes = 1; st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_total = tm.span(0, 2); }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }
 
 // One solve of (M - h L) x = M x in place, enqueued in pieces: the host looks at the flag word every kMsCgPoll iterations.
@@ -217,17 +195,13 @@ static int laplacian_smooth_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int num_
     if (!(step_size >= 0.0) || !std::isfinite(step_size)) return fail(PCU_HIP_ERR_INVALID, "step_size must be finite and not negative");
     if (!m.v || !m.f || !out) return fail(PCU_HIP_ERR_INVALID, "null v / f / out");
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t NV = (size_t)m.nv, NF = (size_t)m.nf, nb = ms_blocks(NV), nbf = ms_blocks(NF);
     size_t bytes = ms_incidence_bytes(NV, NF) + align_up(NF * 24, 256) + ms_adjacency_bytes(NV, NF) + align_up(NF * 3 * sizeof(T), 256) + align_up(NF * 6 * sizeof(T), 256) +
                    align_up(NF * sizeof(T), 256) + 7 * align_up(NV * 3 * sizeof(T), 256) + 3 * align_up(NV * sizeof(T), 256) +
                    align_up(std::max(nb * kMsFoldMax, nbf * 4) * sizeof(T), 256) + 16384;
-    if (!on_dev) bytes += align_up(NV * 3 * sizeof(T), 256) + align_up(NF * 3 * mesh_face_bytes(m.f_kind), 256);
-    if (int rc = ms_begin(c, st, bytes)) return rc;
-    c->time_phases = flags & PCU_HIP_TIME_PHASES;
-    Arena ar{c};
-    Timer tm{c, s, st};             // marks 0-1: checks, incidence and adjacency, 1-2: the cotangent matrix, 2-3: the iterations
-    auto run = [&]() -> int {
+    if (!on_dev) bytes += align_up(NV * 3 * sizeof(T), 256) + align_up(NF * 3 * int_kind_bytes(m.f_kind), 256);
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: checks, incidence and adjacency, 1-2: the cotangent matrix, 2-3: the iterations
         MsStructure S;
         const T* dv = nullptr;
         tm.mark(0);
@@ -282,6 +256,5 @@ static int laplacian_smooth_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int num_
             st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_kernel_search = tm.span(2, 3); st->ms_total = tm.span(0, 3);
         }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }

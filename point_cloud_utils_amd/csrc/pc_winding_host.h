@@ -35,7 +35,7 @@ static size_t pc_index_bytes(int64_t np) {
 // the sort, the nodes' weights and, for host arrays, p, n and a staged
 template <typename T>
 static size_t pc_build_bytes(int64_t np, bool on_dev) {
-    size_t b = mesh_sort_bytes(np) + align_up(2 * (size_t)pc_leaves_pow2(np) * sizeof(double), 256) + 4096;
+    size_t b = sort_bytes((size_t)np) + align_up(2 * (size_t)pc_leaves_pow2(np) * sizeof(double), 256) + 4096;
     if (!on_dev) b += 2 * align_up((size_t)np * 3 * sizeof(T), 256) + align_up((size_t)np * sizeof(T), 256);
     return b;
 }
@@ -115,19 +115,16 @@ static int pc_call(pcu_hip_ctx* c, const PcGiven<T>* pc, const pcu_hip_pc_windin
     if (pc) { if (int rc = pc_validate_rows(pc->np)) return rc; }
     if (int rc = op.validate(nq)) return rc;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
     size_t bytes = mesh_run_bytes<T>(nq, 1, on_dev);
     if (pc) bytes += pc_index_bytes<T>(pc->np) + pc_build_bytes<T>(pc->np, on_dev);
-    if (ctx_begin(c, bytes)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    Timer tm{c, s, st};
-    MeshIdx<T> built;
-    int rc = 0;
-    if (pc) { tm.mark(0); rc = pc_build<T>(ar, ar, s, pc->p, pc->n, pc->a, pc->np, on_dev, built); }
-    if (!rc) rc = mesh_run<T>(ar, s, pc ? built : pc_idx<T>(ix), op, nq, on_dev, out_w, nullptr, nullptr, tm);
-    if (!rc) mesh_stats(st, tm, nq, pc != nullptr);
-    return attempt_exit(c, rc);
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
+        MeshIdx<T> built;
+        if (pc) { tm.mark(0); if (int rc = pc_build<T>(ar, ar, s, pc->p, pc->n, pc->a, pc->np, on_dev, built)) return rc; }
+        if (int rc = mesh_run<T>(ar, s, pc ? built : pc_idx<T>(ix), op, nq, on_dev, out_w, nullptr, nullptr, tm)) return rc;
+        mesh_stats(st, tm, nq, pc != nullptr);
+        return 0;
+    });
 }
 
 template <typename T>
@@ -159,10 +156,8 @@ static int mesh_face_normals_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, T* out_
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
     if (int rc = mesh_validate(m.nv, m.nf, 0, m.f_kind)) return rc;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    if (int rc = ms_begin(c, st, ms_mesh_bytes(m, on_dev) + (on_dev ? 0 : align_up((size_t)m.nf * 3 * sizeof(T), 256)))) return rc;
-    Arena ar{c};
-    auto run = [&]() -> int {
+    return op_run(c, flags, stream, st, ms_mesh_bytes(m, on_dev) + (on_dev ? 0 : align_up((size_t)m.nf * 3 * sizeof(T), 256)), [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         MsMesh<T> M; MsSeen<T> seen;
         if (ms_mesh_stage<T>(ar, s, m, on_dev, M)) return -1;
         T* d_n = out_n;
@@ -177,6 +172,5 @@ static int mesh_face_normals_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, T* out_
         if (seen.bad & kMeshBadNormal) return fail(PCU_HIP_ERR_INVALID, "face normals overflow the scalar type of v");
         if (st) { st->n_queries = m.nf; st->n_passes = 1; }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }

@@ -211,6 +211,10 @@ struct ArenaState {
     std::vector<void*> extra;                 // overflow allocations (of the current call)
     size_t extra_bytes = 0;
 };
+// A result whose size the caller learns from the call that made it waits in the context's `aux` block, as two segments (the second one
+// 256-aligned behind the first), for the _take call that repeats its two counts. One record: a context holds at most one such result.
+enum class Parked { None, VoxelRows, Surface, HexMesh, Adjacency };
+struct ParkedResult { Parked kind = Parked::None; int64_t n0 = 0, n1 = 0; size_t bytes0 = 0, bytes1 = 0; };
 struct pcu_hip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -253,12 +257,9 @@ struct pcu_hip_ctx {
                                               // placement (k_bucket_large) with every build instead of on demand
     unsigned long long* fill2 = nullptr; int fill_parity = 0;   // grid2.h "no memset": two sets of kFillWords bucket fill words; a one-pass build uses set
                                                                  // fill_parity -- left zeroed by its predecessor -- and zeroes the other one for its successor
-    char* aux = nullptr; size_t aux_cap = 0;  // grow-only block for operators that run a search as a sub-step (normals): survives the
-                                              // sub-call's use of the arena
-    int64_t vox_rows = -1;                    // rows of a voxelization parked in `aux` for pcu_hip_voxelize_take (voxelize_host.h); -1: none
-    int64_t mc_nv = -1, mc_nf = -1; int mc_vsize = 0, mc_isize = 0;   // a surface parked there for pcu_hip_marching_cubes_take (marching_cubes_host.h)
-    int64_t hx_nv = -1, hx_k = -1; int hx_vsize = 0;                  // a hex mesh parked there for pcu_hip_sparse_voxel_grid_to_hex_mesh_take
-    int64_t adj_nv = -1, adj_count = -1; int adj_isize = 0;           // a vertex adjacency parked there for pcu_hip_mesh_adjacency_take (mesh_smooth_host.h)
+    char* aux = nullptr; size_t aux_cap = 0;  // grow-only block that survives a sub-call's use of the arena: the normals' workspace (they run a search as a
+                                              // sub-step), and the one result of unknown size that waits for its _take call
+    ParkedResult parked;                      // what waits in `aux`, if anything (aux_reserve, park_reserve / park_commit / park_take)
     // grid2.h: GridGeo -- the layout of this context's last two-sided fused build, per cloud, on the device; what it was computed for, on the host
     struct GeoCache { char* dev = nullptr; bool valid[2] = {false, false}; int n[2] = {0, 0}; double occ = 0, h_want = 0; int max_cells = 0, n_layout = 0, tsize = 0; bool shared = false; } geo;
     unsigned cancel_epoch = 0;                // g_cancel_epoch at this context's last call (ctx_begin: reset of the cross-call device state after an abandoned call)
@@ -1343,6 +1344,37 @@ static int stage_in(Arena& ar, const T* p, int64_t n, bool on_dev, hipStream_t s
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ the frame of an operator
+static hipStream_t pick_stream(pcu_hip_ctx* c, unsigned flags, void* stream) {
+    return (stream || (flags & PCU_HIP_STREAM_GIVEN)) ? (hipStream_t)stream : c->own_stream;
+}
+template <typename U>
+static int stage_any(Arena& ar, const U* p, size_t count, bool on_dev, hipStream_t s, const U** out) {
+    if (on_dev) { *out = p; return 0; }
+    U* d = nullptr;
+    if (aalloc(ar, &d, count)) return -1;
+    HIP_TRY(hipMemcpyAsync(d, p, count * sizeof(U), hipMemcpyHostToDevice, s));
+    *out = d;
+    return 0;
+}
+// The head of a call that reports statistics: they are zeroed, the timing flags cleared, the workspace made ready.
+static int stats_zero_ctx_begin(pcu_hip_ctx* c, pcu_hip_stats* st, size_t bytes) {
+    if (st) memset(st, 0, sizeof *st);
+    c->time_phases = false; c->time_kernels = false;
+    return ctx_begin(c, bytes) ? PCU_HIP_ERR_RUNTIME : 0;
+}
+// An operator over the context's workspace: the caller validates, sizes the workspace and hands over a body, which unpacks the frame with
+// `auto& [c, s, on_dev, ar, tm] = fr;`. Phases are timed (Timer) when the call asks for it and has statistics to put them in.
+struct OpFrame { pcu_hip_ctx* c; hipStream_t s; bool on_dev; Arena ar; Timer tm; };
+template <typename Body>
+static int op_run(pcu_hip_ctx* c, unsigned flags, void* stream, pcu_hip_stats* st, size_t bytes, Body body) {
+    hipStream_t s = pick_stream(c, flags, stream);
+    if (int rc = stats_zero_ctx_begin(c, st, bytes)) return rc;
+    c->time_phases = flags & PCU_HIP_TIME_PHASES;
+    OpFrame fr{c, s, (flags & PCU_HIP_PTRS_ON_DEVICE) != 0, Arena{c}, Timer{c, s, st}};
+    return attempt_exit(c, body(fr));
+}
+
 // ------------------------------------------------------------------------------------------------ knn
 // A dataset kept on the GPU together with its grid index (pcu_hip_index_*): memory owned by the object, not by a call's arena.
 struct pcu_hip_index {
@@ -2144,14 +2176,34 @@ static int chamfer_impl(pcu_hip_ctx* c, const T* x, int64_t nx, const T* y, int6
 
 // ------------------------------------------------------------------------------------------------ normals
 static int aux_reserve(pcu_hip_ctx* c, size_t bytes) {
-    c->vox_rows = -1;                           // (whatever was parked in the block goes with its new use)
-    c->mc_nv = c->mc_nf = -1; c->hx_nv = c->hx_k = -1; c->adj_nv = c->adj_count = -1;
+    c->parked = ParkedResult();                 // (whatever was parked in the block goes with its new use)
     if (bytes > c->aux_cap) {
         if (c->aux) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->aux)); c->aux = nullptr; c->aux_cap = 0; }
         const size_t cap = align_up(bytes + (bytes >> 3), 1 << 20);
         HIP_TRY(hipMalloc((void**)&c->aux, cap));
         c->aux_cap = cap;
     }
+    return 0;
+}
+// Parking a result: reserve its two segments, have them written and waited for, commit. Nothing is parked in between.
+static int park_reserve(pcu_hip_ctx* c, size_t bytes0, size_t bytes1, char** seg0, char** seg1) {
+    if (aux_reserve(c, align_up(bytes0, 256) + bytes1 + 256)) return -1;
+    c->parked.bytes0 = bytes0; c->parked.bytes1 = bytes1;
+    *seg0 = c->aux; *seg1 = c->aux + align_up(bytes0, 256);
+    return 0;
+}
+static void park_commit(pcu_hip_ctx* c, Parked kind, int64_t n0, int64_t n1) { c->parked.kind = kind; c->parked.n0 = n0; c->parked.n1 = n1; }
+// The parked result goes to out0 / out1, once, and only to the call that names its kind and both counts (`refusal`: the operator's text
+// with the two counts as %lld). A cancelled copy leaves it where it is: the call can be issued again.
+static int park_take(pcu_hip_ctx* c, Parked kind, int64_t n0, int64_t n1, void* out0, void* out1, unsigned flags, void* stream, const char* refusal) {
+    const ParkedResult& p = c->parked;
+    if (p.kind != kind || n0 != p.n0 || n1 != p.n1) return fail(PCU_HIP_ERR_INVALID, refusal, (long long)n0, (long long)n1);
+    hipStream_t s = pick_stream(c, flags, stream);
+    const hipMemcpyKind dir = (flags & PCU_HIP_PTRS_ON_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (p.bytes0) HIP_TRY(hipMemcpyAsync(out0, c->aux, p.bytes0, dir, s));
+    if (p.bytes1) HIP_TRY(hipMemcpyAsync(out1, c->aux + align_up(p.bytes0, 256), p.bytes1, dir, s));
+    HIP_WAIT(s);
+    c->parked = ParkedResult();
     return 0;
 }
 static int validate_normals_input(int64_t n, int64_t n_dirs) {
@@ -2171,7 +2223,7 @@ static int normals_knn_impl(pcu_hip_ctx* c, const T* points, int64_t n, const T*
     if (k <= 0) return fail(PCU_HIP_ERR_INVALID, "Invalid number of neighbors (%d) must be greater than 0.", k);
     if (validate_normals_input(n, dirs ? n : 0)) return PCU_HIP_ERR_INVALID;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = (stream || (flags & PCU_HIP_STREAM_GIVEN)) ? (hipStream_t)stream : c->own_stream;
+    hipStream_t s = pick_stream(c, flags, stream);
     auto al = [](size_t v) { return align_up(v, 256); };
     const size_t b_pts = al((size_t)n * 3 * sizeof(T));
     const size_t need = (on_dev ? 0 : 2 * b_pts) + al((size_t)n * k * 8) + al((size_t)n * k * sizeof(T)) + (on_dev ? 0 : b_pts + al((size_t)n));
@@ -2208,33 +2260,27 @@ static int normals_ball_impl(pcu_hip_ctx* c, const T* points, int64_t n, const T
     if (min_pts < 3) return fail(PCU_HIP_ERR_INVALID, "Invalid min_pts_per_ball (%d) must be greater than 3.", min_pts);
     if (max_pts > 0 && max_pts < 3) return fail(PCU_HIP_ERR_INVALID, "Invalid max_pts_per_ball (%d) must either be negative (no max) or a number greater than 3.", max_pts);
     if (validate_normals_input(n, dirs ? n : 0)) return PCU_HIP_ERR_INVALID;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = (stream || (flags & PCU_HIP_STREAM_GIVEN)) ? (hipStream_t)stream : c->own_stream;
-    if (st) memset(st, 0, sizeof *st);
-    c->time_phases = false; c->time_kernels = false;
     const double occ = 8.0;
     size_t need = index_bytes<T>(n, occ) + align_up((size_t)n * sizeof(Pt4<T>), 256) + 8192;
-    if (!on_dev) need += 3 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n, 256);
-    if (ctx_begin(c, need)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
+    if (!(flags & PCU_HIP_PTRS_ON_DEVICE)) need += 3 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n, 256);
+    return op_run(c, flags, stream, st, need, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const T *d_pts, *d_dirs = dirs;
         Pt4<T>* by_row = nullptr;
-        if ((rc = aalloc(ar, &by_row, (size_t)n))) break;
-        if ((rc = stage_in(ar, points, n, on_dev, s, &d_pts))) break;
-        if (dirs && (rc = stage_in(ar, dirs, n, on_dev, s, &d_dirs))) break;
+        if (int rc = aalloc(ar, &by_row, (size_t)n)) return rc;
+        if (int rc = stage_in(ar, points, n, on_dev, s, &d_pts)) return rc;
+        if (dirs) if (int rc = stage_in(ar, dirs, n, on_dev, s, &d_dirs)) return rc;
         T* d_out = out_n; uint8_t* d_keep = out_keep;
-        if (!on_dev) { if ((rc = aalloc(ar, &d_out, (size_t)n * 3))) break; if ((rc = aalloc(ar, &d_keep, (size_t)n))) break; }
+        if (!on_dev) { if (int rc = aalloc(ar, &d_out, (size_t)n * 3)) return rc; if (int rc = aalloc(ar, &d_keep, (size_t)n)) return rc; }
         GridIndex<T> gi;
-        if ((rc = index_alloc(ar, gi, n, occ, IndexFor::Atomic))) break;
+        if (int rc = index_alloc(ar, gi, n, occ, IndexFor::Atomic)) return rc;
         const T radius_t = (T)ball_radius;                          // RadiusResultSet<DistanceType = T>(radius, ...)
         gi.h_want = sqrt((double)radius_t) / 1.98;                  // cells of about half the true search radius: 5^3 cells per point
-        if ((rc = index_build(gi, d_pts, occ, s))) break;
+        if (int rc = index_build(gi, d_pts, occ, s)) return rc;
         // the rule of every searched cloud (nonfinite_error): NaN, or +inf and -inf along one axis, is refused -- the reference's tree over such a cloud
         // has no stable answer. A row with single-signed infinities stays: its d2 is +inf or NaN against every row (itself included), so it is nobody's
         // member, it has no members and is dropped, and it sits in a border cell of a grid laid over the finite values (grid.h).
-        if ((rc = check_nonfinite<T>(gi.gp, kNfNaN | kNfBothInf, s))) break;
+        if (int rc = check_nonfinite<T>(gi.gp, kNfNaN | kNfBothInf, s)) return rc;
         if (st) { st->n_grid_builds = 1; st->n_queries = n; st->n_passes = 1; }
         hipLaunchKernelGGL(k_cells_by_row<T>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, gi.gp, gi.sorted, gi.cell_start, (int)n, by_row);
         const NormalsBallArgs<T> a{gi.gp, by_row, gi.cell_start, d_dirs, (int)n, radius_t, ball_radius, min_pts, max_pts, weight_rbf, drop, d_out, d_keep};
@@ -2245,9 +2291,8 @@ static int normals_ball_impl(pcu_hip_ctx* c, const T* points, int64_t n, const T
             HIP_TRY(hipMemcpyAsync(out_keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, s));
         }
         HIP_WAIT(s);
-    } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+        return 0;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ batches of pairs

@@ -1,5 +1,5 @@
 // csrc/poisson_host.h -- host orchestration of Poisson-disk downsampling (kernels and contract: poisson.h). Included by pcu_hip.hip after
-// the grid-index, arena and scan helpers.
+// the grid index (index_host.h), the operator frame (op_run) and voxel_host.h (the scan).
 #pragma once
 
 // The working set of one call: a grid index over the cloud (rebuilt for every radius) and the per-record / per-cell state of the rounds.
@@ -156,28 +156,23 @@ static int poisson_disk_impl(pcu_hip_ctx* c, const T* pts, int64_t n, double rad
     *out_count = 0;
     float tol = 0.0f;
     if (int rc = pd_check_args(n, radius, target, tolerance, &tol)) return rc;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t N = (size_t)n;
     const bool all_rows = target > 0 && target >= n;
     size_t need = pd_body_bytes<T>(n, target);
-    if (!on_dev) need += (all_rows ? 0 : align_up(N * 3 * sizeof(T), 256)) + align_up(N * 4, 256);
-    if (ctx_begin(c, need)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    PdRun<T> R;
-    do {
+    if (!(flags & PCU_HIP_PTRS_ON_DEVICE)) need += (all_rows ? 0 : align_up(N * 3 * sizeof(T), 256)) + align_up(N * 4, 256);
+    return op_run(c, flags, stream, st, need, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
+        PdRun<T> R;
         const T* d_pts = nullptr;
-        if (!all_rows && (rc = stage_in(ar, pts, n, on_dev, s, &d_pts))) break;
+        if (!all_rows) if (int rc = stage_in(ar, pts, n, on_dev, s, &d_pts)) return rc;
         int32_t* d_out = out_idx;
-        if (!on_dev && (rc = aalloc(ar, &d_out, N))) break;
+        if (!on_dev) if (int rc = aalloc(ar, &d_out, N)) return rc;
         int64_t cnt = 0;
-        if ((rc = pd_body<T>(ar, s, d_pts, n, radius, target, seed, tol, d_out, &cnt, R))) break;
+        if (int rc = pd_body<T>(ar, s, d_pts, n, radius, target, seed, tol, d_out, &cnt, R)) return rc;
         if (!on_dev && cnt > 0) HIP_TRY(hipMemcpyAsync(out_idx, d_out, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         *out_count = cnt;
         if (st && !all_rows) { st->n_queries = n; st->n_passes = R.rounds; st->n_grid_builds = R.radii; }
-    } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+        return 0;
+    });
 }

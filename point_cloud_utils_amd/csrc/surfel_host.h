@@ -38,7 +38,7 @@ static size_t surfel_index_bytes(int64_t np, int subdivs) {
 // the sort and, for host arrays, p, n and r staged
 template <typename T>
 static size_t surfel_build_bytes(int64_t np, bool on_dev) {
-    size_t b = mesh_sort_bytes(np) + 4096;
+    size_t b = sort_bytes((size_t)np) + 4096;
     if (!on_dev) b += 2 * align_up((size_t)np * 3 * sizeof(T), 256) + align_up((size_t)np * sizeof(T), 256);
     return b;
 }
@@ -132,19 +132,16 @@ static int surfel_call(pcu_hip_ctx* c, const SurfelGiven<T>* sf, const pcu_hip_s
     if (sf) { if (int rc = surfel_validate(sf->np, sf->subdivs)) return rc; }
     if (int rc = op.validate(n)) return rc;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    c->time_phases = flags & PCU_HIP_TIME_PHASES; c->time_kernels = false;
     size_t bytes = mesh_run_bytes<T>(n, SurfelRaysOp<T>::kRows3, on_dev);
     if (sf) bytes += surfel_index_bytes<T>(sf->np, sf->subdivs) + surfel_build_bytes<T>(sf->np, on_dev);
-    if (ctx_begin(c, bytes)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    Timer tm{c, s, st};
-    MeshIdx<T> built;
-    int rc = 0;
-    if (sf) { tm.mark(0); rc = surfel_build<T>(ar, ar, s, sf->p, sf->n, sf->r, sf->np, sf->subdivs, on_dev, built, &op.table); }
-    if (!rc) rc = mesh_run<T>(ar, s, sf ? built : surfel_idx<T>(ix), op, n, on_dev, out_t, out_pid, nullptr, tm);
-    if (!rc) mesh_stats(st, tm, n, sf != nullptr);
-    return attempt_exit(c, rc);
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
+        MeshIdx<T> built;
+        if (sf) { tm.mark(0); if (int rc = surfel_build<T>(ar, ar, s, sf->p, sf->n, sf->r, sf->np, sf->subdivs, on_dev, built, &op.table)) return rc; }
+        if (int rc = mesh_run<T>(ar, s, sf ? built : surfel_idx<T>(ix), op, n, on_dev, out_t, out_pid, nullptr, tm)) return rc;
+        mesh_stats(st, tm, n, sf != nullptr);
+        return 0;
+    });
 }
 
 template <typename T>
@@ -183,15 +180,11 @@ static int surfel_geometry_impl(pcu_hip_ctx* c, const T* p, const T* n, const T*
     if (np * ((int64_t)subdivs + 1) > 0x7fffffffll)
         return fail(PCU_HIP_ERR_INVALID, "surfel geometry with more than 2^31-1 vertices does not fit the int32 faces");
     if (np == 0) return 0;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t nv = (size_t)np * ((size_t)subdivs + 1), nf = (size_t)np * (size_t)subdivs;
     size_t bytes = surfel_table_bytes<T>(subdivs) + 4096;
-    if (!on_dev) bytes += surfel_build_bytes<T>(np, false) + align_up(nv * 3 * sizeof(T), 256) + align_up(nf * 12, 256);
-    c->time_phases = false; c->time_kernels = false;
-    if (ctx_begin(c, bytes)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    auto run = [&]() -> int {
+    if (!(flags & PCU_HIP_PTRS_ON_DEVICE)) bytes += surfel_build_bytes<T>(np, false) + align_up(nv * 3 * sizeof(T), 256) + align_up(nf * 12, 256);
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const T *dp = nullptr, *dn = nullptr, *dr = nullptr, *table = nullptr;
         if (stage_in(ar, p, np, on_dev, s, &dp) || stage_in(ar, n, np, on_dev, s, &dn) || stage_any(ar, r, (size_t)np, on_dev, s, &dr) ||
             surfel_table<T>(ar, s, subdivs, &table)) return -1;
@@ -210,6 +203,5 @@ static int surfel_geometry_impl(pcu_hip_ctx* c, const T* p, const T* n, const T*
         if (int rc = surfel_refuse(bad)) return rc;
         if (st) { st->n_queries = np; st->n_passes = 1; }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }

@@ -1,19 +1,7 @@
-// csrc/voxel_host.h -- host orchestration of the SURVEY.md 8f-4 operators (included by pcu_hip.hip after the context / arena
-// helpers): Morton codes (morton.h), voxel-grid downsampling and duplicate removal (voxel.h).
+// csrc/voxel_host.h -- host orchestration of the SURVEY.md 8f-4 operators: Morton codes (morton.h), voxel-grid downsampling and duplicate
+// removal (voxel.h), and the sort, scan and sort-and-rank steps every later *_host.h builds on. Included by pcu_hip.hip after the operator
+// frame (pick_stream, stage_any, op_run), first of the *_host.h headers.
 #pragma once
-
-template <typename U>
-static int stage_any(Arena& ar, const U* p, size_t count, bool on_dev, hipStream_t s, const U** out) {
-    if (on_dev) { *out = p; return 0; }
-    U* d = nullptr;
-    if (aalloc(ar, &d, count)) return -1;
-    HIP_TRY(hipMemcpyAsync(d, p, count * sizeof(U), hipMemcpyHostToDevice, s));
-    *out = d;
-    return 0;
-}
-static hipStream_t pick_stream(pcu_hip_ctx* c, unsigned flags, void* stream) {
-    return (stream || (flags & PCU_HIP_STREAM_GIVEN)) ? (hipStream_t)stream : c->own_stream;
-}
 
 // ---------------------------------------------------------------------------------------------------- Morton codes
 // kind: 0 encode (in: I (n,3) -> out u64 (n)), 1 decode (in: C (n) -> out i32 (n,3)), 2 add, 3 subtract (in, in2: C (n) -> u64 (n))
@@ -24,17 +12,15 @@ static int morton_map_impl(pcu_hip_ctx* c, int kind, const In* in, const In2* in
                                                  : kind == 1 ? "codes must be an array of shape [n] but got an empty array"
                                                              : "codes_1 must be an array of shape [n,] but got an empty array");
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t in_count = kind == 0 ? (size_t)n * 3 : (size_t)n, out_bytes = kind == 1 ? (size_t)n * 12 : (size_t)n * 8;
-    if (ctx_begin(c, on_dev ? 4096 : align_up(in_count * sizeof(In), 256) + align_up((size_t)n * sizeof(In2), 256) + align_up(out_bytes, 256) + 4096)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
+    const size_t bytes = on_dev ? 4096 : align_up(in_count * sizeof(In), 256) + align_up((size_t)n * sizeof(In2), 256) + align_up(out_bytes, 256) + 4096;
+    return op_run(c, flags, stream, nullptr, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const In* d_in; const In2* d_in2 = in2;
-        if ((rc = stage_any(ar, in, in_count, on_dev, s, &d_in))) break;
-        if (kind >= 2 && (rc = stage_any(ar, in2, (size_t)n, on_dev, s, &d_in2))) break;
+        if (stage_any(ar, in, in_count, on_dev, s, &d_in)) return -1;
+        if (kind >= 2 && stage_any(ar, in2, (size_t)n, on_dev, s, &d_in2)) return -1;
         void* d_out = out;
-        if (!on_dev) { char* t = nullptr; if ((rc = aalloc(ar, &t, out_bytes))) break; d_out = t; }
+        if (!on_dev) { char* t = nullptr; if (aalloc(ar, &t, out_bytes)) return -1; d_out = t; }
         const int blocks = (int)std::min<int64_t>((n + 255) / 256, 65536);
         if (kind == 0) hipLaunchKernelGGL((k_morton_encode<In>), dim3(blocks), dim3(256), 0, s, d_in, (long long)n, (uint64_t*)d_out);
         else if (kind == 1) hipLaunchKernelGGL((k_morton_decode<In>), dim3(blocks), dim3(256), 0, s, d_in, (long long)n, (int32_t*)d_out);
@@ -42,9 +28,8 @@ static int morton_map_impl(pcu_hip_ctx* c, int kind, const In* in, const In2* in
         HIP_TRY(hipGetLastError());
         if (!on_dev) HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
-    } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+        return 0;
+    });
 }
 template <typename C>
 static int morton_knn_impl(pcu_hip_ctx* c, const C* codes, int64_t n, const C* qcodes, int64_t m, int k, int sort_dist, int64_t* out_nn, unsigned flags, void* stream) {
@@ -53,22 +38,19 @@ static int morton_knn_impl(pcu_hip_ctx* c, const C* codes, int64_t n, const C* q
     if (n <= 0 || m <= 0) return fail(PCU_HIP_ERR_INVALID, "codes must be an array of shape [n] but got an empty array");
     if (k > n) k = (int)n;                                   // k = std::min(k, (int)codes.rows()), src/morton.cpp:362
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    if (ctx_begin(c, on_dev ? 4096 : align_up((size_t)n * sizeof(C), 256) + align_up((size_t)m * sizeof(C), 256) + align_up((size_t)m * k * 8, 256) + 4096)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
+    const size_t bytes = on_dev ? 4096 : align_up((size_t)n * sizeof(C), 256) + align_up((size_t)m * sizeof(C), 256) + align_up((size_t)m * k * 8, 256) + 4096;
+    return op_run(c, flags, stream, nullptr, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const C *d_codes, *d_q;
-        if ((rc = stage_any(ar, codes, (size_t)n, on_dev, s, &d_codes)) || (rc = stage_any(ar, qcodes, (size_t)m, on_dev, s, &d_q))) break;
+        if (stage_any(ar, codes, (size_t)n, on_dev, s, &d_codes) || stage_any(ar, qcodes, (size_t)m, on_dev, s, &d_q)) return -1;
         long long* d_nn = (long long*)out_nn;
-        if (!on_dev && (rc = aalloc(ar, &d_nn, (size_t)m * k))) break;
+        if (!on_dev && aalloc(ar, &d_nn, (size_t)m * k)) return -1;
         hipLaunchKernelGGL((k_morton_knn<C>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d_codes, (long long)n, d_q, (long long)m, k, sort_dist, d_nn);
         HIP_TRY(hipGetLastError());
         if (!on_dev) HIP_TRY(hipMemcpyAsync(out_nn, d_nn, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
-    } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------- sort by a key triple
@@ -103,12 +85,48 @@ static int own_radix_sort(Arena& ar, hipStream_t s, unsigned long long** keys, u
     HIP_TRY(hipGetLastError());
     return 0;
 }
+// What these take from the arena: one stable sort of n (key, id) pairs (both key and id buffers and the histograms), one scan's tile sums.
+static size_t sort_bytes(size_t n) {
+    return 2 * align_up(n * 8, 256) + 2 * align_up(n * 4, 256) + align_up(256 * ((n + kRsWaveTile - 1) / kRsWaveTile) * 4, 256) + 4096;
+}
+static size_t scan_bytes(size_t n) { return align_up(((n + kScTile - 1) / kScTile + 1) * 8, 256); }
+// Sort, mark, rank: the two halves of "how many distinct keys, and which is which". No wait in either.
+struct SortedRuns {
+    unsigned long long* keys = nullptr;         // in: n keys; after sort_keys: the buffer that holds them sorted
+    unsigned* ids = nullptr;                    // after sort_keys: where each sorted key stood
+    unsigned *flag = nullptr, *scan = nullptr;  // after rank_*: the marks and their inclusive scan; the number of marks is scan[n - 1]
+};
+static int sort_keys(Arena& ar, hipStream_t s, SortedRuns& r, int n, int bits) {
+    unsigned long long* kb = nullptr; unsigned* ib = nullptr;
+    if (aalloc(ar, &kb, (size_t)n) || aalloc(ar, &r.ids, (size_t)n) || aalloc(ar, &ib, (size_t)n)) return -1;
+    return own_radix_sort(ar, s, &r.keys, &kb, &r.ids, &ib, /*ids_identity=*/true, n, bits);
+}
+// write_flags(flag) launches the kernel that marks the n entries; then the scan.
+template <typename WriteFlags>
+static int rank_flags(Arena& ar, hipStream_t s, SortedRuns& r, int n, WriteFlags write_flags) {
+    if (aalloc(ar, &r.flag, (size_t)n) || aalloc(ar, &r.scan, (size_t)n + 1)) return -1;
+    write_flags(r.flag);
+    return own_inclusive_scan(ar, s, (const unsigned*)r.flag, r.scan, (size_t)n);
+}
+// ... with the first entry of every run of equal sorted keys marked
+static int rank_runs(Arena& ar, hipStream_t s, SortedRuns& r, int n) {
+    return rank_flags(ar, s, r, n, [&](unsigned* flag) {
+        hipLaunchKernelGGL(k_run_heads_sorted, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, n, flag);
+    });
+}
+// Enqueues the read-back of "flag word and one count" (the last element of a scan); the caller waits once for these and whatever else it reads.
+template <typename U>
+static int read_flag_and_last(hipStream_t s, const int* d_bad, const U* scan, size_t n, int* bad, U* last) {
+    HIP_TRY(hipMemcpyAsync(bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(last, scan + (n - 1), sizeof(U), hipMemcpyDeviceToHost, s));
+    return 0;
+}
 static int bits_of(unsigned long long v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
 // perm_out: point ids ordered lexicographically by (k0, k1, k2), equal triples in input order. The components are packed, each less its
 // minimum, into one key of as many bits as their ranges need and sorted by the repo's own stable radix passes (radix.h); triples wider than
 // 64 bits in total are sorted component by component, least significant first. One host read-back (the components' ranges).
 template <typename K>
-static int sort_by_triple(Arena& ar, hipStream_t s, const K* k0, const K* k1, const K* k2, unsigned* ids, int n, unsigned** perm_out, const unsigned long long** sorted_keys = nullptr) {
+static int sort_by_triple(Arena& ar, hipStream_t s, const K* k0, const K* k1, const K* k2, unsigned* ids, int n, unsigned** perm_out, unsigned long long** sorted_keys = nullptr) {
     if (sorted_keys) *sorted_keys = nullptr;
     KeyRange* rng = nullptr;
     unsigned long long *ka = nullptr, *kb = nullptr; unsigned* alt = nullptr;
@@ -139,16 +157,14 @@ static int sort_by_triple(Arena& ar, hipStream_t s, const K* k0, const K* k1, co
     *perm_out = cur;
     return 0;
 }
-// head flags + inclusive scan of a sorted order -> (flag, scan); the number of runs is scan[n-1]
+// head flags + inclusive scan of a sorted order -> r.flag, r.scan; the number of runs is scan[n-1]. With sort_by_triple's packed keys
+// (r.keys) the heads are read off them; otherwise off the triples through perm.
 template <typename K>
-static int runs_of(Arena& ar, hipStream_t s, const K* k0, const K* k1, const K* k2, const unsigned* perm, int n, unsigned** flag_out, unsigned** scan_out, const unsigned long long* sorted_keys = nullptr) {
-    unsigned *flag = nullptr, *scan = nullptr;
-    if (aalloc(ar, &flag, (size_t)n) || aalloc(ar, &scan, (size_t)n + 1)) return -1;
-    if (sorted_keys) hipLaunchKernelGGL(k_run_heads_sorted, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sorted_keys, n, flag);
-    else hipLaunchKernelGGL((k_run_heads<K>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, k0, k1, k2, perm, n, flag);
-    if (own_inclusive_scan(ar, s, flag, scan, (size_t)n)) return -1;
-    *flag_out = flag; *scan_out = scan;
-    return 0;
+static int runs_of(Arena& ar, hipStream_t s, const K* k0, const K* k1, const K* k2, const unsigned* perm, int n, SortedRuns& r) {
+    if (r.keys) return rank_runs(ar, s, r, n);
+    return rank_flags(ar, s, r, n, [&](unsigned* flag) {
+        hipLaunchKernelGGL((k_run_heads<K>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, k0, k1, k2, perm, n, flag);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------- voxel-grid downsampling
@@ -170,33 +186,30 @@ static int voxel_downsample_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const 
         return fail(PCU_HIP_ERR_INVALID, "Invalid number of attributes (%lld). Must match number of input vertices (%lld) or be 0.", (long long)attrib_rows, (long long)n);
     if (!has_attr) cols = 0;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t N = (size_t)n;
     size_t need = 20 * align_up(N * 4, 256) + (1 << 20) + (on_dev ? 0 : 2 * (align_up(N * 3 * sizeof(T), 256) + align_up(N * (size_t)cols * sizeof(A), 256)));
-    if (ctx_begin(c, need + 65536)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
+    return op_run(c, flags, stream, nullptr, need + 65536, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const T* d_pts; const A* d_attr = attrib;
-        if ((rc = stage_any(ar, pts, N * 3, on_dev, s, &d_pts))) break;
-        if (has_attr && (rc = stage_any(ar, attrib, N * (size_t)cols, on_dev, s, &d_attr))) break;
+        if (stage_any(ar, pts, N * 3, on_dev, s, &d_pts)) return -1;
+        if (has_attr && stage_any(ar, attrib, N * (size_t)cols, on_dev, s, &d_attr)) return -1;
         T* d_out_v = out_v; A* d_out_a = out_a;
-        if (!on_dev) { if ((rc = aalloc(ar, &d_out_v, N * 3))) break; if (has_attr && (rc = aalloc(ar, &d_out_a, N * (size_t)cols))) break; }
+        if (!on_dev) { if (aalloc(ar, &d_out_v, N * 3)) return -1; if (has_attr && aalloc(ar, &d_out_a, N * (size_t)cols)) return -1; }
         int *k0 = nullptr, *k1 = nullptr, *k2 = nullptr; unsigned* ids = nullptr;
-        if ((rc = aalloc(ar, &k0, N)) || (rc = aalloc(ar, &k1, N)) || (rc = aalloc(ar, &k2, N)) || (rc = aalloc(ar, &ids, N))) break;
+        if (aalloc(ar, &k0, N) || aalloc(ar, &k1, N) || aalloc(ar, &k2, N) || aalloc(ar, &ids, N)) return -1;
         const int nb = (int)((n + kBlock - 1) / kBlock);
         hipLaunchKernelGGL((k_voxel_keys<T>), dim3(nb), dim3(kBlock), 0, s, d_pts, (int)n, vs[0], vs[1], vs[2], mn[0], mn[1], mn[2], k0, k1, k2, ids);
-        unsigned *perm = nullptr, *flag = nullptr, *scan = nullptr;
-        const unsigned long long* skeys = nullptr;
-        if ((rc = sort_by_triple<int>(ar, s, k0, k1, k2, ids, (int)n, &perm, &skeys))) break;
-        if ((rc = runs_of<int>(ar, s, k0, k1, k2, perm, (int)n, &flag, &scan, skeys))) break;
+        unsigned* perm = nullptr; SortedRuns r;
+        if (sort_by_triple<int>(ar, s, k0, k1, k2, ids, (int)n, &perm, &r.keys)) return -1;
+        if (runs_of<int>(ar, s, k0, k1, k2, perm, (int)n, r)) return -1;
+        unsigned *flag = r.flag, *scan = r.scan;
         unsigned *start = nullptr, *keep = nullptr, *keep_scan = nullptr;
-        if ((rc = aalloc(ar, &start, N + 1)) || (rc = aalloc(ar, &keep, N)) || (rc = aalloc(ar, &keep_scan, N))) break;
+        if (aalloc(ar, &start, N + 1) || aalloc(ar, &keep, N) || aalloc(ar, &keep_scan, N)) return -1;
         hipLaunchKernelGGL(k_run_starts, dim3(nb), dim3(kBlock), 0, s, flag, scan, (int)n, start);
         const unsigned* n_runs_dev = scan + (n - 1);
         HIP_TRY(hipMemsetAsync(keep, 0, N * 4, s));
         hipLaunchKernelGGL(k_run_keep, dim3(nb), dim3(kBlock), 0, s, start, n_runs_dev, min_pts, keep);
-        if ((rc = own_inclusive_scan(ar, s, keep, keep_scan, N))) break;
+        if (own_inclusive_scan(ar, s, keep, keep_scan, N)) return -1;
         hipLaunchKernelGGL((k_voxel_means<T, A>), dim3(nb), dim3(kBlock), 0, s, d_pts, d_attr, cols, perm, start, n_runs_dev, keep, keep_scan, d_out_v, d_out_a);
         HIP_TRY(hipGetLastError());
         unsigned n_out = 0;
@@ -208,9 +221,8 @@ static int voxel_downsample_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const 
             if (has_attr) HIP_TRY(hipMemcpyAsync(out_a, d_out_a, (size_t)n_out * cols * sizeof(A), hipMemcpyDeviceToHost, s));
             HIP_WAIT(s);
         }
-    } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------- duplicate removal
@@ -222,24 +234,22 @@ static int dedup_impl(pcu_hip_ctx* c, const T* pts, int64_t n, double epsilon, T
     if (n > 0x7ffffff0ll) return fail(PCU_HIP_ERR_INVALID, "point clouds with more than 2^31-16 rows are not supported");
     typedef typename EncT<T>::type K;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t N = (size_t)n;
-    if (ctx_begin(c, 8 * align_up(N * sizeof(K), 256) + 8 * align_up(N * 4, 256) + (1 << 20) + (on_dev ? 0 : 3 * align_up(N * 3 * sizeof(T), 256)) + 65536)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
+    const size_t bytes = 8 * align_up(N * sizeof(K), 256) + 8 * align_up(N * 4, 256) + (1 << 20) + (on_dev ? 0 : 3 * align_up(N * 3 * sizeof(T), 256)) + 65536;
+    return op_run(c, flags, stream, nullptr, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const T* d_pts;
-        if ((rc = stage_any(ar, pts, N * 3, on_dev, s, &d_pts))) break;
+        if (stage_any(ar, pts, N * 3, on_dev, s, &d_pts)) return -1;
         T* d_out = out_pts; int *d_svi = out_svi, *d_svj = out_svj;
-        if (!on_dev) { if ((rc = aalloc(ar, &d_out, N * 3)) || (rc = aalloc(ar, &d_svi, N)) || (rc = aalloc(ar, &d_svj, N))) break; }
+        if (!on_dev) { if (aalloc(ar, &d_out, N * 3) || aalloc(ar, &d_svi, N) || aalloc(ar, &d_svj, N)) return -1; }
         K *k0 = nullptr, *k1 = nullptr, *k2 = nullptr; unsigned* ids = nullptr;
-        if ((rc = aalloc(ar, &k0, N)) || (rc = aalloc(ar, &k1, N)) || (rc = aalloc(ar, &k2, N)) || (rc = aalloc(ar, &ids, N))) break;
+        if (aalloc(ar, &k0, N) || aalloc(ar, &k1, N) || aalloc(ar, &k2, N) || aalloc(ar, &ids, N)) return -1;
         const int nb = (int)((n + kBlock - 1) / kBlock);
         hipLaunchKernelGGL((k_round_keys<T>), dim3(nb), dim3(kBlock), 0, s, d_pts, (int)n, (T)epsilon, k0, k1, k2, ids);
-        unsigned *perm = nullptr, *flag = nullptr, *scan = nullptr;
-        const unsigned long long* skeys = nullptr;
-        if ((rc = sort_by_triple<K>(ar, s, k0, k1, k2, ids, (int)n, &perm, &skeys))) break;
-        if ((rc = runs_of<K>(ar, s, k0, k1, k2, perm, (int)n, &flag, &scan, skeys))) break;
+        unsigned* perm = nullptr; SortedRuns r;
+        if (sort_by_triple<K>(ar, s, k0, k1, k2, ids, (int)n, &perm, &r.keys)) return -1;
+        if (runs_of<K>(ar, s, k0, k1, k2, perm, (int)n, r)) return -1;
+        unsigned *flag = r.flag, *scan = r.scan;
         hipLaunchKernelGGL((k_dedup_write<T>), dim3(nb), dim3(kBlock), 0, s, d_pts, perm, flag, scan, (int)n, d_out, d_svi, d_svj);
         HIP_TRY(hipGetLastError());
         unsigned n_out = 0;
@@ -252,9 +262,8 @@ static int dedup_impl(pcu_hip_ctx* c, const T* pts, int64_t n, double epsilon, T
             HIP_TRY(hipMemcpyAsync(out_svj, d_svj, N * 4, hipMemcpyDeviceToHost, s));
             HIP_WAIT(s);
         }
-    } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------- pairwise distances / Sinkhorn (8f-3)
@@ -265,27 +274,24 @@ static int pairwise_impl(pcu_hip_ctx* c, const T* a, const T* b, int64_t nb, int
     if (nb > 65535) return fail(PCU_HIP_ERR_INVALID, "more than 65535 batches are not supported");
     if (m > 0x7fffffffll || n > 0x7fffffffll || d > 0x7fffffffll) return fail(PCU_HIP_ERR_INVALID, "dimension too large");
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t na = (size_t)nb * m * d, nbb = (size_t)nb * n * d, no = (size_t)nb * m * n;
-    if (ctx_begin(c, on_dev ? 4096 : align_up(na * sizeof(T), 256) + align_up(nbb * sizeof(T), 256) + align_up(no * sizeof(T), 256) + 4096)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
+    const size_t bytes = on_dev ? 4096 : align_up(na * sizeof(T), 256) + align_up(nbb * sizeof(T), 256) + align_up(no * sizeof(T), 256) + 4096;
+    return op_run(c, flags, stream, nullptr, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const T *da, *db;
-        if ((rc = stage_any(ar, a, na, on_dev, s, &da)) || (rc = stage_any(ar, b, nbb, on_dev, s, &db))) break;
+        if (stage_any(ar, a, na, on_dev, s, &da) || stage_any(ar, b, nbb, on_dev, s, &db)) return -1;
         T* dout = out;
-        if (!on_dev && (rc = aalloc(ar, &dout, no))) break;
+        if (!on_dev && aalloc(ar, &dout, no)) return -1;
         const int pc = std::isnan(p_norm) ? P_TWO : pcode_of(p_norm);                 // ord=None: the 2-norm
         const long long pw_cols = (n + 63) / 64, pw_blocks = pw_cols * ((m + 3) / 4);
-        if (pw_blocks > 0x7fffffffll || nb > 65535) { rc = fail(PCU_HIP_ERR_INVALID, "pairwise_distances: problem too large (more than 2^31-1 tiles of 4 x 64 entries per batch, or more than 65535 batches)"); break; }
+        if (pw_blocks > 0x7fffffffll || nb > 65535) return fail(PCU_HIP_ERR_INVALID, "pairwise_distances: problem too large (more than 2^31-1 tiles of 4 x 64 entries per batch, or more than 65535 batches)");
         if (d > 128) hipLaunchKernelGGL((k_pairwise<T, true>), dim3((unsigned)pw_blocks, (unsigned)nb), dim3(256), 0, s, da, db, (int)m, (int)n, (int)d, pc, p_norm, dout, (int)pw_cols);
         else hipLaunchKernelGGL((k_pairwise<T, false>), dim3((unsigned)pw_blocks, (unsigned)nb), dim3(256), 0, s, da, db, (int)m, (int)n, (int)d, pc, p_norm, dout, (int)pw_cols);
         HIP_TRY(hipGetLastError());
         if (!on_dev) HIP_TRY(hipMemcpyAsync(out, dout, no * sizeof(T), hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
-    } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+        return 0;
+    });
 }
 template <typename T>
 static int sinkhorn_impl(pcu_hip_ctx* c, const T* a, const T* b, const T* M, int64_t nb, int64_t m, int64_t n, double eps, int max_iters, double stop_thresh,
@@ -294,20 +300,17 @@ static int sinkhorn_impl(pcu_hip_ctx* c, const T* a, const T* b, const T* M, int
     if (nb <= 0 || m <= 0 || n <= 0) { if (out_iters) *out_iters = 0; return 0; }
     if (nb > 65535 || m > 0x7fffffffll || n > 0x7fffffffll) return fail(PCU_HIP_ERR_INVALID, "problem too large: at most 65535 batches, 2^31-1 samples per measure");
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t nM = (size_t)nb * m * n, nu = (size_t)nb * m, nv = (size_t)nb * n;
     size_t need = 2 * (align_up(nu * sizeof(T), 256) + align_up(nv * sizeof(T), 256)) + 2 * align_up(((size_t)m / 4 + 64) * nv * sizeof(T), 256) + 8192;
     if (!on_dev) need += 2 * align_up(nM * sizeof(T), 256) + align_up(nu * sizeof(T), 256) + align_up(nv * sizeof(T), 256);
-    if (ctx_begin(c, need)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
+    return op_run(c, flags, stream, nullptr, need, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         SinkArgs<T> k;
-        if ((rc = stage_any(ar, a, nu, on_dev, s, &k.a)) || (rc = stage_any(ar, b, nv, on_dev, s, &k.b)) || (rc = stage_any(ar, M, nM, on_dev, s, &k.M))) break;
+        if (stage_any(ar, a, nu, on_dev, s, &k.a) || stage_any(ar, b, nv, on_dev, s, &k.b) || stage_any(ar, M, nM, on_dev, s, &k.M)) return -1;
         T* dP = out_P;
-        if (!on_dev && (rc = aalloc(ar, &dP, nM))) break;
+        if (!on_dev && aalloc(ar, &dP, nM)) return -1;
         int* flagsd = nullptr;
-        if ((rc = aalloc(ar, &k.u, nu)) || (rc = aalloc(ar, &k.v, nv)) || (rc = aalloc(ar, &k.du, nu)) || (rc = aalloc(ar, &k.dv, nv)) || (rc = aalloc(ar, &flagsd, 16))) break;
+        if (aalloc(ar, &k.u, nu) || aalloc(ar, &k.v, nv) || aalloc(ar, &k.du, nu) || aalloc(ar, &k.dv, nv) || aalloc(ar, &flagsd, 16)) return -1;
         HIP_TRY(hipMemsetAsync(k.u, 0, nu * sizeof(T), s)); HIP_TRY(hipMemsetAsync(k.v, 0, nv * sizeof(T), s));      // u = zeros_like(a), v = zeros_like(b) (:99-100)
         HIP_TRY(hipMemsetAsync(flagsd, 0, 16 * sizeof(int), s));
         k.nb = (int)nb; k.m = (int)m; k.n = (int)n; k.eps = (T)eps; k.done = flagsd;
@@ -328,7 +331,7 @@ static int sinkhorn_impl(pcu_hip_ctx* c, const T* a, const T* b, const T* M, int
             rows_per_slab = (int)((m + n_slabs - 1) / n_slabs);
         }
         T *part_mx = nullptr, *part_sum = nullptr;
-        if ((rc = aalloc(ar, &part_mx, (size_t)n_slabs * nv)) || (rc = aalloc(ar, &part_sum, (size_t)n_slabs * nv))) break;
+        if (aalloc(ar, &part_mx, (size_t)n_slabs * nv) || aalloc(ar, &part_sum, (size_t)n_slabs * nv)) return -1;
         int host_flags[2] = {0, 0};
         for (int it = 0; it < max_iters; ++it) {
             if (fused) {
@@ -349,16 +352,15 @@ static int sinkhorn_impl(pcu_hip_ctx* c, const T* a, const T* b, const T* M, int
         }
         HIP_TRY(hipGetLastError());
         const long long pl_cols = (n + 255) / 256;
-        if (pl_cols * m > 0x7fffffffll) { rc = fail(PCU_HIP_ERR_INVALID, "sinkhorn: cost matrix too large (more than 2^31-1 row segments of 256 entries per batch)"); break; }
+        if (pl_cols * m > 0x7fffffffll) return fail(PCU_HIP_ERR_INVALID, "sinkhorn: cost matrix too large (more than 2^31-1 row segments of 256 entries per batch)");
         hipLaunchKernelGGL((k_sink_plan<T>), dim3((unsigned)(pl_cols * m), (unsigned)nb), dim3(256), 0, s, k, dP, (int)pl_cols);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(host_flags, flagsd, sizeof host_flags, hipMemcpyDeviceToHost, s));
         if (!on_dev) HIP_TRY(hipMemcpyAsync(out_P, dP, nM * sizeof(T), hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         if (out_iters) *out_iters = host_flags[1];
-    } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+        return 0;
+    });
 }
 template <typename T>
 static int dot_impl(pcu_hip_ctx* c, const T* x, const T* y, int64_t count, double* out, unsigned flags, void* stream) {
@@ -366,14 +368,11 @@ static int dot_impl(pcu_hip_ctx* c, const T* x, const T* y, int64_t count, doubl
     *out = 0.0;
     if (count <= 0) return 0;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     constexpr int kParts = 1024;
-    if (ctx_begin(c, (on_dev ? 0 : 2 * align_up((size_t)count * sizeof(T), 256)) + 65536)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
+    return op_run(c, flags, stream, nullptr, (on_dev ? 0 : 2 * align_up((size_t)count * sizeof(T), 256)) + 65536, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const T *dx, *dy; double* part = nullptr;
-        if ((rc = stage_any(ar, x, (size_t)count, on_dev, s, &dx)) || (rc = stage_any(ar, y, (size_t)count, on_dev, s, &dy)) || (rc = aalloc(ar, &part, 2 * kParts))) break;
+        if (stage_any(ar, x, (size_t)count, on_dev, s, &dx) || stage_any(ar, y, (size_t)count, on_dev, s, &dy) || aalloc(ar, &part, 2 * kParts)) return -1;
         hipLaunchKernelGGL((k_dot_partial<T>), dim3(kParts), dim3(256), 0, s, dx, dy, (size_t)count, part);
         HIP_TRY(hipGetLastError());
         double h[2 * kParts];
@@ -381,7 +380,6 @@ static int dot_impl(pcu_hip_ctx* c, const T* x, const T* y, int64_t count, doubl
         HIP_WAIT(s);
         double hi = 0, lo = 0; for (int i = 0; i < kParts; ++i) dd_add(hi, lo, h[2 * i], h[2 * i + 1]);
         *out = hi;
-    } while (0);
-    ctx_end(c);
-    return rc ? (rc < 0 ? rc : PCU_HIP_ERR_RUNTIME) : 0;
+        return 0;
+    });
 }

@@ -1,5 +1,6 @@
 // csrc/voxelize_host.h -- host orchestration of voxelize_triangle_mesh, sparse_voxel_grid_boundary and voxel_grid_geometry (kernels and
-// contract: voxelize.h). Included by pcu_hip.hip after mesh_sample_host.h (ms_mesh_stage / ms_mesh_refuse) and voxel_host.h (sort, scan).
+// contract: voxelize.h). Included by pcu_hip.hip after the operator frame and the parking functions, voxel_host.h (sort_keys, rank_runs,
+// the scan), mesh_host.h (mesh_validate, int_kind_check) and mesh_sample_host.h (ms_mesh_stage / ms_mesh_refuse).
 #pragma once
 
 constexpr int64_t kVxMaxRows = 0x7ffffff0ll;                 // rows one sort takes
@@ -14,17 +15,16 @@ static int vx_grid_check(const double* size, const double* origin, const char* s
     }
     return 0;
 }
-static int vx_kind_bytes(int kind) { return (kind == 0 || kind == 2) ? 4 : 8; }
 static int vx_bits_between(int lo, int hi) { return bits_of((unsigned long long)((unsigned)(lo + (1 << 20)) ^ (unsigned)(hi + (1 << 20)))); }
 
-// The rows of the context's last voxelization wait in its `aux` block for pcu_hip_voxelize_take: the row count is the one value the host
-// has to see before the caller's output can exist.
+// The rows of the context's last voxelization are parked for pcu_hip_voxelize_take: the row count is the one value the host has to see
+// before the caller's output can exist.
 static int vx_park(pcu_hip_ctx* c, hipStream_t s, const int* rows, int64_t m) {
-    c->vox_rows = -1;
-    if (aux_reserve(c, (size_t)m * 12 + 256)) return -1;
-    HIP_TRY(hipMemcpyAsync(c->aux, rows, (size_t)m * 12, hipMemcpyDeviceToDevice, s));
+    char *seg0 = nullptr, *seg1 = nullptr;
+    if (park_reserve(c, (size_t)m * 12, 0, &seg0, &seg1)) return -1;
+    HIP_TRY(hipMemcpyAsync(seg0, rows, (size_t)m * 12, hipMemcpyDeviceToDevice, s));
     HIP_WAIT(s);
-    c->vox_rows = m;
+    park_commit(c, Parked::VoxelRows, m, 0);
     return 0;
 }
 
@@ -35,18 +35,14 @@ static int voxelize_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, const double* si
                          pcu_hip_stats* st) {
     if (!c || !out_rows) return fail(PCU_HIP_ERR_INVALID, "null context / out_rows");
     *out_rows = 0;
-    c->vox_rows = -1;
+    c->parked = ParkedResult();
     if (int rc = mesh_validate(m.nv, m.nf, 0, m.f_kind)) return rc;
     VxGrid g;
     if (int rc = vx_grid_check(size, origin, "Invalid voxel size", &g)) return rc;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t NF = (size_t)m.nf;
-    if (int rc = ms_begin(c, st, ms_mesh_bytes(m, on_dev) + align_up(NF * 24, 256) + 2 * align_up(NF * 8, 256) + (1 << 20))) return rc;
-    c->time_phases = flags & PCU_HIP_TIME_PHASES;
-    Arena ar{c};
-    Timer tm{c, s, st};             // marks 0-1: extent and scan, 2-3: test pass, 4-5: emit pass, 5-6: sort and unique
-    auto run = [&]() -> int {
+    const size_t bytes = ms_mesh_bytes(m, flags & PCU_HIP_PTRS_ON_DEVICE) + align_up(NF * 24, 256) + 2 * align_up(NF * 8, 256) + (1 << 20);
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: extent and scan, 2-3: test pass, 4-5: emit pass, 5-6: sort and unique
         MsMesh<T> M; MsSeen<T> seen;
         tm.mark(0);
         if (ms_mesh_stage(ar, s, m, on_dev, M)) return -1;
@@ -89,29 +85,25 @@ static int voxelize_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, const double* si
         if (kept > (unsigned long long)kVxMaxRows) return fail(PCU_HIP_ERR_INVALID, "voxelize_triangle_mesh: more than 2^31-16 overlapping (face, voxel) pairs are not supported");
         // emit pass, sort, unique
         const int K = (int)kept;
-        unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
-        if (aalloc(ar, &ka, (size_t)K) || aalloc(ar, &kb, (size_t)K) || aalloc(ar, &ia, (size_t)K) || aalloc(ar, &ib, (size_t)K)) return -1;
+        SortedRuns r; int* rows = nullptr;
+        if (aalloc(ar, &r.keys, (size_t)K) || aalloc(ar, &rows, (size_t)K * 3)) return -1;
         tm.mark(4);
         for (unsigned long long s0 = 0; s0 < nslices; s0 += kVxLaunchSlices) {
             if (s0) HIP_WAIT(s);
             const unsigned nb = (unsigned)std::min(kVxLaunchSlices, nslices - s0);
             hipLaunchKernelGGL(k_vx_emit, dim3(nb), dim3(kVxThreads), 0, s, (const int*)ext, (const unsigned long long*)C, nf, s0, (const unsigned long long*)words,
-                               (const unsigned long long*)bcnt, (const unsigned long long*)bscan, ka);
+                               (const unsigned long long*)bcnt, (const unsigned long long*)bscan, r.keys);
         }
         HIP_TRY(hipGetLastError());
         tm.mark(5);
         const int bits = 3 * std::max(vx_bits_between(hh.lo[0], hh.hi[0]), std::max(vx_bits_between(hh.lo[1], hh.hi[1]), vx_bits_between(hh.lo[2], hh.hi[2])));
-        if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, K, bits)) return -1;
-        unsigned *flag = nullptr, *scan = nullptr; int* rows = nullptr;
-        if (aalloc(ar, &flag, (size_t)K) || aalloc(ar, &scan, (size_t)K) || aalloc(ar, &rows, (size_t)K * 3)) return -1;
-        const int nbk = (K + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(k_run_heads_sorted, dim3(nbk), dim3(kBlock), 0, s, (const unsigned long long*)ka, K, flag);
-        if (own_inclusive_scan(ar, s, (const unsigned*)flag, scan, (size_t)K)) return -1;
-        hipLaunchKernelGGL(k_vx_rows, dim3(nbk), dim3(kBlock), 0, s, (const unsigned long long*)ka, (const unsigned*)flag, (const unsigned*)scan, K, rows);
+        if (sort_keys(ar, s, r, K, bits) || rank_runs(ar, s, r, K)) return -1;
+        hipLaunchKernelGGL(k_vx_rows, dim3((K + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, (const unsigned*)r.flag, (const unsigned*)r.scan, K,
+                           rows);
         HIP_TRY(hipGetLastError());
         tm.mark(6);
         unsigned n_rows = 0;
-        HIP_TRY(hipMemcpyAsync(&n_rows, scan + (K - 1), 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&n_rows, r.scan + (K - 1), 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         if (vx_park(c, s, rows, (int64_t)n_rows)) return -1;
         *out_rows = (int64_t)n_rows;
@@ -120,20 +112,12 @@ static int voxelize_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, const double* si
             st->ms_index = tm.span(0, 1); st->ms_search = tm.span(2, 3); st->ms_tie = tm.span(4, 5); st->ms_kernel_search = tm.span(5, 6); st->ms_total = tm.span(0, 6);
         }
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }
 // The rows of this context's last pcu_hip_voxelize_triangle_mesh_*: out_ijk (rows, 3) int32. They can be taken once.
 static int voxelize_take_impl(pcu_hip_ctx* c, int64_t rows, int32_t* out_ijk, unsigned flags, void* stream) {
     if (!c || !out_ijk) return fail(PCU_HIP_ERR_INVALID, "null context / out_ijk");
-    if (c->vox_rows < 0 || rows != c->vox_rows) return fail(PCU_HIP_ERR_INVALID, "pcu_hip_voxelize_take: this context holds no voxelization of %lld rows", (long long)rows);
-    hipStream_t s = pick_stream(c, flags, stream);
-    if (rows > 0) {
-        HIP_TRY(hipMemcpyAsync(out_ijk, c->aux, (size_t)rows * 12, (flags & PCU_HIP_PTRS_ON_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        HIP_WAIT(s);                            // (a cancelled copy leaves the rows where they are: the call can be issued again)
-    }
-    c->vox_rows = -1;
-    return 0;
+    return park_take(c, Parked::VoxelRows, rows, 0, out_ijk, nullptr, flags, stream, "pcu_hip_voxelize_take: this context holds no voxelization of %lld rows");
 }
 
 // sparse_voxel_grid_boundary (src/sparse_voxel_grid.cpp:473-522). out_idx (n) worst case; *out_count rows are written, ascending.
@@ -141,39 +125,35 @@ static int voxel_boundary_impl(pcu_hip_ctx* c, const void* ijk, int64_t n, int k
     if (!c || !out_count) return fail(PCU_HIP_ERR_INVALID, "null context / out_count");
     *out_count = 0;
     if (n <= 0) return fail(PCU_HIP_ERR_INVALID, "Invalid grid_coordinates has zero rows!");
-    if (kind < 0 || kind > 3) return fail(PCU_HIP_ERR_INVALID, "kind must be one of PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64");
+    if (int rc = int_kind_check(kind)) return rc;
     if (n > kVxMaxRows) return fail(PCU_HIP_ERR_INVALID, "voxel grids with more than 2^31-16 rows are not supported");
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t N = (size_t)n;
-    if (ctx_begin(c, 4 * align_up(N * 8, 256) + 4 * align_up(N * 4, 256) + align_up(256 * ((N + kRsWaveTile - 1) / kRsWaveTile) * 4, 256) +
-                         (on_dev ? 0 : align_up(N * 3 * vx_kind_bytes(kind), 256)) + (1 << 20))) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    auto run = [&]() -> int {
+    const size_t bytes = sort_bytes(N) + scan_bytes(N) + 2 * align_up(N * 8, 256) + 2 * align_up(N * 4, 256) +      // (codes and rows; flags and scan)
+                         ((flags & PCU_HIP_PTRS_ON_DEVICE) ? 0 : align_up(N * 3 * int_kind_bytes(kind), 256)) + (1 << 20);
+    return op_run(c, flags, stream, nullptr, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const char* d_in = nullptr;
-        if (stage_any(ar, static_cast<const char*>(ijk), N * 3 * vx_kind_bytes(kind), on_dev, s, &d_in)) return -1;
-        unsigned long long *codes = nullptr, *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr, *flag = nullptr, *scan = nullptr; int* d_bad = nullptr;
+        if (stage_any(ar, static_cast<const char*>(ijk), N * 3 * int_kind_bytes(kind), on_dev, s, &d_in)) return -1;
+        unsigned long long* codes = nullptr; SortedRuns r; int* d_bad = nullptr;
         long long* d_out = reinterpret_cast<long long*>(out_idx);
-        if (aalloc(ar, &codes, N) || aalloc(ar, &ka, N) || aalloc(ar, &kb, N) || aalloc(ar, &ia, N) || aalloc(ar, &ib, N) || aalloc(ar, &flag, N) ||
-            aalloc(ar, &scan, N) || aalloc(ar, &d_bad, 1) || (!on_dev && aalloc(ar, &d_out, N))) return -1;
+        if (aalloc(ar, &codes, N) || aalloc(ar, &r.keys, N) || aalloc(ar, &d_bad, 1) || (!on_dev && aalloc(ar, &d_out, N))) return -1;
         const int nn = (int)n, nb = (nn + kBlock - 1) / kBlock;
         HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_vb_codes, dim3(nb), dim3(kBlock), 0, s, (const void*)d_in, kind, nn, codes, ka, d_bad);
-        if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, nn, 63)) return -1;
-        hipLaunchKernelGGL(k_vb_flag, dim3(nb), dim3(kBlock), 0, s, (const unsigned long long*)codes, (const unsigned long long*)ka, nn, flag);
-        if (own_inclusive_scan(ar, s, (const unsigned*)flag, scan, N)) return -1;
-        hipLaunchKernelGGL(k_vb_rows, dim3(nb), dim3(kBlock), 0, s, (const unsigned*)flag, (const unsigned*)scan, nn, d_out);
+        hipLaunchKernelGGL(k_vb_codes, dim3(nb), dim3(kBlock), 0, s, (const void*)d_in, kind, nn, codes, r.keys, d_bad);
+        if (sort_keys(ar, s, r, nn, 63)) return -1;
+        if (rank_flags(ar, s, r, nn, [&, s = s](unsigned* flag) {
+                hipLaunchKernelGGL(k_vb_flag, dim3(nb), dim3(kBlock), 0, s, (const unsigned long long*)codes, (const unsigned long long*)r.keys, nn, flag);
+            })) return -1;
+        hipLaunchKernelGGL(k_vb_rows, dim3(nb), dim3(kBlock), 0, s, (const unsigned*)r.flag, (const unsigned*)r.scan, nn, d_out);
         HIP_TRY(hipGetLastError());
         int bad = 0; unsigned m = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&m, scan + (N - 1), 4, hipMemcpyDeviceToHost, s));
+        if (read_flag_and_last(s, d_bad, r.scan, N, &bad, &m)) return -1;
         HIP_WAIT(s);
         if (bad) return fail(PCU_HIP_ERR_INVALID, "Invalid vertex leads to an overflow integer. Perhaps grid_size is too small.");
         if (!on_dev && m) { HIP_TRY(hipMemcpyAsync(out_idx, d_out, (size_t)m * 8, hipMemcpyDeviceToHost, s)); HIP_WAIT(s); }
         *out_count = (int64_t)m;
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }
 
 // voxel_grid_geometry (src/mesh_for_voxels.cpp:11-79): out_v (8 n, 3) float, out_f (12 n, 3) int32
@@ -181,18 +161,16 @@ static int voxel_geometry_impl(pcu_hip_ctx* c, const void* ijk, int64_t n, int k
                                unsigned flags, void* stream) {
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
     if (n <= 0) return fail(PCU_HIP_ERR_INVALID, "Invalid input point cloud with zero points: points must have shape (n, 3) (n > 0). Got points.shape =(%lld, 3).", (long long)n);
-    if (kind < 0 || kind > 3) return fail(PCU_HIP_ERR_INVALID, "kind must be one of PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64");
+    if (int rc = int_kind_check(kind)) return rc;
     VxGrid g;
     if (int rc = vx_grid_check(size, origin, "Voxel size must be positive", &g)) return rc;
     if (8 * n > 0x7fffffffll) return fail(PCU_HIP_ERR_INVALID, "voxel geometry with more than 2^31-1 vertices does not fit the int32 faces");
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
     const size_t N = (size_t)n;
-    if (ctx_begin(c, on_dev ? 4096 : align_up(N * 3 * vx_kind_bytes(kind), 256) + align_up(N * 96, 256) + align_up(N * 144, 256) + 4096)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    auto run = [&]() -> int {
+    const size_t bytes = (flags & PCU_HIP_PTRS_ON_DEVICE) ? 4096 : align_up(N * 3 * int_kind_bytes(kind), 256) + align_up(N * 96, 256) + align_up(N * 144, 256) + 4096;
+    return op_run(c, flags, stream, nullptr, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
         const char* d_in = nullptr;
-        if (stage_any(ar, static_cast<const char*>(ijk), N * 3 * vx_kind_bytes(kind), on_dev, s, &d_in)) return -1;
+        if (stage_any(ar, static_cast<const char*>(ijk), N * 3 * int_kind_bytes(kind), on_dev, s, &d_in)) return -1;
         float* d_v = out_v; int* d_f = out_f;
         if (!on_dev && (aalloc(ar, &d_v, N * 24) || aalloc(ar, &d_f, N * 36))) return -1;
         hipLaunchKernelGGL(k_vg_geometry, dim3((unsigned)((12 * n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, (const void*)d_in, kind, (long long)n, g, gap, d_v, d_f);
@@ -203,6 +181,5 @@ static int voxel_geometry_impl(pcu_hip_ctx* c, const void* ijk, int64_t n, int k
         }
         HIP_WAIT(s);
         return 0;
-    };
-    return attempt_exit(c, run());
+    });
 }
