@@ -46,6 +46,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "components.h"
 #include "marching_cubes.h"
 #include "mesh_smooth.h"
+#include "mesh_repair.h"
 
 using namespace pcu;
 
@@ -2445,6 +2446,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "components_host.h"
 #include "marching_cubes_host.h"
 #include "mesh_smooth_host.h"
+#include "mesh_repair_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2827,6 +2829,25 @@ int pcu_hip_laplacian_smooth_mesh_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, 
 PCU_MS_ABI(f32, float)
 PCU_MS_ABI(f64, double)
 #undef PCU_MS_ABI
+// remove_mesh_vertices, remove_unreferenced_mesh_vertices, deduplicate_mesh_vertices and orient_mesh_faces (mesh_repair.h, mesh_repair_host.h)
+#define PCU_MR_ABI(SUF, T)                                                                                                                            \
+int pcu_hip_remove_mesh_vertices_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const unsigned char* mask,     \
+                                       T* out_v, void* out_f, int64_t* out_nv, int64_t* out_nf, unsigned flags, void* stream, pcu_hip_stats* st) {   \
+    CallGuard dg(c); return abi_rc(remove_mesh_vertices_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, mask, out_v, out_f, out_nv, out_nf, flags, stream, st)); } \
+int pcu_hip_remove_unreferenced_mesh_vertices_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, T* out_v,         \
+                                                    void* out_f, void* out_corr_v, void* out_corr_f, int64_t* out_nv, unsigned flags, void* stream,  \
+                                                    pcu_hip_stats* st) {                                                                             \
+    CallGuard dg(c); return abi_rc(remove_unreferenced_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, out_v, out_f, out_corr_v, out_corr_f, out_nv, flags, stream, st)); } \
+int pcu_hip_deduplicate_mesh_vertices_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, double epsilon, T* out_v, \
+                                            void* out_f, int32_t* out_svi, int32_t* out_svj, int64_t* out_nv, int64_t* out_nf, unsigned flags,       \
+                                            void* stream, pcu_hip_stats* st) {                                                                       \
+    CallGuard dg(c); return abi_rc(dedup_mesh_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, epsilon, out_v, out_f, out_svi, out_svj, out_nv, out_nf, flags, stream, st)); }
+PCU_MR_ABI(f32, float)
+PCU_MR_ABI(f64, double)
+#undef PCU_MR_ABI
+int pcu_hip_orient_mesh_faces(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_f, void* out_c, int64_t* out_patches, unsigned flags,
+                              void* stream, pcu_hip_stats* st) {
+    CallGuard dg(c); return abi_rc(orient_mesh_faces_impl(c, f, nf, f_kind, nv, out_f, out_c, out_patches, flags, stream, st)); }
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {

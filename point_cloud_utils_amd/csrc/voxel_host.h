@@ -227,33 +227,45 @@ static int voxel_downsample_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const 
 
 // ---------------------------------------------------------------------------------------------------- duplicate removal
 // deduplicate_point_cloud (src/remove_duplicates.cpp:108-129). out_pts (n,3), out_svi (n) worst case; out_svj (n); *out_count = unique rows.
+// What dedup_device takes from the arena for n rows.
+template <typename T>
+static size_t dedup_bytes(size_t n) { return 8 * align_up(n * sizeof(typename EncT<T>::type), 256) + 8 * align_up(n * 4, 256) + (1 << 20) + 65536; }
+// The device side, for the callers that go on with svj (mesh_repair_host.h): d_out (n,3), d_svi (n), d_svj (n) on the device; *n_out_dev
+// points at the number of unique rows, on the device. One wait inside (sort_by_triple reads the keys' ranges).
+template <typename T>
+static int dedup_device(Arena& ar, hipStream_t s, const T* d_pts, int n, double epsilon, T* d_out, int* d_svi, int* d_svj, const unsigned** n_out_dev) {
+    typedef typename EncT<T>::type K;
+    const size_t N = (size_t)n;
+    K *k0 = nullptr, *k1 = nullptr, *k2 = nullptr; unsigned* ids = nullptr;
+    if (aalloc(ar, &k0, N) || aalloc(ar, &k1, N) || aalloc(ar, &k2, N) || aalloc(ar, &ids, N)) return -1;
+    const int nb = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL((k_round_keys<T>), dim3(nb), dim3(kBlock), 0, s, d_pts, n, (T)epsilon, k0, k1, k2, ids);
+    unsigned* perm = nullptr; SortedRuns r;
+    if (sort_by_triple<K>(ar, s, k0, k1, k2, ids, n, &perm, &r.keys)) return -1;
+    if (runs_of<K>(ar, s, k0, k1, k2, perm, n, r)) return -1;
+    hipLaunchKernelGGL((k_dedup_write<T>), dim3(nb), dim3(kBlock), 0, s, d_pts, perm, r.flag, r.scan, n, d_out, d_svi, d_svj);
+    HIP_TRY(hipGetLastError());
+    *n_out_dev = r.scan + (N - 1);
+    return 0;
+}
 template <typename T>
 static int dedup_impl(pcu_hip_ctx* c, const T* pts, int64_t n, double epsilon, T* out_pts, int32_t* out_svi, int32_t* out_svj, int64_t* out_count, unsigned flags, void* stream) {
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
     if (n <= 0) { *out_count = 0; return 0; }
     if (n > 0x7ffffff0ll) return fail(PCU_HIP_ERR_INVALID, "point clouds with more than 2^31-16 rows are not supported");
-    typedef typename EncT<T>::type K;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
     const size_t N = (size_t)n;
-    const size_t bytes = 8 * align_up(N * sizeof(K), 256) + 8 * align_up(N * 4, 256) + (1 << 20) + (on_dev ? 0 : 3 * align_up(N * 3 * sizeof(T), 256)) + 65536;
+    const size_t bytes = dedup_bytes<T>(N) + (on_dev ? 0 : 3 * align_up(N * 3 * sizeof(T), 256));
     return op_run(c, flags, stream, nullptr, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;
         const T* d_pts;
         if (stage_any(ar, pts, N * 3, on_dev, s, &d_pts)) return -1;
         T* d_out = out_pts; int *d_svi = out_svi, *d_svj = out_svj;
         if (!on_dev) { if (aalloc(ar, &d_out, N * 3) || aalloc(ar, &d_svi, N) || aalloc(ar, &d_svj, N)) return -1; }
-        K *k0 = nullptr, *k1 = nullptr, *k2 = nullptr; unsigned* ids = nullptr;
-        if (aalloc(ar, &k0, N) || aalloc(ar, &k1, N) || aalloc(ar, &k2, N) || aalloc(ar, &ids, N)) return -1;
-        const int nb = (int)((n + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL((k_round_keys<T>), dim3(nb), dim3(kBlock), 0, s, d_pts, (int)n, (T)epsilon, k0, k1, k2, ids);
-        unsigned* perm = nullptr; SortedRuns r;
-        if (sort_by_triple<K>(ar, s, k0, k1, k2, ids, (int)n, &perm, &r.keys)) return -1;
-        if (runs_of<K>(ar, s, k0, k1, k2, perm, (int)n, r)) return -1;
-        unsigned *flag = r.flag, *scan = r.scan;
-        hipLaunchKernelGGL((k_dedup_write<T>), dim3(nb), dim3(kBlock), 0, s, d_pts, perm, flag, scan, (int)n, d_out, d_svi, d_svj);
-        HIP_TRY(hipGetLastError());
+        const unsigned* n_out_dev = nullptr;
+        if (dedup_device<T>(ar, s, d_pts, (int)n, epsilon, d_out, d_svi, d_svj, &n_out_dev)) return -1;
         unsigned n_out = 0;
-        HIP_TRY(hipMemcpyAsync(&n_out, scan + (n - 1), 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&n_out, n_out_dev, 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         *out_count = (int64_t)n_out;
         if (!on_dev) {
