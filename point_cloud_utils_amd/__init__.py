@@ -25,6 +25,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import Stats, set_cell_occupancy, device_count  # noqa: F401
+from ._call import (_DT_FAST, _ENV_FLAGS, _FN, _TIMING, _Dev, _Handle, _dtype_name, _flags, _fn, _is_torch,  # noqa: F401
+                    _last_stats, _record, _shape2)
+from ._checks import _check_float
 
 __all__ = ["k_nearest_neighbors", "one_sided_hausdorff_distance", "hausdorff_distance", "chamfer_distance",
            "estimate_point_cloud_normals_knn", "estimate_point_cloud_normals_ball",
@@ -43,12 +46,6 @@ __all__ = ["k_nearest_neighbors", "one_sided_hausdorff_distance", "hausdorff_dis
            "remove_mesh_vertices", "remove_unreferenced_mesh_vertices", "deduplicate_mesh_vertices", "orient_mesh_faces",
            "last_stats", "set_timing", "set_cell_occupancy", "device_count", "DatasetIndex", "cancel"]
 
-_last_stats = [None]      # the Stats struct of the most recent call (turned into a dict on demand)
-# PCU_HIP_NO_TIE_ORDER=1: skip the kd-tree tie-order resolver (exact ties then ordered by (d2, row)); for experiments.
-_ENV_FLAGS = _lib.NO_TIE_ORDER if __import__("os").environ.get("PCU_HIP_NO_TIE_ORDER", "0") not in ("", "0") else 0
-_TIMING = [int(__import__("os").environ.get("PCU_HIP_TIMING", "0") or 0)]
-
-
 def cancel():
     """Ask the call that is in flight (any thread of this process) to stop: it returns early and raises KeyboardInterrupt in its caller, as
     Ctrl-C does -- the reference polls PyErr_CheckSignals() inside its search loops (src/point_cloud_distance.cpp:60-75, 96-98). Callable from
@@ -65,53 +62,15 @@ def set_timing(level):
     return old
 
 
-def _flags():
-    return _ENV_FLAGS | (_lib.TIME_KERNELS if _TIMING[0] >= 1 else 0) | (_lib.TIME_PHASES if _TIMING[0] >= 2 else 0)
-
-
 def last_stats():
     """Statistics of the most recent call (escalations, tie handling, device milliseconds)."""
     st = _last_stats[0]
     return st.as_dict() if st is not None else {}
 
 
-def _is_torch(a):
-    return type(a).__module__.startswith("torch") and hasattr(a, "data_ptr")
-
-
-def _shape2(a):
-    sh = tuple(a.shape)
-    if len(sh) == 2:
-        return sh
-    if len(sh) == 1:            # numpyeigen maps a 1-D array to a column vector
-        return (sh[0], 1)
-    raise ValueError(f"Invalid number of dimensions ({len(sh)}): expected a matrix of shape (n, 3).")
-
-
-_DT_FAST = {np.dtype("float32"): "float32", np.dtype("float64"): "float64"}
-
-
-def _dtype_name(a):
-    dt = getattr(a, "dtype", None)
-    try:
-        name = _DT_FAST.get(dt)            # the two supported dtypes, numpy or torch, without string work
-    except TypeError:
-        name = None
-    if name is not None:
-        return name
-    if _is_torch(a):
-        name = str(a.dtype).replace("torch.", "")
-        if name in ("float32", "float64"):
-            _DT_FAST[a.dtype] = name
-        return name
-    return np.asarray(a).dtype.name
-
-
 def _check_pair(a, b, aname, bname, zero_fmt, dim_fmt):
     """dtype / shape validation in the order of src/point_cloud_distance.cpp:136-149 (and :195-208)."""
-    da, db = _dtype_name(a), _dtype_name(b)
-    if da not in ("float32", "float64"):
-        raise ValueError(f"Invalid scalar type ({da}) for argument '{aname}'. Expected one of ['float32', 'float64'].")
+    da, db = _check_float(a, aname), _dtype_name(b)
     if db != da:
         raise ValueError(f"Invalid scalar type ({db}) for argument '{bname}'. Expected it to match argument "
                          f"'{aname}' which is of type {da}.")
@@ -133,71 +92,12 @@ _HD_DIM = ("Only 3D inputs are supported: source and targets must have shape (n,
            "Got source.shape = ({}, {}), target.shape = ({}, {}).")
 
 
-class _Dev:
-    """Resolved inputs of one call: contiguous buffers, pointers, device, stream, flags."""
-
-    def __init__(self, a, b):
-        self.torch = _is_torch(a) or _is_torch(b)
-        if self.torch:
-            import torch
-            if not (_is_torch(a) and _is_torch(b)) or not (a.is_cuda and b.is_cuda) or a.device != b.device:
-                raise ValueError("torch inputs must both be CUDA/HIP tensors on the same device")
-            self.a, self.b = a.contiguous(), b.contiguous()
-            self.device = a.device.index if a.device.index is not None else torch.cuda.current_device()
-            self.tdev = a.device
-            # the library launches on torch's current stream, so its kernels are ordered after the producers of the input
-            # tensors (torch's default stream is the legacy NULL stream, handle 0: STREAM_GIVEN makes NULL mean exactly that)
-            raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)       # (the handle without building a Stream object: ~2 us per call)
-            self.stream = raw(self.device) if raw is not None else torch.cuda.current_stream(a.device).cuda_stream
-            self.flags = _lib.PTRS_ON_DEVICE | _flags() | _lib.STREAM_GIVEN
-            self.pa, self.pb = self.a.data_ptr(), self.b.data_ptr()
-            self.np_dtype = np.float32 if a.dtype == torch.float32 else np.float64
-            self.t_dtype = a.dtype
-        else:
-            self.a, self.b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-            self.device = _lib.default_device()
-            self.stream = None
-            self.flags = _flags()
-            self.pa, self.pb = self.a.ctypes.data, self.b.ctypes.data
-            self.np_dtype = self.a.dtype.type
-        self.suffix = "f32" if self.np_dtype == np.float32 else "f64"
-        self.ctx = _lib.ctx(self.device)
-
-    def empty(self, shape, kind):
-        """kind: 'T' (input dtype) or 'i64'."""
-        if self.torch:
-            import torch
-            return torch.empty(shape, dtype=self.t_dtype if kind == "T" else torch.int64, device=self.tdev)
-        return np.empty(shape, dtype=self.np_dtype if kind == "T" else np.int64)
-
-    @staticmethod
-    def ptr(x):
-        if x is None:
-            return None
-        return x.data_ptr() if _is_torch(x) else x.ctypes.data
-
-
-def _record(st):
-    _last_stats[0] = st
-
-
 def _squeeze(dists, corrs, n, k):
     """npe::move(..., squeeze): singleton dimensions are dropped, as numpy.squeeze does -- (n,) for k == 1 (pinned by the
     reference's tests/test_examples.py:363-368), (k,) for n == 1, 0-d for n == k == 1 (unpinned in the reference)."""
     if n == 1 and k == 1:
         return dists.reshape(()), corrs.reshape(())
     return dists.reshape(-1), corrs.reshape(-1)
-
-
-_FN = {}
-
-
-def _fn(op, suffix):
-    """Entry point `pcu_hip_<op>_<suffix>` (looked up once)."""
-    f = _FN.get((op, suffix))
-    if f is None:
-        f = _FN[(op, suffix)] = getattr(_lib.lib(), f"pcu_hip_{op}_{suffix}")
-    return f
 
 
 def k_nearest_neighbors(query_points, dataset_points, k, squared_distances=False, max_points_per_leaf=10,
@@ -357,7 +257,7 @@ def chamfer_distance(x, y, return_index=False, p_norm=2, max_points_per_leaf=10)
     return cham_dist
 
 
-class DatasetIndex:
+class DatasetIndex(_Handle):
     """A dataset kept on the GPU together with its search index (not in the reference API, which rebuilds its kd-tree on
     every call -- three times, src/point_cloud_distance.cpp:41-42): build once, query many times.
 
@@ -367,34 +267,26 @@ class DatasetIndex:
     `dataset_points`: (m, 3) float32 / float64, numpy or CUDA/HIP torch tensor (copied; the caller's array can go away).
     `k_hint` sizes the grid cells for the k that will mostly be asked for; any k > 0 is answered exactly.
     Queries must have the dataset's dtype. The index lives on one GPU; call close() (or use `with`) to free it."""
+    _noun, _destroy = "index", "pcu_hip_index_destroy"
 
     def __init__(self, dataset_points, k_hint=1):
-        da = _dtype_name(dataset_points)
-        if da not in ("float32", "float64"):
-            raise ValueError(f"Invalid scalar type ({da}) for argument 'dataset_points'. Expected one of ['float32', 'float64'].")
+        _check_float(dataset_points, "dataset_points")
         sh = _shape2(dataset_points)
         if sh[0] == 0 or sh[1] != 3:
             raise ValueError(f"dataset_points must have shape (m, 3) with m > 0. Got dataset_points.shape = ({sh[0]}, {sh[1]}).")
         d = _Dev(dataset_points, dataset_points)
-        self._suffix, self._np_dtype, self._torch, self._device = d.suffix, d.np_dtype, d.torch, d.device
-        h = ctypes.c_void_p()
-        rc = _fn("index_create", d.suffix)(d.ctx, d.pa, int(d.a.shape[0]), int(k_hint), d.flags, d.stream, ctypes.byref(h))
-        if rc:
-            _lib.check(rc)
-        self._h = h
+        self._suffix, self._np_dtype, self._torch = d.suffix, d.np_dtype, d.torch
+        self._open("index_create", d, d.pa, int(d.a.shape[0]), int(k_hint))
         self.num_points = int(d.a.shape[0])
 
     def k_nearest_neighbors(self, query_points, k, squared_distances=False, max_points_per_leaf=10):
         """See point_cloud_utils_amd.k_nearest_neighbors; the dataset is the indexed one."""
-        if self._h is None:
-            raise ValueError("the index has been closed")
+        self._check_open()
         k = int(k)
         if k <= 0:
             raise ValueError(f"Invalid value for k ({k}) must be greater than 0.")
-        dq = _dtype_name(query_points)
+        dq = _check_float(query_points, "query_points")
         want = "float32" if self._suffix == "f32" else "float64"
-        if dq not in ("float32", "float64"):
-            raise ValueError(f"Invalid scalar type ({dq}) for argument 'query_points'. Expected one of ['float32', 'float64'].")
         if dq != want:
             raise ValueError(f"Invalid scalar type ({dq}) for argument 'query_points'. Expected it to match the indexed dataset which is of type {want}.")
         sq = _shape2(query_points)
@@ -403,8 +295,8 @@ class DatasetIndex:
         if sq[1] != 3:
             raise ValueError(_KNN_DIM.format(sq[0], sq[1], self.num_points, 3))
         d = _Dev(query_points, query_points)
-        if d.torch and d.device != self._device:
-            raise ValueError("query tensor and index live on different devices")
+        if d.torch:                                  # (a numpy query goes to the default device's context, whatever the index's)
+            self._same_device(d, "query tensor")
         n = int(d.a.shape[0])
         dists = d.empty((n, k), "T")
         corrs = d.empty((n, k), "i64")
@@ -422,24 +314,6 @@ class DatasetIndex:
             if q.flags.f_contiguous and not q.flags.c_contiguous:
                 dists = np.asfortranarray(dists)
         return dists, corrs
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            _lib.lib().pcu_hip_index_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 from ._normals import estimate_point_cloud_normals_knn, estimate_point_cloud_normals_ball  # noqa: E402,F401

@@ -1,0 +1,224 @@
+"""The argument checks that more than one feature module uses, one copy each: scalar types, the reference's shape checks with its texts
+(src/common/common.h), this package's row limit, what the library checks on the device found on the host for host arrays, and the placing of
+further arrays beside the resolved ones of a call. Order, texts and exception types are part of the contract (tests/test_check_texts.py).
+It imports _call only."""
+import numpy as np
+
+from ._call import _FACE_KINDS, _Dev, _dtype_name, _is_torch, _shape2
+
+_MAX_ROWS = 2 ** 27 - 16
+_ROW_LIMIT = "meshes and point clouds with more than 2^27-16 rows are not supported"
+_SAME_DEVICE = "torch inputs must all be CUDA/HIP tensors on the same device"
+_RAY_ROWS = ("ray_o and ray_d must have the same number of rows (one ray origin per ray direction). "
+             "(Note: ray_o can have one row to use the same origin for all directions)")
+_ZERO_POINTS = "Invalid input point cloud with zero points: points must have shape (n, 3) (n > 0). Got points.shape =({}, {})."
+_NOT_3D = "Only 3D inputs are supported: v must have shape (n, 3) (n > 0). Got points.shape =({}, {})."
+
+
+# ------------------------------------------------------------------------------------------------ scalar types and counts
+def _check_float(x, name):
+    dx = _dtype_name(x)
+    if dx not in ("float32", "float64"):
+        raise ValueError(f"Invalid scalar type ({dx}) for argument '{name}'. Expected one of ['float32', 'float64'].")
+    return dx
+
+
+def _match(x, name, want, what):
+    dx = _dtype_name(x)
+    if dx != want:
+        raise ValueError(f"Invalid scalar type ({dx}) for argument '{name}'. Expected it to match {what} which is of type {want}.")
+
+
+def _check_rows(*counts):
+    if max(counts) > _MAX_ROWS:
+        raise ValueError(_ROW_LIMIT)
+
+
+def _size(a):
+    n = 1
+    for x in a.shape:
+        n *= int(x)
+    return n
+
+
+# ------------------------------------------------------------------------------------------------ points, normals, parameters
+def _check_points_dtype(p, want=None):
+    dp = _check_float(p, "p")
+    if want is not None and dp != want:
+        raise ValueError(f"Invalid scalar type ({dp}) for argument 'p'. Expected it to match the indexed mesh which is of type {want}.")
+    return dp, _shape2(p)
+
+
+def _check_points(p, want=None):
+    """Scalar type, then validate_point_cloud (src/common/common.h:58-74; zero rows are allowed), then the row limit. Returns (dtype name, #p)."""
+    dp, sp = _check_points_dtype(p, want)
+    if sp[1] != 3:
+        raise ValueError(_NOT_3D.format(*sp))
+    _check_rows(sp[0])
+    return dp, sp[0]
+
+
+def _check_points_nonzero(p):
+    """validate_point_cloud(p, allow_0=false) (src/common/common.h:58-74), then the row limit. Returns #p."""
+    sp = _shape2(p)
+    if sp[0] == 0:
+        raise ValueError(_ZERO_POINTS.format(*sp))
+    if sp[1] != 3:
+        raise ValueError(_NOT_3D.format(*sp))
+    _check_rows(sp[0])
+    return sp[0]
+
+
+def _check_normals(p, n, allow_zero, **more):
+    """Scalar types (p's; n and the arrays of `more`, by argument name, must match it), then validate_point_cloud_normals(p, n, allow_0)
+    (src/common/common.h:78-110). Returns (dtype name, #p); the row limit is the caller's."""
+    dp = _check_float(p, "p")
+    for name, x in (("n", n),) + tuple(more.items()):
+        _match(x, name, dp, "argument 'p'")
+    sp, sn = _shape2(p), _shape2(n)
+    if sp[0] == 0 and not allow_zero:
+        raise ValueError(_ZERO_POINTS.format(*sp))
+    if sp[1] != 3:
+        raise ValueError(_NOT_3D.format(*sp))
+    if sn[1] != 3:
+        raise ValueError(f"Invalid shape for normals: must have shape (n, 3) (n > 0). Got normals.shape =({sn[0]}, {sn[1]}).")
+    if sn[0] != sp[0]:
+        raise ValueError("Invalid input point cloud. Number of normals must match number of points. "
+                         f"Got points.shape =({sp[0]}, {sp[1]}) and normals.shape = {sn[0]}, {sn[1]}")
+    return dp, sp[0]
+
+
+def _check_beta(beta, noun):
+    beta = float(beta)
+    if not beta > 0.0:
+        raise ValueError(f"beta must be greater than 0 (finite, or +inf for the plain sum over all {noun})")
+    return beta
+
+
+def _check_bounds(lower_bound, upper_bound):
+    lower_bound, upper_bound = float(lower_bound), float(upper_bound)
+    if lower_bound != lower_bound or upper_bound != upper_bound:
+        raise ValueError("lower_bound and upper_bound must not be NaN")
+    if lower_bound > upper_bound:
+        raise ValueError("lower_bound must not be greater than upper_bound")
+    return lower_bound, upper_bound
+
+
+# ------------------------------------------------------------------------------------------------ rays
+def _check_rays(ray_o, ray_d, want, match):
+    """Scalar types (both must be `want`; `match` names what that is), then the reference's shape checks in its order
+    (src/ray_mesh_intersection.cpp:117-134). Returns (#rays, single origin?)."""
+    _match(ray_o, "ray_o", want, match)
+    _match(ray_d, "ray_d", want, match)
+    so, sd = _shape2(ray_o), _shape2(ray_d)
+    single = _size(ray_o) == 3
+    if not single and so[0] != sd[0]:
+        raise ValueError(_RAY_ROWS)
+    if so[1] != 3 and not single:
+        raise ValueError(f"Invalid shape for ray_o must have shape (N, 3) but got ({so[0]}, {so[1]}).")
+    if sd[1] != 3:
+        raise ValueError(f"Invalid shape for ray_d must have shape (N, 3) but got ({sd[0]}, {sd[1]}).")
+    return sd[0], single
+
+
+def _check_ray_limits(n, ray_near, ray_far):
+    _check_rows(n)
+    ray_near, ray_far = float(ray_near), float(ray_far)
+    if ray_near != ray_near or ray_far != ray_far:
+        raise ValueError("ray_near and ray_far must not be NaN")
+    return ray_near, ray_far
+
+
+def _origins_for(d, ray_o, single):
+    """ray_o next to the resolved arrays of a call (_beside), as (1, 3) or (n, 3). Returns (array, rows)."""
+    oo = _beside(d, ray_o)
+    if single:
+        oo = oo.reshape(1, 3)
+    return oo, int(oo.shape[0])
+
+
+# ------------------------------------------------------------------------------------------------ host arrays: what the device would find
+def _host_finite(**arrays):
+    """What the library checks on the device for device-resident input, found on the host for host arrays (before any device work)."""
+    for name, x in arrays.items():
+        if not bool(np.isfinite(x).all()):
+            raise ValueError(f"{name} must not contain NaN or infinite " + ("values" if name == "a" else "coordinates"))
+
+
+def _host_ray_checks(ray_o, ray_d):
+    _host_finite(ray_o=ray_o, ray_d=ray_d)
+
+
+def _host_mesh_checks(v, f):
+    _host_finite(v=v)
+    nv = int(v.shape[0])
+    if (f.dtype.kind == "i" and int(f.min()) < 0) or int(f.max()) >= nv:
+        raise ValueError(f"f must hold row indices of v: found a face index outside [0, {nv})")
+
+
+# ------------------------------------------------------------------------------------------------ meshes
+def _beside(d, x):
+    """`x` next to the resolved arrays of a call: same kind (torch on that device / numpy), contiguous."""
+    if d.torch:
+        if not _is_torch(x) or not x.is_cuda or x.device != d.tdev:
+            raise ValueError(_SAME_DEVICE)
+        return x.contiguous()
+    if _is_torch(x):
+        raise ValueError(_SAME_DEVICE)
+    return np.ascontiguousarray(x)
+
+
+def _face_dtype_name(f):
+    if _is_torch(f):
+        return str(f.dtype).replace("torch.", "")
+    return np.asarray(f).dtype.name
+
+
+def _check_face_dtype(f):
+    df = _face_dtype_name(f)
+    kinds = ["int32", "int64"] if _is_torch(f) else list(_FACE_KINDS)
+    if df not in kinds:
+        raise ValueError(f"Invalid scalar type ({df}) for argument 'f'. Expected one of {kinds}.")
+
+
+def _check_mesh(v, f, want=None):
+    """Scalar types, then validate_mesh (src/common/common.h:133-147), then this package's row limit. Returns (dtype name, #v, #f)."""
+    dv = _check_float(v, "v") if want is None else _dtype_name(v)
+    if want is not None and dv != want:
+        raise ValueError(f"Invalid scalar type ({dv}) for argument 'v'. Expected it to match argument 'p' which is of type {want}.")
+    _check_face_dtype(f)
+    sv, sf = _shape2(v), _shape2(f)
+    got = f"Got v.shape =({sv[0]}, {sv[1]}), f.shape = ({sf[0]}, {sf[1]})."
+    if sv[0] == 0 or sf[0] == 0:
+        raise ValueError("Invalid input mesh with zero elements: v and f must have shape (n, 3) and (m, 3) (n, m > 0). " + got)
+    if sv[1] != 3 or sf[1] != 3:
+        raise ValueError("Only 3D inputs are supported: v and f must have shape (n, 3) and (m, 3) (n, m > 0). " + got)
+    _check_rows(sv[0], sf[0])
+    return dv, sv[0], sf[0]
+
+
+def _resolve(v, f):
+    """The arrays of a call whose mesh passed _check_mesh: host checks for host arrays, then (_Dev, faces, #v, #f)."""
+    if not (_is_torch(v) or _is_torch(f)):
+        _host_mesh_checks(np.asarray(v), np.asarray(f))
+    d = _Dev(v, v)
+    ff = _beside(d, f)
+    return d, ff, _shape2(v)[0], _shape2(f)[0]
+
+
+def _mesh_args(d, ff, nv, nf):
+    return d.pa, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)]
+
+
+# ------------------------------------------------------------------------------------------------ results
+def _scalar_rows(w, n):
+    return w.reshape(()) if n == 1 else w
+
+
+def _face_rows(fi, bc, like, n):
+    """(f_idx, bc) as returned: the face in the dtype of `like`, f's (-1 wraps for an unsigned one, as the reference's assignment does);
+    singleton dimensions squeezed as the package's other calls do (numpyeigen's squeeze)."""
+    fi = fi.to(like.dtype) if _is_torch(fi) else fi.astype(like.dtype, copy=False)
+    if n == 1:
+        fi, bc = fi.reshape(()), bc.reshape(3)
+    return fi, bc

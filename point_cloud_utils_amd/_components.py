@@ -6,8 +6,8 @@ import operator
 
 import numpy as np
 
-from ._call import _FACE_KINDS, _call, _int_out
-from ._mesh import _check_mesh, _face_dtype_name, _faces_for
+from ._call import _Dev, _FACE_KINDS, _call, _int_out, _is_torch, _shape2
+from ._checks import _beside, _check_mesh, _face_dtype_name
 
 _MAX_CELLS = 2 ** 31 - 16
 _GRID_KINDS = {"int32": 0, "int64": 1, "float32": 2, "float64": 3}
@@ -39,7 +39,6 @@ def connected_components(v, f):
         ValueError: the dtype, shape and row-limit checks of the other mesh operators (more than 2**27 - 16 rows), a face index outside
         [0, #v). v's coordinates are never read: non-finite ones are not an error here.
     """
-    from . import _Dev, _is_torch, _shape2
     _check_mesh(v, f)
     nv, nf = _shape2(v)[0], _shape2(f)[0]
     if not (_is_torch(v) or _is_torch(f)):
@@ -47,7 +46,7 @@ def connected_components(v, f):
         if (fa.dtype.kind == "i" and int(fa.min()) < 0) or int(fa.max()) >= nv:
             raise ValueError(f"f must hold row indices of v: found a face index outside [0, {nv})")
     d = _Dev(v, v)
-    ff = _faces_for(d, f)
+    ff = _beside(d, f)
     name = _face_dtype_name(ff)
     cv, cf, cnv, cnf = (_int_out(d, (n,), np.dtype(name)) for n in (nv, nf, nv, nv))
     count = ctypes.c_int64(0)
@@ -107,7 +106,6 @@ def flood_fill_3d(grid, start_coord, fill_value):
         shape"), grid.ndim != 3 ("grid must have shape [w, h, d]"), an unsupported dtype, a seed outside the grid or a zero-sized axis
         ("seed point must be inside grid"), more than 2**31 - 16 cells.
     """
-    from . import _Dev, _is_torch
     seed = _coord3i(start_coord)
     if not _is_torch(grid):
         grid = np.asarray(grid)

@@ -6,8 +6,8 @@ import ctypes
 
 import numpy as np
 
-from ._call import _FACE_KINDS, _call, _int_out
-from ._mesh import _MAX_ROWS, _check_face_dtype, _check_mesh, _face_dtype_name, _faces_for
+from ._call import _Dev, _FACE_KINDS, _call, _int_out, _is_torch, _shape2
+from ._checks import _beside, _check_face_dtype, _check_mesh, _check_rows, _face_dtype_name
 
 _MAX_INDEX = 2 ** 31 - 16
 
@@ -20,7 +20,6 @@ def _check_signed_faces(f):
 
 def _host_face_range(v, f, nv):
     """For host arrays, what the library checks on the device: before any device work."""
-    from . import _is_torch
     if not (_is_torch(v) or _is_torch(f)):
         fa = np.asarray(f)
         if (fa.dtype.kind == "i" and int(fa.min()) < 0) or int(fa.max()) >= nv:
@@ -55,7 +54,6 @@ def remove_mesh_vertices(v, f, mask):
         ValueError: the dtype, shape and row-limit checks of the other mesh operators (f: int32 / int64), a mask that is not bool, "mask
         should have the same number of rows as v", "mask should have only one column", a face index outside [0, #v).
     """
-    from . import _Dev, _is_torch, _shape2
     _, nv, nf = _check_mesh(v, f)
     _check_signed_faces(f)
     dm = str(mask.dtype).replace("torch.", "") if _is_torch(mask) else np.asarray(mask).dtype.name
@@ -68,7 +66,7 @@ def remove_mesh_vertices(v, f, mask):
         raise ValueError("mask should have only one column")
     _host_face_range(v, f, nv)
     d = _Dev(v, v)
-    ff, mm = _faces_for(d, f), _faces_for(d, mask)
+    ff, mm = _beside(d, f), _beside(d, mask)
     name = _face_dtype_name(ff)
     v_out, f_out = d.empty((nv, 3), "T"), _int_out(d, (nf, 3), np.dtype(name))
     kept_v, kept_f = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -99,11 +97,10 @@ def remove_unreferenced_mesh_vertices(v, f):
         Rows of v are copied, never computed with: v_new[f_new] equals v[f] bit for bit. last_stats()["n_escalated"] is 0: no face is dropped.
         ValueError: the dtype, shape and row-limit checks of the other mesh operators, a face index outside [0, #v).
     """
-    from . import _Dev
     _, nv, nf = _check_mesh(v, f)
     _host_face_range(v, f, nv)
     d = _Dev(v, v)
-    ff = _faces_for(d, f)
+    ff = _beside(d, f)
     name = _face_dtype_name(ff)
     dt = np.dtype(name)
     v_new, f_new, corr_v, corr_f = d.empty((nv, 3), "T"), _int_out(d, (nf, 3), dt), _int_out(d, (nv,), dt), _int_out(d, (nv,), dt)
@@ -138,13 +135,12 @@ def deduplicate_mesh_vertices(v, f, epsilon, return_index=True):
         last_stats()["n_escalated"] is the number of faces dropped. Equal arguments give equal bytes.
         ValueError: the dtype, shape and row-limit checks of the other mesh operators (f: int32 / int64), a face index outside [0, #v).
     """
-    from . import _Dev
     _, nv, nf = _check_mesh(v, f)
     _check_signed_faces(f)
     eps = float(epsilon)
     _host_face_range(v, f, nv)
     d = _Dev(v, v)
-    ff = _faces_for(d, f)
+    ff = _beside(d, f)
     name = _face_dtype_name(ff)
     v_out, f_out = d.empty((nv, 3), "T"), _int_out(d, (nf, 3), np.dtype(name))
     svi, svj = _int_out(d, (nv,), np.int32), _int_out(d, (nv,), np.int32)
@@ -185,15 +181,13 @@ def orient_mesh_faces(f, weighting_type="uniform"):
         ValueError: a dtype other than the four integer types, zero rows or a second dimension other than 3 (the reference's texts), more
         than 2**27 - 16 rows, a negative index, an index above 2**31 - 17.
     """
-    from . import _Dev, _is_torch, _shape2
     _check_face_dtype(f)
     sf = _shape2(f if _is_torch(f) else np.asarray(f))
     if sf[0] == 0:
         raise ValueError(f"Invalid input faces with zero elements: f must have shape (n, 3) where n > 0. Got f.shape =({sf[0]}, {sf[1]}).")
     if sf[1] != 3:
         raise ValueError(f"Only triangle inputs are supported: f must have shape (n, 3) where n > 0. Got f.shape =({sf[0]}, {sf[1]}).")
-    if sf[0] > _MAX_ROWS:
-        raise ValueError("meshes and point clouds with more than 2^27-16 rows are not supported")
+    _check_rows(sf[0])
     nf = sf[0]
     if not _is_torch(f):
         fa = np.asarray(f)
@@ -205,7 +199,7 @@ def orient_mesh_faces(f, weighting_type="uniform"):
     if top >= _MAX_INDEX:
         raise ValueError("face indices above 2^31-17 are not supported")
     d = _Dev(f, f)
-    ff = _faces_for(d, f)
+    ff = _beside(d, f)
     name = _face_dtype_name(ff)
     dt = np.dtype(name)
     oriented, comps = _int_out(d, (nf, 3), dt), _int_out(d, (nf,), dt)

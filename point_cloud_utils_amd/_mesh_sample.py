@@ -8,10 +8,9 @@ import time
 
 import numpy as np
 
-from ._call import _FACE_KINDS, _call
-from ._mesh import (_MAX_ROWS, _check_mesh, _face_dtype_name, _faces_for, _host_mesh_checks)
-
-_ROW_LIMIT = "meshes and point clouds with more than 2^27-16 rows are not supported"
+from . import _lib
+from ._call import Stats, _Dev, _call, _fn, _record
+from ._checks import _MAX_ROWS, _check_mesh, _check_rows, _face_rows, _mesh_args, _resolve
 
 
 def _seed(random_seed):
@@ -21,30 +20,6 @@ def _seed(random_seed):
     if seed == 0:                                          # the reference's documented behaviour: a seed from the clock
         seed = (time.time_ns() & 0xFFFFFFFF) or 1
     return seed
-
-
-def _resolve(v, f):
-    """The arrays of a call whose mesh passed _check_mesh: host checks for host arrays, then (_Dev, faces, #v, #f)."""
-    from . import _Dev, _is_torch, _shape2
-    if not (_is_torch(v) or _is_torch(f)):
-        _host_mesh_checks(np.asarray(v), np.asarray(f))
-    d = _Dev(v, v)
-    ff = _faces_for(d, f)
-    return d, ff, _shape2(v)[0], _shape2(f)[0]
-
-
-def _mesh_args(d, ff, nv, nf):
-    from . import _Dev
-    return d.pa, nv, _Dev.ptr(ff), nf, _FACE_KINDS[_face_dtype_name(ff)]
-
-
-def _rows(fi, bc, like, n):
-    """(f_idx, bc) as returned: the face in f's dtype, singleton dimensions squeezed as _mesh._finish does."""
-    from . import _is_torch
-    fi = fi.to(like.dtype) if _is_torch(fi) else fi.astype(like.dtype, copy=False)
-    if n == 1:
-        fi, bc = fi.reshape(()), bc.reshape(3)
-    return fi, bc
 
 
 def mesh_face_areas(v, f, num_threads=-1):
@@ -65,7 +40,6 @@ def mesh_face_areas(v, f, num_threads=-1):
         0; where a square overflows the result is what IEEE arithmetic gives (inf, or NaN). Non-finite coordinates, face indices outside
         [0, #v) and arrays of more than 2**27 - 16 rows raise ValueError.
     """
-    from . import _Dev
     _check_mesh(v, f)
     d, ff, nv, nf = _resolve(v, f)
     areas = d.empty((nf,), "T")
@@ -95,18 +69,16 @@ def sample_mesh_random(v, f, num_samples, random_seed=0):
         A mesh without area raises ValueError("Mesh has zero area"), one whose areas overflow v's dtype ValueError as well; so do
         non-finite coordinates, face indices outside [0, #v) and more than 2**27 - 16 rows or samples.
     """
-    from . import _Dev
     _check_mesh(v, f)
     num_samples = int(num_samples)
     if num_samples <= 0:
         raise ValueError("num_samples must be positive")
-    if num_samples > _MAX_ROWS:
-        raise ValueError(_ROW_LIMIT)
+    _check_rows(num_samples)
     seed = _seed(random_seed)
     d, ff, nv, nf = _resolve(v, f)
     fi, bc = d.empty((num_samples,), "i64"), d.empty((num_samples, 3), "T")
     _call("sample_mesh_random", d, *_mesh_args(d, ff, nv, nf), num_samples, seed, _Dev.ptr(fi), _Dev.ptr(bc))
-    return _rows(fi, bc, ff, num_samples)
+    return _face_rows(fi, bc, ff, num_samples)
 
 
 def sample_mesh_poisson_disk(v, f, num_samples, radius=0.0, use_geodesic_distance=True, best_choice_sampling=True, random_seed=0,
@@ -140,7 +112,6 @@ def sample_mesh_poisson_disk(v, f, num_samples, radius=0.0, use_geodesic_distanc
         runs once at the radius sqrt(area / (0.7 pi num_samples)) and never looks at sample_num_tolerance (about 1333 samples for a request
         of 1000); here the documented count is kept. Errors as for sample_mesh_random, and for more than 2**27 - 16 candidates.
     """
-    from . import _Dev, _lib, _fn, _record, Stats
     _check_mesh(v, f)
     num_samples, radius = int(num_samples), float(radius)
     if num_samples <= 0 and radius <= 0.0:
@@ -153,8 +124,7 @@ def sample_mesh_poisson_disk(v, f, num_samples, radius=0.0, use_geodesic_distanc
         raise ValueError("oversampling_factor must be >= 1.0")
     if num_samples <= 0 and radius != radius:
         raise ValueError("radius must not be NaN")
-    if num_samples > _MAX_ROWS:
-        raise ValueError(_ROW_LIMIT)
+    _check_rows(num_samples)
     n_c = None
     if not radius > 0.0:                                   # (with a radius the candidate count depends on the mesh's area: the library is asked)
         n_c = math.ceil(of * max(num_samples, 1))
@@ -182,4 +152,4 @@ def sample_mesh_poisson_disk(v, f, num_samples, radius=0.0, use_geodesic_distanc
     fi, bc = fi[:m], bc[:m]
     if n_c > 2 * m:                                        # (do not keep the candidates' room alive behind a small result)
         fi, bc = (fi.clone(), bc.clone()) if d.torch else (fi.copy(), bc.copy())
-    return _rows(fi, bc, ff, m)
+    return _face_rows(fi, bc, ff, m)

@@ -7,16 +7,14 @@ import math
 
 import numpy as np
 
-from ._call import _FACE_KINDS, _call, _take
-from ._mesh import _MAX_ROWS, _check_mesh, _face_dtype_name, _faces_for
-from ._mesh_sample import _mesh_args, _resolve
+from ._call import _Dev, _FACE_KINDS, _call, _is_torch, _shape2, _take
+from ._checks import _beside, _check_mesh, _check_rows, _face_dtype_name, _mesh_args, _resolve
 
 _WEIGHTINGS = {"uniform": 0, "area": 1, "angle": 2}
 
 
 def _check_faces(f):
     """Scalar type (int32 / int64: the reference's), then validate_mesh_faces (src/common/common.h:113-127) and the row limit. Returns #f."""
-    from . import _shape2
     df = _face_dtype_name(f)
     if df not in ("int32", "int64"):
         raise ValueError(f"Invalid scalar type ({df}) for argument 'f'. Expected one of ['int32', 'int64'].")
@@ -25,8 +23,7 @@ def _check_faces(f):
         raise ValueError(f"Invalid input faces with zero elements: f must have shape (n, 3) where n > 0. Got f.shape =({sf[0]}, {sf[1]}).")
     if sf[1] != 3:
         raise ValueError(f"Only triangle inputs are supported: f must have shape (n, 3) where n > 0. Got f.shape =({sf[0]}, {sf[1]}).")
-    if sf[0] > _MAX_ROWS:
-        raise ValueError("meshes and point clouds with more than 2^27-16 rows are not supported")
+    _check_rows(sf[0])
     return sf[0]
 
 
@@ -49,7 +46,6 @@ def mesh_vertex_adjacency(f, num_vertices=None):
         ValueError: a dtype other than int32 / int64, zero rows or a second dimension other than 3 (the reference's texts), a face index
         outside [0, nv), more than 2**27 - 16 rows.
     """
-    from . import _Dev, _is_torch
     nf = _check_faces(f)
     if num_vertices is None:
         top = int(f.max())
@@ -60,14 +56,13 @@ def mesh_vertex_adjacency(f, num_vertices=None):
         nv = int(num_vertices)
         if nv <= 0:
             raise ValueError("num_vertices must be positive")
-    if nv > _MAX_ROWS:
-        raise ValueError("meshes and point clouds with more than 2^27-16 rows are not supported")
+    _check_rows(nv)
     if not _is_torch(f):
         fa = np.asarray(f)
         if int(fa.min()) < 0 or int(fa.max()) >= nv:
             raise ValueError(f"f must hold row indices of v: found a face index outside [0, {nv})")
     d = _Dev(f, f)
-    ff = _faces_for(d, f)
+    ff = _beside(d, f)
     name = _face_dtype_name(ff)
     count = ctypes.c_int64(0)
     _call("mesh_adjacency", d, _Dev.ptr(ff), nf, _FACE_KINDS[name], nv, ctypes.addressof(count), suffix=False)
@@ -90,7 +85,6 @@ def adjacency_list(f):
         The rows of mesh_vertex_adjacency(f) as Python lists: each neighbour once, ascending. This is libigl's sorted, unique
         igl::adjacency_list as far as its source is remembered here; it was not at hand.
     """
-    from . import _is_torch
     offsets, neighbours = mesh_vertex_adjacency(f)
     if _is_torch(offsets):
         offsets, neighbours = offsets.cpu().numpy(), neighbours.cpu().numpy()
@@ -120,7 +114,6 @@ def estimate_mesh_vertex_normals(v, f, weighting_type="uniform"):
         ValueError: the reference's text for another weighting_type; the dtype, shape and row-limit checks of the other mesh operators;
         non-finite coordinates; a face index outside [0, #v); normals whose length overflows v's dtype.
     """
-    from . import _Dev
     _check_mesh(v, f)
     if weighting_type not in _WEIGHTINGS:
         raise ValueError(f"Invalid weighting_type must be one of 'uniform', 'angle', or 'area', but got '{weighting_type}'")
@@ -160,7 +153,6 @@ def laplacian_smooth_mesh(v, f, num_iters, step_size=0.1, use_cotan_weights=Fals
         int64); non-finite coordinates; a face index outside [0, #v). RuntimeError: a solve that has not stopped after 4096 iterations (a
         chosen cap) or that met p.Ap <= 0.
     """
-    from . import _Dev
     _check_mesh(v, f)
     df = _face_dtype_name(f)
     if df not in ("int32", "int64"):

@@ -4,9 +4,11 @@ import ctypes
 
 import numpy as np
 
+from . import _lib
+from ._call import Stats, _Dev, _dtype_name, _is_torch, _record
+
 
 def _run(kind, points, view_directions, drop_angle_threshold, max_points_per_leaf, **kw):
-    from . import _lib, _Dev, _is_torch, _record, Stats
     if view_directions is None:
         view_directions = np.zeros([0, 3], dtype=points.dtype) if not _is_torch(points) else None
     torch_in = _is_torch(points)
@@ -26,7 +28,6 @@ def _run(kind, points, view_directions, drop_angle_threshold, max_points_per_lea
     if has_dirs and (int(view_directions.shape[0]) != n or int(view_directions.shape[1]) != 3):
         raise ValueError("Invalid view directions does not match the number of points. If view directions are passed in, they must have the same shape "
                          f"as points. Got points.shape = ({n}, {points.shape[1]}), and view_dirs.shape = ({view_directions.shape[0]}, {view_directions.shape[1]}).")
-    from . import _dtype_name
     da = _dtype_name(points)
     if da not in ("float32", "float64"):
         raise ValueError(f"Invalid scalar type ({da}) for argument 'points'. Expected one of ['float32', 'float64'].")

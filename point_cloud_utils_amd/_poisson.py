@@ -6,6 +6,9 @@ import time
 
 import numpy as np
 
+from . import _lib
+from ._call import Stats, _Dev, _dtype_name, _is_torch, _record
+
 
 def downsample_point_cloud_poisson_disk(v, radius, target_num_samples=-1, random_seed=0, sample_num_tolerance=0.04):
     """
@@ -27,7 +30,6 @@ def downsample_point_cloud_poisson_disk(v, radius, target_num_samples=-1, random
                 the rows the serial greedy takes when it visits the rows in an order drawn from random_seed; equal arguments give equal
                 results.
     """
-    from . import _lib, _Dev, _dtype_name, _is_torch, _record, Stats
     dn = _dtype_name(v)
     if dn not in ("float32", "float64"):
         raise ValueError(f"Invalid scalar type ({dn}) for argument 'v'. Expected one of ['float32', 'float64'].")

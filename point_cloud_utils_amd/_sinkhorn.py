@@ -5,11 +5,13 @@ import ctypes
 
 import numpy as np
 
+from . import _lib
+from ._call import _dtype_name, _is_torch
+
 
 def _prep(arrs):
     """contiguous buffers, (ctx, flags, stream, torch?, device), dtype suffix"""
     from ._voxel import _ctx_flags
-    from . import _dtype_name
     ctx, flags, stream, t, tdev = _ctx_flags(*arrs)
     dn = _dtype_name(arrs[0])
     if dn not in ("float32", "float64"):
@@ -32,7 +34,6 @@ def _promote_pair(a, b):
     integer array is float64). Two differences: a float16 result is computed and returned in float32 (no half kernels); and integers are
     converted BEFORE the subtraction, so small integer types do not wrap around as numpy's `a - b` does (uint8 3 - 5 is -2 here, 254 there)
     -- the distance of the values, not of their wrapped difference."""
-    from . import _dtype_name, _is_torch
 
     def np_dtype(x):
         try:
@@ -54,7 +55,6 @@ def _promote_pair(a, b):
 
 
 def _expand(x, shape):
-    from . import _is_torch
     if tuple(x.shape) == tuple(shape):
         return x
     return x.expand(*shape) if _is_torch(x) else np.broadcast_to(x, shape)
@@ -72,7 +72,6 @@ def pairwise_distances(a, b, p=None):
     Returns:
       M : A (m, n, n)-shaped array containing the pairwise distance_tensor between each pair of inputs in a batch.
     """
-    from . import _lib, _dtype_name
     from ._voxel import _empty, _ptr
     squeezed = False
     if len(a.shape) == 2 and len(b.shape) == 2:
@@ -120,7 +119,6 @@ def sinkhorn(a, b, M, eps, max_iters=100, stop_thresh=1e-3):
     Returns:
       P : An (m, n, n)-shaped array of correspondences between distributions U and V
     """
-    from . import _lib, _is_torch
     from ._voxel import _empty, _ptr
     sq = (lambda x: x.squeeze()) if _is_torch(M) else np.squeeze
     M = sq(M); a = sq(a); b = sq(b)
@@ -179,7 +177,6 @@ def earth_movers_distance(p, q, p_norm=2, eps=1e-4, max_iters=100, stop_thresh=1
       emd : The earth mover's distance between point clouds p and q
       P : An (n, m)-shaped array of correspondences between point clouds p and q
     """
-    from . import _lib, _is_torch
     from ._voxel import _ptr
     M = pairwise_distances(p, q, p_norm)
     if _is_torch(p):

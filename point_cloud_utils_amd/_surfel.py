@@ -2,13 +2,11 @@
 (point_cloud_utils/_ray_point_cloud_intersector.py, _point_cloud_geometry.py over src/ray_point_cloud_intersection.cpp) over the HIP kernels of
 csrc/surfel.h. Same arguments, defaults, dtypes and result order; the values follow this library's deterministic contract (DESIGN.md, row
 f11): the ray contract of ray_mesh_intersection (f7) applied to a stated fan geometry, bit for bit, instead of Embree's float32."""
-import ctypes
-
 import numpy as np
 
-from ._call import _call
-from ._mesh import _check_ray_limits, _check_rays, _check_rows, _host_ray_checks, _origins_for, _scalar_rows
-from ._pc_winding import _beside, _host_finite, _match
+from ._call import _Dev, _Handle, _call, _int_out, _is_torch
+from ._checks import (_SAME_DEVICE, _beside, _check_normals, _check_ray_limits, _check_rays, _check_rows, _host_finite, _host_ray_checks,
+                      _origins_for, _scalar_rows)
 
 _INT32_MAX = 2 ** 31 - 1
 
@@ -25,32 +23,19 @@ def _check_subdivs(subdivs):
 def _check_surfels(p, n):
     """Scalar types, then validate_point_cloud_normals (src/common/common.h:78-110; zero points are allowed, as in the reference) and the
     row limit. Returns (dtype name, #p)."""
-    from . import _dtype_name, _shape2
-    dp = _dtype_name(p)
-    if dp not in ("float32", "float64"):
-        raise ValueError(f"Invalid scalar type ({dp}) for argument 'p'. Expected one of ['float32', 'float64'].")
-    _match(n, "n", dp, "argument 'p'")
-    sp, sn = _shape2(p), _shape2(n)
-    if sp[1] != 3:
-        raise ValueError(f"Only 3D inputs are supported: v must have shape (n, 3) (n > 0). Got points.shape =({sp[0]}, {sp[1]}).")
-    if sn[1] != 3:
-        raise ValueError(f"Invalid shape for normals: must have shape (n, 3) (n > 0). Got normals.shape =({sn[0]}, {sn[1]}).")
-    if sn[0] != sp[0]:
-        raise ValueError("Invalid input point cloud. Number of normals must match number of points. "
-                         f"Got points.shape =({sp[0]}, {sp[1]}) and normals.shape = {sn[0]}, {sn[1]}")
-    _check_rows(sp[0])
-    return dp, sp[0]
+    dp, np_ = _check_normals(p, n, True)
+    _check_rows(np_)
+    return dp, np_
 
 
 def _radii(p, r, np_):
     """_validate_point_radius_internal (point_cloud_utils/_point_cloud_geometry.py:24-42) for numpy and torch: a scalar, a list or tuple, or
     an array of shape (N,) or (N, 1), in p's dtype and of p's kind (a tensor on p's device for a tensor p)."""
-    from . import _is_torch
     if _is_torch(p):
         import torch
         if not _is_torch(r):
             if isinstance(r, np.ndarray):
-                raise ValueError("torch inputs must all be CUDA/HIP tensors on the same device")
+                raise ValueError(_SAME_DEVICE)
             if np.isscalar(r):
                 r = torch.full((np_,), float(r), dtype=p.dtype, device=p.device)
             elif isinstance(r, (list, tuple)):
@@ -58,7 +43,7 @@ def _radii(p, r, np_):
             else:
                 raise ValueError("Argument r must be a scalar or numpy array with the same number of rows as p")
     elif _is_torch(r):
-        raise ValueError("torch inputs must all be CUDA/HIP tensors on the same device")
+        raise ValueError(_SAME_DEVICE)
     elif not isinstance(r, np.ndarray):
         if np.isscalar(r):
             r = r * np.ones(np_)
@@ -78,7 +63,6 @@ def _radii(p, r, np_):
 def _resolve_surfels(p, n, r, np_, rays=()):
     """The cloud's arrays resolved for a call (_Dev over p and n), and r next to them. What the library checks on the device for
     device-resident input is found on the host for host arrays (before any device work), the call's rays included."""
-    from . import _Dev, _is_torch
     rr = _radii(p, r, np_)
     if not any(_is_torch(x) for x in (p, n) + tuple(rays)):
         _host_finite(p=np.asarray(p), n=np.asarray(n))
@@ -91,7 +75,6 @@ def _resolve_surfels(p, n, r, np_, rays=()):
 
 
 def _pid32(pid):
-    from . import _is_torch
     if _is_torch(pid):
         import torch
         return pid.to(torch.int32)
@@ -123,7 +106,6 @@ def ray_surfel_intersection(p, n, ray_o, ray_d, r=0.1, subdivs=4, ray_near=0.0, 
       pid wins. A point with a zero normal or a zero radius is never hit. Non-finite values, NaN ray_near / ray_far, subdivs < 4 and arrays
       of more than 2**27 - 16 rows raise ValueError; zero points (every ray misses) and zero rays are allowed.
     """
-    from . import _Dev, _is_torch
     dp, np_ = _check_surfels(p, n)
     nr, single = _check_rays(ray_o, ray_d, dp, "argument 'p'")
     subdivs = _check_subdivs(subdivs)
@@ -156,23 +138,18 @@ def pointcloud_surfel_geometry(p, n, r=0.1, subdivs=7):
       traces. A zero normal gives a fan collapsed onto its centre. Non-finite values, subdivs < 4, more than 2**27 - 16 points and more than
       2**31 - 1 vertices raise ValueError.
     """
-    from . import _Dev
     _, np_ = _check_surfels(p, n)
     subdivs = _check_subdivs(subdivs)
     if np_ * (subdivs + 1) > _INT32_MAX:
         raise ValueError("surfel geometry with more than 2^31-1 vertices does not fit the int32 faces")
     d, rr = _resolve_surfels(p, n, r, np_)
     v = d.empty((np_ * (subdivs + 1), 3), "T")
-    if d.torch:
-        import torch
-        f = torch.empty((np_ * subdivs, 3), dtype=torch.int32, device=d.tdev)
-    else:
-        f = np.empty((np_ * subdivs, 3), dtype=np.int32)
+    f = _int_out(d, (np_ * subdivs, 3), np.int32)
     _call("surfel_geometry", d, d.pa, d.pb, _Dev.ptr(rr), np_, subdivs, _Dev.ptr(v), _Dev.ptr(f))
     return v, f
 
 
-class RaySurfelIntersector:
+class RaySurfelIntersector(_Handle):
     """
     Class used to find the intersection between rays and a point cloud converted to surfels (the reference's
     point_cloud_utils.RaySurfelIntersector): the cloud is indexed once and queried many times.
@@ -182,6 +159,8 @@ class RaySurfelIntersector:
 
     The index holds 9 scalars per point (a copy: the caller's arrays can go away) and lives on one GPU; close() (or `with`) frees it.
     """
+    _noun, _destroy = "surfel index", "pcu_hip_surfel_index_destroy"
+
     def __init__(self, p, n, r=0.1, subdivs=7):
         """
         Args:
@@ -190,52 +169,24 @@ class RaySurfelIntersector:
           r : Array or Scalar describing the size of each geometry element
           subdivs : Number of triangles per surfel (at least 4)
         """
-        from . import _lib, _Dev, _fn
-        self._h = None
         dp, np_ = _check_surfels(p, n)
         subdivs = _check_subdivs(subdivs)
         d, rr = _resolve_surfels(p, n, r, np_)
         self.p, self.n, self.r, self.num_subdivs = p, n, rr, subdivs
-        self._dtype_name, self._device = dp, d.device
-        h = ctypes.c_void_p()
-        rc = _fn("surfel_index_create", d.suffix)(d.ctx, d.pa, d.pb, _Dev.ptr(rr), np_, subdivs, d.flags, d.stream, ctypes.byref(h))
-        if rc:
-            _lib.check(rc)
-        self._h = h
+        self._dtype_name = dp
+        self._open("surfel_index_create", d, d.pa, d.pb, _Dev.ptr(rr), np_, subdivs)
         self.num_points = np_
 
     def intersect_rays(self, ray_o, ray_d, ray_near=0.0, ray_far=np.inf):
         """See point_cloud_utils_amd.ray_surfel_intersection; the cloud is the indexed one and the rays must have its dtype."""
-        from . import _Dev, _is_torch
-        if self._h is None:
-            raise ValueError("the surfel index has been closed")
+        self._check_open()
         nr, single = _check_rays(ray_o, ray_d, self._dtype_name, "the indexed point cloud")
         ray_near, ray_far = _check_ray_limits(nr, ray_near, ray_far)
         if not (_is_torch(ray_o) or _is_torch(ray_d)):
             _host_ray_checks(np.asarray(ray_o), np.asarray(ray_d))
         d = _Dev(ray_d, ray_d)
-        if d.device != self._device:
-            raise ValueError("rays and surfel index live on different devices")
+        self._same_device(d, "rays")
         oo, o_rows = _origins_for(d, ray_o, single)
         pid, t = d.empty((nr,), "i64"), d.empty((nr,), "T")
         _call("surfel_index_rays", d, self._h, _Dev.ptr(oo), o_rows, d.pa, nr, ray_near, ray_far, _Dev.ptr(pid), _Dev.ptr(t))
         return _scalar_rows(_pid32(pid), nr), _scalar_rows(t, nr)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            from . import _lib
-            _lib.lib().pcu_hip_surfel_index_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

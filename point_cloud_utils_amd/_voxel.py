@@ -5,10 +5,12 @@ import ctypes
 
 import numpy as np
 
+from . import _lib
+from ._call import _dtype_name, _flags, _is_torch
+
 
 def _ctx_flags(*arrays):
     """(ctx, flags, stream, torch?, device) for numpy (host) or CUDA/HIP torch inputs."""
-    from . import _lib, _is_torch, _flags
     if any(_is_torch(a) for a in arrays if a is not None):
         import torch
         ts = [a for a in arrays if a is not None]
@@ -59,7 +61,6 @@ def morton_encode(pts, num_threads=-1):
     Returns:
         morton_codes : an (n,)-shaped uint64 array of morton encoded points
     """
-    from . import _lib
     _int_kind(pts, ("int32", "int64"), "pts")
     if len(pts.shape) != 2 or int(pts.shape[0]) <= 0:
         raise ValueError("pts must be an array of shape [n, 3] but got an empty array")
@@ -87,7 +88,6 @@ def morton_decode(codes, num_threads=-1):
     Returns:
         points : an (n, 3)-shaped int32 array of 3D points
     """
-    from . import _lib
     c, n, (ctx, flags, stream, t, tdev) = _codes(codes, "codes")
     out = _empty((n, 3), np.int32, t, tdev)
     _lib.check(_lib.lib().pcu_hip_morton_decode(ctx, _ptr(c), n, _ptr(out), flags, stream))
@@ -111,7 +111,6 @@ def _codes(codes, name, others=()):
 
 
 def _addsub(codes_1, codes_2, sub):
-    from . import _lib
     c1, n, _ = _codes(codes_1, "codes_1")
     c2, n2, (ctx, flags, stream, t, tdev) = _codes(codes_2, "codes_2", (c1,))
     if n2 != n:
@@ -146,7 +145,6 @@ def morton_knn(codes, qcodes, k, sort_dist=True):
     Returns:
         nn_idx : an (m, min(k, n))-shaped int64 array of indices into codes
     """
-    from . import _lib
     k = int(k)
     if k <= 0:
         raise ValueError("k must be greater than 0")
@@ -163,7 +161,6 @@ def morton_knn(codes, qcodes, k, sort_dist=True):
 # ------------------------------------------------------------------------------------------------------------ voxel grid
 def _downsample_one(points, attrib, voxel_size, min_bound, max_bound, min_points_per_voxel):
     """downsample_point_cloud_voxel_grid_internal: (ret_v, ret_attrib) for one attribute matrix (or an empty one)."""
-    from . import _lib, _dtype_name
     ctx, flags, stream, t, tdev = _ctx_flags(points, attrib if attrib is not None and attrib.shape[0] else None)
     pn = _dtype_name(points)
     if pn not in ("float32", "float64"):
@@ -212,7 +209,6 @@ def downsample_point_cloud_on_voxel_grid(voxel_size, points, *args, min_bound=No
         just the vertices if no attributes are passed in. Rows are ordered by voxel index (x, then y, then z) -- the reference
         returns them in the iteration order of its hash table; the voxel means themselves are bit-identical.
     """
-    from . import _is_torch
     if np.isscalar(voxel_size):
         voxel_size = np.array([voxel_size] * 3)
     else:
@@ -266,7 +262,6 @@ def deduplicate_point_cloud(points, epsilon, return_index=True):
             svi : #x_new indices (int32) so that x_new = x[svi]  (the lowest row of every group)
             svj : #x indices (int32) so that x ~ x_new[svj]
     """
-    from . import _lib, _dtype_name
     pn = _dtype_name(points)
     if pn not in ("float32", "float64"):
         raise ValueError(f"Invalid scalar type ({pn}) for argument 'points'. Expected one of ['float32', 'float64'].")

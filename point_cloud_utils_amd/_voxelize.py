@@ -6,9 +6,8 @@ import ctypes
 
 import numpy as np
 
-from ._call import _FACE_KINDS, _call, _int_out, _plain, _take
-from ._mesh import _check_mesh
-from ._mesh_sample import _mesh_args, _resolve
+from ._call import _Dev, _FACE_KINDS, _call, _int_out, _is_torch, _plain, _shape2, _take
+from ._checks import _check_mesh, _mesh_args, _resolve
 
 _RANGE = 2 ** 20                       # voxel coordinates live in [-2^20, 2^20): the 21 bits per axis of a 64-bit Morton code
 _INT32_MAX = 2 ** 31 - 1
@@ -48,7 +47,6 @@ def _triple(a):
 
 def _check_ijk(ijk, name, zero_text, shape_text):
     """dtype, rows and columns of an (n, 3) integer array. Returns (kind, n)."""
-    from . import _is_torch, _shape2
     dn = str(ijk.dtype).replace("torch.", "") if _is_torch(ijk) else np.asarray(ijk).dtype.name
     kinds = ["int32", "int64"] if _is_torch(ijk) else list(_FACE_KINDS)
     if dn not in kinds:
@@ -115,7 +113,6 @@ def sparse_voxel_grid_boundary(grid_coordinates):
         beyond that range is absent, a coordinate beyond it raises ValueError (the reference has undefined behaviour there). Zero rows and
         a second dimension other than 3 raise ValueError with the reference's texts.
     """
-    from . import _Dev, _is_torch
     kind, n = _check_ijk(grid_coordinates, "grid_coordinates", "Invalid grid_coordinates has zero rows!",
                          "Invalid shape for grid_coordinates must have shape (N, 3) but got ({}, {})")
     if n > _INT32_MAX - 15:
@@ -158,7 +155,6 @@ def voxel_grid_geometry(ijk, voxel_size=np.array((1., 1., 1.)), voxel_origin=np.
         ValueError: zero rows, a non-positive size ("Voxel size must be positive"), a size or origin that is not a triple ("Invalid shape"),
         more than (2**31 - 1) / 8 voxels.
     """
-    from . import _Dev
     origin = _coord3d(voxel_origin)
     size = _number_or_coord3d(voxel_size)
     kind, n = _check_ijk(ijk, "ijk", "Invalid input point cloud with zero points: points must have shape (n, 3) (n > 0). Got points.shape =({}, {}).",

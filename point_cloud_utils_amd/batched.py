@@ -13,6 +13,9 @@ import ctypes
 
 import numpy as np
 
+from . import _HD_DIM, _HD_ZERO, _KNN_DIM, _KNN_ZERO, _check_pair, _lib
+from ._call import Stats, _Dev, _record
+
 CHUNK = 64          # pairs handed to one library call (bounds how many input clouds are alive at once)
 
 
@@ -52,7 +55,6 @@ def _rank_world(group):
 
 def _run_chunk(kind, pairs, lanes, squared=False, p_norm=2.0, max_points_per_leaf=10):
     """One library call for a list of (x, y) pairs. Returns a list of result rows."""
-    from . import _lib, _check_pair, _Dev, _KNN_ZERO, _KNN_DIM, _HD_ZERO, _HD_DIM, _record, Stats
     devs = []
     for x, y in pairs:
         if kind == "hausdorff":

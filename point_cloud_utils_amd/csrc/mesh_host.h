@@ -1,27 +1,29 @@
 // csrc/mesh_host.h -- host orchestration of closest_points_on_mesh, ray_mesh_intersection (kernels, contracts and index layout: mesh.h),
-// triangle_soup_fast_winding_number and signed_distance_to_mesh (mesh_winding.h). Included by pcu_hip.hip after the operator frame (op_run,
-// stage_any) and voxel_host.h (sort_bytes, the radix sort).
+// triangle_soup_fast_winding_number and signed_distance_to_mesh (mesh_winding.h), and the frames of every index that is an element tree
+// (TreeIndex, tree_index_create, tree_index_check, tree_call), which pc_winding_host.h and surfel_host.h use too. Included by pcu_hip.hip
+// after the operator frame (op_run, stage_any, index_out_begin) and voxel_host.h (sort_bytes, the radix sort).
 #pragma once
 
-// A mesh kept on the GPU as its search index (pcu_hip_mesh_index_*): one block owned by the object, not by a call's arena.
-struct pcu_hip_mesh_index {
+// An element tree kept on the GPU as a search index: one block owned by the object, not by a call's arena. The three handle types of the ABI
+// (the mesh's here, the dipole tree's in pc_winding_host.h, the surfel tree's in surfel_host.h) are this record under their own names.
+struct TreeIndex {
     int elem_size = 0;            // 4: float, 8: double
     int device = 0;
-    int64_t nf = 0;
+    int64_t count = 0;            // faces or points
     void* mem = nullptr;
     MeshIdx<float> m32; MeshIdx<double> m64;
 };
-template <typename T> static MeshIdx<T>& mesh_idx(pcu_hip_mesh_index* p);
-template <> MeshIdx<float>& mesh_idx<float>(pcu_hip_mesh_index* p) { return p->m32; }
-template <> MeshIdx<double>& mesh_idx<double>(pcu_hip_mesh_index* p) { return p->m64; }
-
-static void mesh_index_free(pcu_hip_mesh_index* p) {
+template <typename T> static MeshIdx<T>& tree_idx(TreeIndex* p) { if constexpr (sizeof(T) == 4) return p->m32; else return p->m64; }
+template <typename T> static const MeshIdx<T>& tree_idx(const TreeIndex* p) { if constexpr (sizeof(T) == 4) return p->m32; else return p->m64; }
+template <typename H> static void tree_index_free(H* p) {        // (H: the handle type it was made as)
     if (!p) return;
     if (p->mem) (void)hipFree(p->mem);
     delete p;
 }
-static int mesh_leaves_pow2(int64_t nf) {
-    const int64_t leaves = (nf + kMeshLeaf - 1) / kMeshLeaf;
+struct pcu_hip_mesh_index : TreeIndex {};
+// the leaves of a tree over `count` elements, `leaf` to a leaf, rounded up to a power of two
+static int leaves_pow2(int64_t count, int leaf) {
+    const int64_t leaves = (count + leaf - 1) / leaf;
     int P = 1;
     while (P < leaves) P <<= 1;
     return P;
@@ -29,7 +31,7 @@ static int mesh_leaves_pow2(int64_t nf) {
 // `moments`: with the centres, radii and moments of mesh_winding.h (34 more T per node, about 17 per face)
 template <typename T>
 static size_t mesh_index_bytes(int64_t nf, bool moments) {
-    const size_t N = (size_t)nf, P = (size_t)mesh_leaves_pow2(nf);
+    const size_t N = (size_t)nf, P = (size_t)leaves_pow2(nf, kMeshLeaf);
     size_t b = align_up(sizeof(MeshHead<T>), 256) + align_up(N * 9 * sizeof(T), 256) + align_up(N * 4, 256) + align_up(2 * P * 6 * sizeof(T), 256) + 1024;
     if (moments) b += align_up(2 * P * 4 * sizeof(T), 256) + align_up(2 * P * 30 * sizeof(T), 256);
     return b;
@@ -42,7 +44,7 @@ static int int_kind_check(int kind) {
 template <typename T>
 static size_t mesh_build_bytes(int64_t nv, int64_t nf, int f_kind, bool on_dev, bool moments) {
     size_t b = sort_bytes((size_t)nf) + align_up((size_t)nf * 12, 256) + 4096;
-    if (moments) b += align_up(2 * (size_t)mesh_leaves_pow2(nf) * sizeof(double), 256);      // (the nodes' areas)
+    if (moments) b += align_up(2 * (size_t)leaves_pow2(nf, kMeshLeaf) * sizeof(double), 256);      // (the nodes' areas)
     if (!on_dev) b += align_up((size_t)nv * 3 * sizeof(T), 256) + align_up((size_t)nf * 3 * int_kind_bytes(f_kind), 256);
     return b;
 }
@@ -53,7 +55,6 @@ static size_t mesh_run_bytes(int64_t n, int rows3, bool on_dev) {
     if (!on_dev) b += rows3 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n * sizeof(T), 256) + align_up((size_t)n * 8, 256);
     return b;
 }
-constexpr int64_t kMeshMaxRows = 0x07fffff0ll;
 static int mesh_row_limit() { return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported"); }
 // validate_mesh (src/common/common.h:133-147) and this package's row limit
 static int mesh_validate(int64_t nv, int64_t nf, int64_t np, int f_kind) {
@@ -61,7 +62,7 @@ static int mesh_validate(int64_t nv, int64_t nf, int64_t np, int f_kind) {
         return fail(PCU_HIP_ERR_INVALID, "Invalid input mesh with zero elements: v and f must have shape (n, 3) and (m, 3) (n, m > 0). Got v.shape =(%lld, 3), f.shape = (%lld, 3).",
                     (long long)nv, (long long)nf);
     if (np < 0) return fail(PCU_HIP_ERR_INVALID, "negative number of query points");
-    if (f_kind < 0 || f_kind > 3) return fail(PCU_HIP_ERR_INVALID, "f_kind must be one of PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64");
+    if (int_kind_check(f_kind)) return fail(PCU_HIP_ERR_INVALID, "f_kind must be one of PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64");
     if (nv > kMeshMaxRows || nf > kMeshMaxRows || np > kMeshMaxRows) return mesh_row_limit();
     return 0;
 }
@@ -73,7 +74,7 @@ static int mesh_build(Arena& ari, Arena& ar, hipStream_t s, const T* v, int64_t 
                       MeshIdx<T>& M) {
     const T* dv = nullptr; const char* df = nullptr;
     if (stage_in(ar, v, nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(f), (size_t)nf * 3 * int_kind_bytes(f_kind), on_dev, s, &df)) return -1;
-    M.nf = (int)nf; M.P = mesh_leaves_pow2(nf);
+    M.nf = (int)nf; M.P = leaves_pow2(nf, kMeshLeaf);
     int* fidx = nullptr;
     if (aalloc(ari, &M.head, 1) || aalloc(ari, &M.tri, (size_t)nf * 9) || aalloc(ari, &M.face, (size_t)nf) || aalloc(ari, &M.box, (size_t)M.P * 12) ||
         aalloc(ar, &fidx, (size_t)nf * 3)) return -1;
@@ -230,55 +231,78 @@ static void mesh_stats(pcu_hip_stats* st, Timer& tm, int64_t np, bool built) {
     st->ms_total = built ? tm.span(0, 2) : st->ms_search;
 }
 
-// One call of either operator. Mesh given (`mesh`): index, rows and temporaries in the call's arena; index given (`ix`): rows and temporaries.
+// ---------------------------------------------------------------------------------------------------- the frames of an index
+// The refusals ahead of a call's own: `given`: the structure comes with the call; otherwise the handle `ix` must fit the call and the context.
+template <typename T>
+static int tree_index_check(pcu_hip_ctx* c, const TreeIndex* ix, bool given, const char* noun, pcu_hip_stats* st) {
+    if (!c || !(given || ix)) return given ? fail(PCU_HIP_ERR_INVALID, "null context") : fail(PCU_HIP_ERR_INVALID, "null context / %s", noun);
+    if (st) memset(st, 0, sizeof *st);
+    if (given) return 0;
+    if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the %s was built for the other scalar type", noun);
+    if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the %s lives on another device than the context", noun);
+    return 0;
+}
+// One validated call of an operator. Index given (`ix`): rows and temporaries in the call's arena; otherwise `build(ar, s, on_dev, built, op)`
+// makes the tree there too, out of `given_bytes` more.
+template <typename T, typename Op, typename Build>
+static int tree_call(pcu_hip_ctx* c, unsigned flags, void* stream, pcu_hip_stats* st, const TreeIndex* ix, size_t given_bytes, Build build, Op op, int64_t n,
+                     T* out_val, int64_t* out_fi, T* out_bc) {
+    const size_t bytes = mesh_run_bytes<T>(n, Op::kRows3, flags & PCU_HIP_PTRS_ON_DEVICE) + (ix ? 0 : given_bytes);
+    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;
+        MeshIdx<T> built;
+        if (!ix) { tm.mark(0); if (int rc = build(ar, s, on_dev, built, op)) return rc; }
+        if (int rc = mesh_run<T>(ar, s, ix ? tree_idx<T>(ix) : built, op, n, on_dev, out_val, out_fi, out_bc, tm)) return rc;
+        mesh_stats(st, tm, n, !ix);
+        return 0;
+    });
+}
+// Makes a handle H over its own block of `index_bytes`, after the caller's index_out_begin and validation: `build(ari, ar, s, h)` enqueues
+// into the block (`ari`) with temporaries from the context (`ar`, `build_bytes`). A failure of any kind leaves no handle behind.
+template <typename T, typename H, typename Build>
+static int tree_index_create(pcu_hip_ctx* c, unsigned flags, void* stream, int64_t count, size_t index_bytes, size_t build_bytes, const char* noun, H** out,
+                             Build build) {
+    hipStream_t s = pick_stream(c, flags, stream);
+    H* h = new H();
+    h->elem_size = (int)sizeof(T); h->device = c->device; h->count = count;
+    if (hipMalloc(&h->mem, index_bytes) != hipSuccess) { h->mem = nullptr; tree_index_free(h); return fail(PCU_HIP_ERR_RUNTIME, "out of device memory for the %s", noun); }
+    if (ctx_begin(c, build_bytes)) { tree_index_free(h); return PCU_HIP_ERR_RUNTIME; }
+    ArenaState blk;                                 // a bump allocator over the index's own block
+    blk.base = static_cast<char*>(h->mem); blk.cap = index_bytes;
+    Arena ari{&blk}, ar{c};
+    int rc = build(ari, ar, s, *h);
+    if (!rc) rc = wait_stream(s);                   // (the temporaries go back to the context with this call)
+    rc = attempt_exit(c, index_block_exit(blk, rc, noun));
+    if (rc) { (void)hipStreamSynchronize(s); tree_index_free(h); return rc; }
+    *out = h;
+    return 0;
+}
+
+// One call of a mesh operator, the mesh given (`mesh`) or its index (`ix`).
 template <typename T> struct MeshGiven { const T* v; int64_t nv; const void* f; int64_t nf; int f_kind; };
 template <typename T, typename Op>
 static int mesh_call(pcu_hip_ctx* c, const MeshGiven<T>* mesh, const pcu_hip_mesh_index* ix, Op op, int64_t n, T* out_val, int64_t* out_fi, T* out_bc,
                      unsigned flags, void* stream, pcu_hip_stats* st) {
-    if (mesh ? !c : (!c || !ix)) return fail(PCU_HIP_ERR_INVALID, mesh ? "null context" : "null context / mesh index");
-    if (st) memset(st, 0, sizeof *st);
-    if (!mesh) {
-        if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the mesh index was built for the other scalar type");
-        if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the mesh index lives on another device than the context");
-        if (Op::kMoments && !mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)).mom)
-            return fail(PCU_HIP_ERR_INVALID, "the mesh index was created without PCU_HIP_MESH_MOMENTS");
-    }
+    if (int rc = tree_index_check<T>(c, ix, mesh != nullptr, "mesh index", st)) return rc;
+    if (!mesh && Op::kMoments && !tree_idx<T>(ix).mom) return fail(PCU_HIP_ERR_INVALID, "the mesh index was created without PCU_HIP_MESH_MOMENTS");
     if (int rc = op.validate(n)) return rc;
     if (mesh) { if (int rc = mesh_validate(mesh->nv, mesh->nf, n, mesh->f_kind)) return rc; }
     else if (n < 0 || n > kMeshMaxRows) return mesh_row_limit();
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    size_t bytes = mesh_run_bytes<T>(n, Op::kRows3, on_dev);
-    if (mesh) bytes += mesh_index_bytes<T>(mesh->nf, Op::kMoments) + mesh_build_bytes<T>(mesh->nv, mesh->nf, mesh->f_kind, on_dev, Op::kMoments);
-    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
-        auto& [c, s, on_dev, ar, tm] = fr;
-        MeshIdx<T> built;
-        if (mesh) { tm.mark(0); if (int rc = mesh_build<T>(ar, ar, s, mesh->v, mesh->nv, mesh->f, mesh->nf, mesh->f_kind, on_dev, Op::kMoments, built)) return rc; }
-        if (int rc = mesh_run<T>(ar, s, mesh ? built : mesh_idx<T>(const_cast<pcu_hip_mesh_index*>(ix)), op, n, on_dev, out_val, out_fi, out_bc, tm)) return rc;
-        mesh_stats(st, tm, n, mesh != nullptr);
-        return 0;
-    });
+    const size_t given = mesh ? mesh_index_bytes<T>(mesh->nf, Op::kMoments) + mesh_build_bytes<T>(mesh->nv, mesh->nf, mesh->f_kind, on_dev, Op::kMoments) : 0;
+    return tree_call<T>(c, flags, stream, st, mesh ? nullptr : ix, given, [&](Arena& ar, hipStream_t s, bool on_dev, MeshIdx<T>& built, Op&) {
+        return mesh_build<T>(ar, ar, s, mesh->v, mesh->nv, mesh->f, mesh->nf, mesh->f_kind, on_dev, Op::kMoments, built);
+    }, op, n, out_val, out_fi, out_bc);
 }
 
 template <typename T>
 static int mesh_index_create_impl(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, unsigned flags, void* stream,
                                   pcu_hip_mesh_index** out) {
-    if (!c || !out) return fail(PCU_HIP_ERR_INVALID, "null context / output");
-    *out = nullptr;
+    if (int rc = index_out_begin(c, out)) return rc;
     if (int rc = mesh_validate(nv, nf, 0, f_kind)) return rc;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE, moments = flags & PCU_HIP_MESH_MOMENTS;
-    hipStream_t s = pick_stream(c, flags, stream);
-    pcu_hip_mesh_index* p = new pcu_hip_mesh_index();
-    p->elem_size = (int)sizeof(T); p->device = c->device; p->nf = nf;
-    const size_t bytes = mesh_index_bytes<T>(nf, moments);
-    if (hipMalloc(&p->mem, bytes) != hipSuccess) { p->mem = nullptr; mesh_index_free(p); return fail(PCU_HIP_ERR_RUNTIME, "out of device memory for the mesh index"); }
-    if (ctx_begin(c, mesh_build_bytes<T>(nv, nf, f_kind, on_dev, moments))) { mesh_index_free(p); return PCU_HIP_ERR_RUNTIME; }
-    ArenaState blk;                                 // a bump allocator over the index's own block
-    blk.base = static_cast<char*>(p->mem); blk.cap = bytes;
-    Arena ari{&blk}, ar{c};
-    int rc = mesh_build<T>(ari, ar, s, v, nv, f, nf, f_kind, on_dev, moments, mesh_idx<T>(p));
-    if (!rc) rc = wait_stream(s);                   // (the temporaries go back to the context with this call)
-    rc = attempt_exit(c, index_block_exit(blk, rc, "mesh index"));
-    if (rc) { (void)hipStreamSynchronize(s); mesh_index_free(p); return rc; }
-    *out = p;
-    return 0;
+    return tree_index_create<T>(c, flags, stream, nf, mesh_index_bytes<T>(nf, moments), mesh_build_bytes<T>(nv, nf, f_kind, on_dev, moments), "mesh index", out,
+                                [&](Arena& ari, Arena& ar, hipStream_t s, pcu_hip_mesh_index& h) {
+        return mesh_build<T>(ari, ar, s, v, nv, f, nf, f_kind, on_dev, moments, tree_idx<T>(&h));
+    });
 }

@@ -1,41 +1,22 @@
 // csrc/pc_winding_host.h -- host orchestration of point_cloud_fast_winding_number and estimate_mesh_face_normals (kernels and contract:
-// pc_winding.h). The dipole tree is a MeshIdx whose elements are points: the rows go through mesh_run like the mesh operators'. Included by
-// pcu_hip.hip after mesh_host.h and mesh_sample_host.h.
+// pc_winding.h). The dipole tree is a MeshIdx whose elements are points: its handle, its create and its calls go through the frames of
+// mesh_host.h (TreeIndex, tree_index_create, tree_call), the rows through mesh_run like the mesh operators'. Included by pcu_hip.hip after
+// mesh_host.h and mesh_sample_host.h.
 #pragma once
 
-// An oriented point cloud kept on the GPU as its dipole tree (pcu_hip_pc_winding_index_*): one block owned by the object.
-struct pcu_hip_pc_winding_index {
-    int elem_size = 0;            // 4: float, 8: double
-    int device = 0;
-    int64_t np = 0;
-    void* mem = nullptr;
-    MeshIdx<float> m32; MeshIdx<double> m64;
-};
-template <typename T> static const MeshIdx<T>& pc_idx(const pcu_hip_pc_winding_index* p);
-template <> const MeshIdx<float>& pc_idx<float>(const pcu_hip_pc_winding_index* p) { return p->m32; }
-template <> const MeshIdx<double>& pc_idx<double>(const pcu_hip_pc_winding_index* p) { return p->m64; }
-static void pc_index_free(pcu_hip_pc_winding_index* p) {
-    if (!p) return;
-    if (p->mem) (void)hipFree(p->mem);
-    delete p;
-}
-static int pc_leaves_pow2(int64_t np) {
-    const int64_t leaves = (np + kPcLeaf - 1) / kPcLeaf;
-    int P = 1;
-    while (P < leaves) P <<= 1;
-    return P;
-}
+// An oriented point cloud kept on the GPU as its dipole tree (pcu_hip_pc_winding_index_*): the TreeIndex of mesh_host.h over points.
+struct pcu_hip_pc_winding_index : TreeIndex {};
 // head, 6 T per point, and per node its box, centre and radius, moments (40 T per node: about 10 per point)
 template <typename T>
 static size_t pc_index_bytes(int64_t np) {
-    const size_t N = (size_t)np, P = (size_t)pc_leaves_pow2(np);
+    const size_t N = (size_t)np, P = (size_t)leaves_pow2(np, kPcLeaf);
     return align_up(sizeof(MeshHead<T>), 256) + align_up(N * 6 * sizeof(T), 256) + align_up(2 * P * 6 * sizeof(T), 256) + align_up(2 * P * 4 * sizeof(T), 256) +
            align_up(2 * P * 30 * sizeof(T), 256) + 1024;
 }
 // the sort, the nodes' weights and, for host arrays, p, n and a staged
 template <typename T>
 static size_t pc_build_bytes(int64_t np, bool on_dev) {
-    size_t b = sort_bytes((size_t)np) + align_up(2 * (size_t)pc_leaves_pow2(np) * sizeof(double), 256) + 4096;
+    size_t b = sort_bytes((size_t)np) + align_up(2 * (size_t)leaves_pow2(np, kPcLeaf) * sizeof(double), 256) + 4096;
     if (!on_dev) b += 2 * align_up((size_t)np * 3 * sizeof(T), 256) + align_up((size_t)np * sizeof(T), 256);
     return b;
 }
@@ -52,7 +33,7 @@ template <typename T>
 static int pc_build(Arena& ari, Arena& ar, hipStream_t s, const T* p, const T* n, const T* a, int64_t np, bool on_dev, MeshIdx<T>& M) {
     const T *dp = nullptr, *dn = nullptr, *da = nullptr;
     if (stage_in(ar, p, np, on_dev, s, &dp) || stage_in(ar, n, np, on_dev, s, &dn) || stage_any(ar, a, (size_t)np, on_dev, s, &da)) return -1;
-    M.nf = (int)np; M.P = pc_leaves_pow2(np);
+    M.nf = (int)np; M.P = leaves_pow2(np, kPcLeaf);
     double* weight = nullptr;
     unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
     if (aalloc(ari, &M.head, 1) || aalloc(ari, &M.tri, (size_t)np * 6) || aalloc(ari, &M.box, (size_t)M.P * 12) || aalloc(ari, &M.ctr, (size_t)M.P * 8) ||
@@ -100,54 +81,30 @@ struct PcWindingOp : MeshPointsOp<T> {          // point_cloud_fast_winding_numb
     static int message(int) { return fail(PCU_HIP_ERR_INVALID, "q must not contain NaN or infinite coordinates"); }
 };
 
-// One call. Cloud given (`pc`): tree, rows and temporaries in the call's arena; index given (`ix`): rows and temporaries.
+// One call, the cloud given (`pc`) or its index (`ix`).
 template <typename T> struct PcGiven { const T* p; const T* n; const T* a; int64_t np; };
 template <typename T>
 static int pc_call(pcu_hip_ctx* c, const PcGiven<T>* pc, const pcu_hip_pc_winding_index* ix, const T* q, int64_t nq, double beta, T* out_w, unsigned flags,
                    void* stream, pcu_hip_stats* st) {
-    if (pc ? !c : (!c || !ix)) return fail(PCU_HIP_ERR_INVALID, pc ? "null context" : "null context / point cloud winding index");
-    if (st) memset(st, 0, sizeof *st);
-    if (!pc) {
-        if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the point cloud winding index was built for the other scalar type");
-        if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the point cloud winding index lives on another device than the context");
-    }
+    if (int rc = tree_index_check<T>(c, ix, pc != nullptr, "point cloud winding index", st)) return rc;
     PcWindingOp<T> op{{q}, beta};
     if (pc) { if (int rc = pc_validate_rows(pc->np)) return rc; }
     if (int rc = op.validate(nq)) return rc;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    size_t bytes = mesh_run_bytes<T>(nq, 1, on_dev);
-    if (pc) bytes += pc_index_bytes<T>(pc->np) + pc_build_bytes<T>(pc->np, on_dev);
-    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
-        auto& [c, s, on_dev, ar, tm] = fr;
-        MeshIdx<T> built;
-        if (pc) { tm.mark(0); if (int rc = pc_build<T>(ar, ar, s, pc->p, pc->n, pc->a, pc->np, on_dev, built)) return rc; }
-        if (int rc = mesh_run<T>(ar, s, pc ? built : pc_idx<T>(ix), op, nq, on_dev, out_w, nullptr, nullptr, tm)) return rc;
-        mesh_stats(st, tm, nq, pc != nullptr);
-        return 0;
-    });
+    const size_t given = pc ? pc_index_bytes<T>(pc->np) + pc_build_bytes<T>(pc->np, flags & PCU_HIP_PTRS_ON_DEVICE) : 0;
+    return tree_call<T>(c, flags, stream, st, pc ? nullptr : ix, given, [&](Arena& ar, hipStream_t s, bool on_dev, MeshIdx<T>& built, PcWindingOp<T>&) {
+        return pc_build<T>(ar, ar, s, pc->p, pc->n, pc->a, pc->np, on_dev, built);
+    }, op, nq, out_w, nullptr, nullptr);
 }
 
 template <typename T>
 static int pc_index_create_impl(pcu_hip_ctx* c, const T* p, const T* n, const T* a, int64_t np, unsigned flags, void* stream, pcu_hip_pc_winding_index** out) {
-    if (!c || !out) return fail(PCU_HIP_ERR_INVALID, "null context / output");
-    *out = nullptr;
+    if (int rc = index_out_begin(c, out)) return rc;
     if (int rc = pc_validate_rows(np)) return rc;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    pcu_hip_pc_winding_index* h = new pcu_hip_pc_winding_index();
-    h->elem_size = (int)sizeof(T); h->device = c->device; h->np = np;
-    const size_t bytes = pc_index_bytes<T>(np);
-    if (hipMalloc(&h->mem, bytes) != hipSuccess) { h->mem = nullptr; pc_index_free(h); return fail(PCU_HIP_ERR_RUNTIME, "out of device memory for the point cloud winding index"); }
-    if (ctx_begin(c, pc_build_bytes<T>(np, on_dev))) { pc_index_free(h); return PCU_HIP_ERR_RUNTIME; }
-    ArenaState blk;                                 // a bump allocator over the index's own block
-    blk.base = static_cast<char*>(h->mem); blk.cap = bytes;
-    Arena ari{&blk}, ar{c};
-    int rc = pc_build<T>(ari, ar, s, p, n, a, np, on_dev, const_cast<MeshIdx<T>&>(pc_idx<T>(h)));
-    if (!rc) rc = wait_stream(s);                   // (the temporaries go back to the context with this call)
-    rc = attempt_exit(c, index_block_exit(blk, rc, "point cloud winding index"));
-    if (rc) { (void)hipStreamSynchronize(s); pc_index_free(h); return rc; }
-    *out = h;
-    return 0;
+    return tree_index_create<T>(c, flags, stream, np, pc_index_bytes<T>(np), pc_build_bytes<T>(np, on_dev), "point cloud winding index", out,
+                                [&](Arena& ari, Arena& ar, hipStream_t s, pcu_hip_pc_winding_index& h) {
+        return pc_build<T>(ari, ar, s, p, n, a, np, on_dev, tree_idx<T>(&h));
+    });
 }
 
 // estimate_mesh_face_normals (src/mesh_normals.cpp:65-80)

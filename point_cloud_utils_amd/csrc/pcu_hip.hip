@@ -1349,6 +1349,27 @@ static int stage_in(Arena& ar, const T* p, int64_t n, bool on_dev, hipStream_t s
 static hipStream_t pick_stream(pcu_hip_ctx* c, unsigned flags, void* stream) {
     return (stream || (flags & PCU_HIP_STREAM_GIVEN)) ? (hipStream_t)stream : c->own_stream;
 }
+constexpr int64_t kMeshMaxRows = 0x07fffff0ll;      // rows of a mesh, a cloud or a batch of queries: 2^27 - 16
+// The head and the two feet of the entry points that own an index object (the dataset's grid here, the element trees of mesh_host.h).
+template <typename H>
+static int index_out_begin(pcu_hip_ctx* c, H** out) {
+    if (!c || !out) return fail(PCU_HIP_ERR_INVALID, "null context / output");
+    *out = nullptr;
+    return 0;
+}
+// A create that a late request turned into PCU_HIP_ERR_CANCELLED (abi_rc) gives its index back: the caller sees an error and would drop the handle.
+template <typename H, typename Free>
+static int index_create_foot(pcu_hip_ctx* c, int rc, H** out, Free free_fn) {
+    if (rc && out && *out) { DeviceGuard g(c->device); (void)hipDeviceSynchronize(); free_fn(*out); *out = nullptr; }
+    return rc;
+}
+template <typename H, typename Free>
+static void index_destroy(H* ix, Free free_fn) {
+    if (!ix) return;
+    DeviceGuard dg(ix->device);
+    (void)hipDeviceSynchronize();
+    free_fn(ix);
+}
 template <typename U>
 static int stage_any(Arena& ar, const U* p, size_t count, bool on_dev, hipStream_t s, const U** out) {
     if (on_dev) { *out = p; return 0; }
@@ -2380,13 +2401,12 @@ static void index_free(pcu_hip_index* p) {
 }
 template <typename T>
 static int index_create_impl(pcu_hip_ctx* c, const T* dataset, int64_t nr, int k_hint, unsigned flags, void* stream, pcu_hip_index** out) {
-    if (!c || !out) return fail(PCU_HIP_ERR_INVALID, "null context / output");
-    *out = nullptr;
+    if (int rc = index_out_begin(c, out)) return rc;
     if (nr <= 0) return fail(PCU_HIP_ERR_INVALID, "Invalid input set with zero elements: dataset_points must have shape (m, 3). Got dataset_points.shape = (%lld, 3).", (long long)nr);
-    if (nr > 0x07fffff0ll) return fail(PCU_HIP_ERR_INVALID, "point clouds with more than 2^27-16 rows are not supported");
+    if (nr > kMeshMaxRows) return fail(PCU_HIP_ERR_INVALID, "point clouds with more than 2^27-16 rows are not supported");
     if (k_hint <= 0) k_hint = 1;
     if (k_hint > kMaxK) k_hint = kMaxK;
-    hipStream_t s = (stream || (flags & PCU_HIP_STREAM_GIVEN)) ? (hipStream_t)stream : c->own_stream;
+    hipStream_t s = pick_stream(c, flags, stream);
     pcu_hip_index* p = new pcu_hip_index();
     p->elem_size = (int)sizeof(T); p->device = c->device; p->n = nr;
     p->occ = c->occupancy > 0 ? c->occupancy : default_occupancy(k_hint);
@@ -2634,11 +2654,11 @@ int pcu_hip_debug_kd_tree_f64(pcu_hip_ctx* c, const double* pts, int64_t n, int 
 
 int pcu_hip_index_create_f32(pcu_hip_ctx* c, const float* r, int64_t nr, int k_hint, unsigned flags, void* stream, pcu_hip_index** out) {
     CallGuard dg(c);
-    return abi_rc(index_create_impl<float>(c, r, nr, k_hint, flags, stream, out));
+    return index_create_foot(c, abi_rc(index_create_impl<float>(c, r, nr, k_hint, flags, stream, out)), out, index_free);
 }
 int pcu_hip_index_create_f64(pcu_hip_ctx* c, const double* r, int64_t nr, int k_hint, unsigned flags, void* stream, pcu_hip_index** out) {
     CallGuard dg(c);
-    return abi_rc(index_create_impl<double>(c, r, nr, k_hint, flags, stream, out));
+    return index_create_foot(c, abi_rc(index_create_impl<double>(c, r, nr, k_hint, flags, stream, out)), out, index_free);
 }
 int pcu_hip_index_knn_f32(pcu_hip_ctx* c, const pcu_hip_index* ix, const float* q, int64_t nq, int k, int max_leaf, float* od, int64_t* oi,
                           unsigned flags, void* stream, pcu_hip_stats* st) {
@@ -2653,15 +2673,9 @@ int pcu_hip_index_knn_f64(pcu_hip_ctx* c, const pcu_hip_index* ix, const double*
     return abi_rc(knn_impl<double>(c, q, nq, nullptr, ix->n, k, max_leaf, od, oi, flags, stream, st, ix));
 }
 int64_t pcu_hip_index_size(const pcu_hip_index* ix) { return ix ? ix->n : 0; }
-void pcu_hip_index_destroy(pcu_hip_index* ix) {
-    if (!ix) return;
-    DeviceGuard dg(ix->device);
-    (void)hipDeviceSynchronize();
-    index_free(ix);
-}
+void pcu_hip_index_destroy(pcu_hip_index* ix) { index_destroy(ix, index_free); }
 
-// closest_points_on_mesh (mesh.h, mesh_host.h). A create that a late request turns into PCU_HIP_ERR_CANCELLED gives its index back: the caller sees an
-// error and would drop the handle.
+// closest_points_on_mesh (mesh.h, mesh_host.h)
 #define PCU_MESH(SUF, T)                                                                                                                              \
 int pcu_hip_closest_points_on_mesh_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const T* p, int64_t np,      \
                                          T* out_d, int64_t* out_fi, T* out_bc, unsigned flags, void* stream, pcu_hip_stats* st) {                   \
@@ -2670,9 +2684,8 @@ int pcu_hip_closest_points_on_mesh_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv,
 int pcu_hip_mesh_index_create_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, unsigned flags, void* stream,    \
                                     pcu_hip_mesh_index** out) {                                                                                      \
     CallGuard dg(c);                                                                                                                                 \
-    const int rc = abi_rc(mesh_index_create_impl<T>(c, v, nv, f, nf, f_kind, flags, stream, out));                                                   \
-    if (rc && out && *out) { DeviceGuard g(c->device); (void)hipDeviceSynchronize(); mesh_index_free(*out); *out = nullptr; }                        \
-    return rc; }                                                                                                                                     \
+    return index_create_foot(c, abi_rc(mesh_index_create_impl<T>(c, v, nv, f, nf, f_kind, flags, stream, out)),                                      \
+                             out, tree_index_free<pcu_hip_mesh_index>); }                                                                            \
 int pcu_hip_mesh_index_closest_##SUF(pcu_hip_ctx* c, const pcu_hip_mesh_index* ix, const T* p, int64_t np, T* out_d, int64_t* out_fi, T* out_bc,     \
                                      unsigned flags, void* stream, pcu_hip_stats* st) {                                                              \
     CallGuard dg(c); return abi_rc(mesh_call<T>(c, nullptr, ix, MeshPointsOp<T>{p}, np, out_d, out_fi, out_bc, flags, stream, st)); }
@@ -2739,9 +2752,8 @@ int pcu_hip_point_cloud_fast_winding_number_##SUF(pcu_hip_ctx* c, const T* p, co
 int pcu_hip_pc_winding_index_create_##SUF(pcu_hip_ctx* c, const T* p, const T* n, const T* a, int64_t np, unsigned flags, void* stream,              \
                                           pcu_hip_pc_winding_index** out) {                                                                          \
     CallGuard dg(c);                                                                                                                                 \
-    const int rc = abi_rc(pc_index_create_impl<T>(c, p, n, a, np, flags, stream, out));                                                              \
-    if (rc && out && *out) { DeviceGuard g(c->device); (void)hipDeviceSynchronize(); pc_index_free(*out); *out = nullptr; }                          \
-    return rc; }                                                                                                                                     \
+    return index_create_foot(c, abi_rc(pc_index_create_impl<T>(c, p, n, a, np, flags, stream, out)),                                                 \
+                             out, tree_index_free<pcu_hip_pc_winding_index>); }                                                                      \
 int pcu_hip_pc_winding_index_query_##SUF(pcu_hip_ctx* c, const pcu_hip_pc_winding_index* ix, const T* q, int64_t nq, double beta, T* out_w,          \
                                          unsigned flags, void* stream, pcu_hip_stats* st) {                                                          \
     CallGuard dg(c); return abi_rc(pc_call<T>(c, nullptr, ix, q, nq, beta, out_w, flags, stream, st)); }                                             \
@@ -2750,12 +2762,7 @@ int pcu_hip_estimate_mesh_face_normals_##SUF(pcu_hip_ctx* c, const T* v, int64_t
     CallGuard dg(c); return abi_rc(mesh_face_normals_impl<T>(c, MeshGiven<T>{v, nv, f, nf, f_kind}, out_n, flags, stream, st)); }
 PCU_PC_WIND(f32, float) PCU_PC_WIND(f64, double)
 #undef PCU_PC_WIND
-void pcu_hip_pc_winding_index_destroy(pcu_hip_pc_winding_index* ix) {
-    if (!ix) return;
-    DeviceGuard dg(ix->device);
-    (void)hipDeviceSynchronize();
-    pc_index_free(ix);
-}
+void pcu_hip_pc_winding_index_destroy(pcu_hip_pc_winding_index* ix) { index_destroy(ix, tree_index_free<pcu_hip_pc_winding_index>); }
 // ray_surfel_intersection and pointcloud_surfel_geometry (surfel.h, surfel_host.h)
 #define PCU_SURFEL(SUF, T)                                                                                                                            \
 int pcu_hip_surfel_geometry_##SUF(pcu_hip_ctx* c, const T* p, const T* n, const T* r, int64_t np, int subdivs, T* out_v, int32_t* out_f,             \
@@ -2769,22 +2776,16 @@ int pcu_hip_surfel_rays_##SUF(pcu_hip_ctx* c, const T* p, const T* n, const T* r
 int pcu_hip_surfel_index_create_##SUF(pcu_hip_ctx* c, const T* p, const T* n, const T* r, int64_t np, int subdivs, unsigned flags, void* stream,     \
                                       pcu_hip_surfel_index** out) {                                                                                  \
     CallGuard dg(c);                                                                                                                                 \
-    const int rc = abi_rc(surfel_index_create_impl<T>(c, p, n, r, np, subdivs, flags, stream, out));                                                 \
-    if (rc && out && *out) { DeviceGuard g(c->device); (void)hipDeviceSynchronize(); surfel_index_free(*out); *out = nullptr; }                      \
-    return rc; }                                                                                                                                     \
+    return index_create_foot(c, abi_rc(surfel_index_create_impl<T>(c, p, n, r, np, subdivs, flags, stream, out)),                                    \
+                             out, tree_index_free<pcu_hip_surfel_index>); }                                                                          \
 int pcu_hip_surfel_index_rays_##SUF(pcu_hip_ctx* c, const pcu_hip_surfel_index* ix, const T* ray_o, int64_t o_rows, const T* ray_d, int64_t n_rays,  \
                                     double ray_near, double ray_far, int64_t* out_pid, T* out_t, unsigned flags, void* stream, pcu_hip_stats* st) { \
     CallGuard dg(c);                                                                                                                                 \
     return abi_rc(surfel_call<T>(c, nullptr, ix, ray_o, o_rows, ray_d, n_rays, ray_near, ray_far, out_pid, out_t, flags, stream, st)); }
 PCU_SURFEL(f32, float) PCU_SURFEL(f64, double)
 #undef PCU_SURFEL
-int64_t pcu_hip_surfel_index_size(const pcu_hip_surfel_index* ix) { return ix ? ix->np : 0; }
-void pcu_hip_surfel_index_destroy(pcu_hip_surfel_index* ix) {
-    if (!ix) return;
-    DeviceGuard dg(ix->device);
-    (void)hipDeviceSynchronize();
-    surfel_index_free(ix);
-}
+int64_t pcu_hip_surfel_index_size(const pcu_hip_surfel_index* ix) { return ix ? ix->count : 0; }
+void pcu_hip_surfel_index_destroy(pcu_hip_surfel_index* ix) { index_destroy(ix, tree_index_free<pcu_hip_surfel_index>); }
 // voxelize_triangle_mesh, sparse_voxel_grid_boundary and voxel_grid_geometry (voxelize.h, voxelize_host.h)
 #define PCU_VOXELIZE(SUF, T)                                                                                                                          \
 int pcu_hip_voxelize_triangle_mesh_##SUF(pcu_hip_ctx* c, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, const double* voxel_size,    \
@@ -2855,12 +2856,7 @@ int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int 
 int pcu_hip_flood_fill_3d(pcu_hip_ctx* c, const void* grid, void* out, int64_t sx, int64_t sy, int64_t sz, const int64_t* seed3, int kind, double fill_value,
                           int64_t* out_filled, unsigned flags, void* stream, pcu_hip_stats* st) {
     CallGuard dg(c); return abi_rc(flood_fill_impl(c, grid, out, sx, sy, sz, seed3, kind, fill_value, out_filled, flags, stream, st)); }
-int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->nf : 0; }
-void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) {
-    if (!ix) return;
-    DeviceGuard dg(ix->device);
-    (void)hipDeviceSynchronize();
-    mesh_index_free(ix);
-}
+int64_t pcu_hip_mesh_index_size(const pcu_hip_mesh_index* ix) { return ix ? ix->count : 0; }
+void pcu_hip_mesh_index_destroy(pcu_hip_mesh_index* ix) { index_destroy(ix, tree_index_free<pcu_hip_mesh_index>); }
 
 }  // extern "C"

@@ -1,37 +1,20 @@
 // csrc/surfel_host.h -- host orchestration of ray_surfel_intersection, RaySurfelIntersector and pointcloud_surfel_geometry (kernels and
-// contract: surfel.h). The surfel tree is a MeshIdx whose elements are points (rows (p, A, B)); the rays go through mesh_run like the mesh's.
-// Included by pcu_hip.hip after pc_winding_host.h.
+// contract: surfel.h). The surfel tree is a MeshIdx whose elements are points (rows (p, A, B)): its handle, its create and its calls go
+// through the frames of mesh_host.h (TreeIndex, tree_index_create, tree_call), the rays through mesh_run like the mesh's. Included by
+// pcu_hip.hip after pc_winding_host.h.
 #pragma once
 
-// An oriented point cloud with radii kept on the GPU as its surfel tree (pcu_hip_surfel_index_*): one block owned by the object.
-struct pcu_hip_surfel_index {
-    int elem_size = 0;            // 4: float, 8: double
-    int device = 0;
-    int64_t np = 0;
-    int subdivs = 0;
-    void* mem = nullptr;
+// An oriented point cloud with radii kept on the GPU as its surfel tree (pcu_hip_surfel_index_*): the TreeIndex of mesh_host.h over points,
+// and the table its walk needs.
+struct pcu_hip_surfel_index : TreeIndex {
     const void* table = nullptr;  // (subdivs, 2): cos, sin in the scalar type, inside mem
-    MeshIdx<float> m32; MeshIdx<double> m64;
+    int subdivs = 0;
 };
-template <typename T> static const MeshIdx<T>& surfel_idx(const pcu_hip_surfel_index* p);
-template <> const MeshIdx<float>& surfel_idx<float>(const pcu_hip_surfel_index* p) { return p->m32; }
-template <> const MeshIdx<double>& surfel_idx<double>(const pcu_hip_surfel_index* p) { return p->m64; }
-static void surfel_index_free(pcu_hip_surfel_index* p) {
-    if (!p) return;
-    if (p->mem) (void)hipFree(p->mem);
-    delete p;
-}
-static int surfel_leaves_pow2(int64_t np) {
-    const int64_t leaves = (np + kSurfelLeaf - 1) / kSurfelLeaf;
-    int P = 1;
-    while (P < leaves) P <<= 1;
-    return P;
-}
 template <typename T> static size_t surfel_table_bytes(int subdivs) { return align_up((size_t)subdivs * 2 * sizeof(T), 256); }
 // head, table, 9 T and a row per point, a box per node
 template <typename T>
 static size_t surfel_index_bytes(int64_t np, int subdivs) {
-    const size_t N = (size_t)np, P = (size_t)surfel_leaves_pow2(np);
+    const size_t N = (size_t)np, P = (size_t)leaves_pow2(np, kSurfelLeaf);
     return align_up(sizeof(MeshHead<T>), 256) + surfel_table_bytes<T>(subdivs) + align_up(N * 9 * sizeof(T), 256) + align_up(N * 4, 256) +
            align_up(2 * P * 6 * sizeof(T), 256) + 1024;
 }
@@ -77,7 +60,7 @@ static int surfel_build(Arena& ari, Arena& ar, hipStream_t s, const T* p, const 
                         const T** table) {
     const T *dp = nullptr, *dn = nullptr, *dr = nullptr;
     if (stage_in(ar, p, np, on_dev, s, &dp) || stage_in(ar, n, np, on_dev, s, &dn) || stage_any(ar, r, (size_t)np, on_dev, s, &dr)) return -1;
-    M.nf = (int)np; M.P = surfel_leaves_pow2(np);
+    M.nf = (int)np; M.P = leaves_pow2(np, kSurfelLeaf);
     unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
     if (aalloc(ari, &M.head, 1) || surfel_table<T>(ari, s, subdivs, table) || aalloc(ari, &M.tri, (size_t)np * 9) || aalloc(ari, &M.face, (size_t)np) ||
         aalloc(ari, &M.box, (size_t)M.P * 12) ||
@@ -117,57 +100,34 @@ struct SurfelRaysOp : MeshRaysOp<T> {           // ray_surfel_intersection (src/
     }
 };
 
-// One call. Cloud given (`sf`): tree, rows and temporaries in the call's arena; index given (`ix`): rows and temporaries.
+// One call, the cloud given (`sf`) or its index (`ix`).
 template <typename T> struct SurfelGiven { const T* p; const T* n; const T* r; int64_t np; int subdivs; };
 template <typename T>
 static int surfel_call(pcu_hip_ctx* c, const SurfelGiven<T>* sf, const pcu_hip_surfel_index* ix, const T* ray_o, int64_t o_rows, const T* ray_d, int64_t n,
                        double ray_near, double ray_far, int64_t* out_pid, T* out_t, unsigned flags, void* stream, pcu_hip_stats* st) {
-    if (sf ? !c : (!c || !ix)) return fail(PCU_HIP_ERR_INVALID, sf ? "null context" : "null context / surfel index");
-    if (st) memset(st, 0, sizeof *st);
-    if (!sf) {
-        if (ix->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the surfel index was built for the other scalar type");
-        if (ix->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the surfel index lives on another device than the context");
-    }
+    if (int rc = tree_index_check<T>(c, ix, sf != nullptr, "surfel index", st)) return rc;
     SurfelRaysOp<T> op{{ray_o, o_rows, ray_d, ray_near, ray_far}, sf ? nullptr : static_cast<const T*>(ix->table), sf ? sf->subdivs : ix->subdivs};
     if (sf) { if (int rc = surfel_validate(sf->np, sf->subdivs)) return rc; }
     if (int rc = op.validate(n)) return rc;
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    size_t bytes = mesh_run_bytes<T>(n, SurfelRaysOp<T>::kRows3, on_dev);
-    if (sf) bytes += surfel_index_bytes<T>(sf->np, sf->subdivs) + surfel_build_bytes<T>(sf->np, on_dev);
-    return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
-        auto& [c, s, on_dev, ar, tm] = fr;
-        MeshIdx<T> built;
-        if (sf) { tm.mark(0); if (int rc = surfel_build<T>(ar, ar, s, sf->p, sf->n, sf->r, sf->np, sf->subdivs, on_dev, built, &op.table)) return rc; }
-        if (int rc = mesh_run<T>(ar, s, sf ? built : surfel_idx<T>(ix), op, n, on_dev, out_t, out_pid, nullptr, tm)) return rc;
-        mesh_stats(st, tm, n, sf != nullptr);
-        return 0;
-    });
+    const size_t given = sf ? surfel_index_bytes<T>(sf->np, sf->subdivs) + surfel_build_bytes<T>(sf->np, flags & PCU_HIP_PTRS_ON_DEVICE) : 0;
+    return tree_call<T>(c, flags, stream, st, sf ? nullptr : ix, given, [&](Arena& ar, hipStream_t s, bool on_dev, MeshIdx<T>& built, SurfelRaysOp<T>& op) {
+        return surfel_build<T>(ar, ar, s, sf->p, sf->n, sf->r, sf->np, sf->subdivs, on_dev, built, &op.table);
+    }, op, n, out_t, out_pid, nullptr);
 }
 
 template <typename T>
 static int surfel_index_create_impl(pcu_hip_ctx* c, const T* p, const T* n, const T* r, int64_t np, int subdivs, unsigned flags, void* stream,
                                     pcu_hip_surfel_index** out) {
-    if (!c || !out) return fail(PCU_HIP_ERR_INVALID, "null context / output");
-    *out = nullptr;
+    if (int rc = index_out_begin(c, out)) return rc;
     if (int rc = surfel_validate(np, subdivs)) return rc;
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    hipStream_t s = pick_stream(c, flags, stream);
-    pcu_hip_surfel_index* h = new pcu_hip_surfel_index();
-    h->elem_size = (int)sizeof(T); h->device = c->device; h->np = np; h->subdivs = subdivs;
-    const size_t bytes = surfel_index_bytes<T>(np, subdivs);
-    if (hipMalloc(&h->mem, bytes) != hipSuccess) { h->mem = nullptr; surfel_index_free(h); return fail(PCU_HIP_ERR_RUNTIME, "out of device memory for the surfel index"); }
-    if (ctx_begin(c, surfel_build_bytes<T>(np, on_dev))) { surfel_index_free(h); return PCU_HIP_ERR_RUNTIME; }
-    ArenaState blk;                                 // a bump allocator over the index's own block
-    blk.base = static_cast<char*>(h->mem); blk.cap = bytes;
-    Arena ari{&blk}, ar{c};
-    const T* table = nullptr;
-    int rc = surfel_build<T>(ari, ar, s, p, n, r, np, subdivs, on_dev, const_cast<MeshIdx<T>&>(surfel_idx<T>(h)), &table);
-    h->table = table;
-    if (!rc) rc = wait_stream(s);                   // (the temporaries go back to the context with this call)
-    rc = attempt_exit(c, index_block_exit(blk, rc, "surfel index"));
-    if (rc) { (void)hipStreamSynchronize(s); surfel_index_free(h); return rc; }
-    *out = h;
-    return 0;
+    return tree_index_create<T>(c, flags, stream, np, surfel_index_bytes<T>(np, subdivs), surfel_build_bytes<T>(np, on_dev), "surfel index", out,
+                                [&](Arena& ari, Arena& ar, hipStream_t s, pcu_hip_surfel_index& h) {
+        const T* table = nullptr;
+        const int rc = surfel_build<T>(ari, ar, s, p, n, r, np, subdivs, on_dev, tree_idx<T>(&h), &table);
+        h.table = table; h.subdivs = subdivs;
+        return rc;
+    });
 }
 
 // pointcloud_surfel_geometry (src/ray_point_cloud_intersection.cpp:321-340): (np (subdivs + 1), 3) vertices in T, (np subdivs, 3) int32 faces
