@@ -43,7 +43,7 @@ __all__ = ["k_nearest_neighbors", "one_sided_hausdorff_distance", "hausdorff_dis
            "connected_components", "flood_fill_3d",
            "marching_cubes_sparse_voxel_grid", "sparse_voxel_grid_to_hex_mesh",
            "adjacency_list", "mesh_vertex_adjacency", "estimate_mesh_vertex_normals", "laplacian_smooth_mesh",
-           "remove_mesh_vertices", "remove_unreferenced_mesh_vertices", "deduplicate_mesh_vertices", "orient_mesh_faces",
+           "remove_mesh_vertices", "remove_unreferenced_mesh_vertices", "deduplicate_mesh_vertices", "orient_mesh_faces", "decimate_triangle_mesh",
            "last_stats", "set_timing", "set_cell_occupancy", "device_count", "DatasetIndex", "cancel"]
 
 def cancel():
@@ -331,3 +331,4 @@ from ._components import connected_components, flood_fill_3d  # noqa: E402,F401
 from ._marching_cubes import marching_cubes_sparse_voxel_grid, sparse_voxel_grid_to_hex_mesh  # noqa: E402,F401
 from ._mesh_smooth import adjacency_list, mesh_vertex_adjacency, estimate_mesh_vertex_normals, laplacian_smooth_mesh  # noqa: E402,F401
 from ._mesh_repair import remove_mesh_vertices, remove_unreferenced_mesh_vertices, deduplicate_mesh_vertices, orient_mesh_faces  # noqa: E402,F401
+from ._mesh_decimate import decimate_triangle_mesh  # noqa: E402,F401

@@ -47,6 +47,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "marching_cubes.h"
 #include "mesh_smooth.h"
 #include "mesh_repair.h"
+#include "decimate.h"
 
 using namespace pcu;
 
@@ -214,7 +215,7 @@ struct ArenaState {
 };
 // A result whose size the caller learns from the call that made it waits in the context's `aux` block, as two segments (the second one
 // 256-aligned behind the first), for the _take call that repeats its two counts. One record: a context holds at most one such result.
-enum class Parked { None, VoxelRows, Surface, HexMesh, Adjacency };
+enum class Parked { None, VoxelRows, Surface, HexMesh, Adjacency, Decimated };
 struct ParkedResult { Parked kind = Parked::None; int64_t n0 = 0, n1 = 0; size_t bytes0 = 0, bytes1 = 0; };
 struct pcu_hip_ctx {
     int device = 0;
@@ -2467,6 +2468,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "marching_cubes_host.h"
 #include "mesh_smooth_host.h"
 #include "mesh_repair_host.h"
+#include "decimate_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2849,6 +2851,15 @@ PCU_MR_ABI(f64, double)
 int pcu_hip_orient_mesh_faces(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_f, void* out_c, int64_t* out_patches, unsigned flags,
                               void* stream, pcu_hip_stats* st) {
     CallGuard dg(c); return abi_rc(orient_mesh_faces_impl(c, f, nf, f_kind, nv, out_f, out_c, out_patches, flags, stream, st)); }
+// decimate_triangle_mesh (decimate.h, decimate_host.h)
+int pcu_hip_decimate_triangle_mesh_f32(pcu_hip_ctx* c, const float* v, int64_t nv, const void* f, int64_t nf, int f_kind, int64_t max_faces, int64_t* out_nv, int64_t* out_nf,
+                                       unsigned flags, void* stream, pcu_hip_stats* st) {
+    CallGuard dg(c); return abi_rc(decimate_impl<float>(c, MeshGiven<float>{v, nv, f, nf, f_kind}, max_faces, out_nv, out_nf, flags, stream, st)); }
+int pcu_hip_decimate_triangle_mesh_f64(pcu_hip_ctx* c, const double* v, int64_t nv, const void* f, int64_t nf, int f_kind, int64_t max_faces, int64_t* out_nv, int64_t* out_nf,
+                                       unsigned flags, void* stream, pcu_hip_stats* st) {
+    CallGuard dg(c); return abi_rc(decimate_impl<double>(c, MeshGiven<double>{v, nv, f, nf, f_kind}, max_faces, out_nv, out_nf, flags, stream, st)); }
+int pcu_hip_decimate_triangle_mesh_take(pcu_hip_ctx* c, int64_t nv, int64_t nf, void* out_v, void* out_f, void* out_corr_v, void* out_corr_f, unsigned flags, void* stream) {
+    CallGuard dg(c); return abi_rc(decimate_take_impl(c, nv, nf, out_v, out_f, out_corr_v, out_corr_f, flags, stream)); }
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
