@@ -44,6 +44,7 @@ __all__ = ["k_nearest_neighbors", "one_sided_hausdorff_distance", "hausdorff_dis
            "marching_cubes_sparse_voxel_grid", "sparse_voxel_grid_to_hex_mesh",
            "adjacency_list", "mesh_vertex_adjacency", "estimate_mesh_vertex_normals", "laplacian_smooth_mesh",
            "remove_mesh_vertices", "remove_unreferenced_mesh_vertices", "deduplicate_mesh_vertices", "orient_mesh_faces", "decimate_triangle_mesh",
+           "radius_search", "radius_count",
            "last_stats", "set_timing", "set_cell_occupancy", "device_count", "DatasetIndex", "cancel"]
 
 def cancel():
@@ -266,7 +267,8 @@ class DatasetIndex(_Handle):
 
     `dataset_points`: (m, 3) float32 / float64, numpy or CUDA/HIP torch tensor (copied; the caller's array can go away).
     `k_hint` sizes the grid cells for the k that will mostly be asked for; any k > 0 is answered exactly.
-    Queries must have the dataset's dtype. The index lives on one GPU; call close() (or use `with`) to free it."""
+    Queries must have the dataset's dtype. The index lives on one GPU; call close() (or use `with`) to free it.
+    radius_search / radius_count answer fixed-radius queries over the same grid."""
     _noun, _destroy = "index", "pcu_hip_index_destroy"
 
     def __init__(self, dataset_points, k_hint=1):
@@ -315,6 +317,16 @@ class DatasetIndex(_Handle):
                 dists = np.asfortranarray(dists)
         return dists, corrs
 
+    def radius_search(self, query_points, radius, squared_distances=False, sort_results=True):
+        """See point_cloud_utils_amd.radius_search; the dataset is the indexed one and the bytes returned are the free function's for every
+        radius (with sort_results=False the members are the same and their order follows the index's own grid). The index was laid out for
+        k-NN (k_hint): when the radius is large against its cells the scan walks more cells -- it stays exact and only gets slower."""
+        return _index_radius_search(self, query_points, radius, squared_distances, sort_results)
+
+    def radius_count(self, query_points, radius):
+        """See point_cloud_utils_amd.radius_count; the dataset is the indexed one (the note of radius_search on large radii holds here too)."""
+        return _index_radius_count(self, query_points, radius)
+
 
 from ._normals import estimate_point_cloud_normals_knn, estimate_point_cloud_normals_ball  # noqa: E402,F401
 from ._voxel import (morton_encode, morton_decode, morton_add, morton_subtract, morton_knn,  # noqa: E402,F401
@@ -332,3 +344,4 @@ from ._marching_cubes import marching_cubes_sparse_voxel_grid, sparse_voxel_grid
 from ._mesh_smooth import adjacency_list, mesh_vertex_adjacency, estimate_mesh_vertex_normals, laplacian_smooth_mesh  # noqa: E402,F401
 from ._mesh_repair import remove_mesh_vertices, remove_unreferenced_mesh_vertices, deduplicate_mesh_vertices, orient_mesh_faces  # noqa: E402,F401
 from ._mesh_decimate import decimate_triangle_mesh  # noqa: E402,F401
+from ._radius import radius_search, radius_count, _index_radius_search, _index_radius_count  # noqa: E402,F401

@@ -48,6 +48,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "mesh_smooth.h"
 #include "mesh_repair.h"
 #include "decimate.h"
+#include "radius.h"
 
 using namespace pcu;
 
@@ -215,7 +216,7 @@ struct ArenaState {
 };
 // A result whose size the caller learns from the call that made it waits in the context's `aux` block, as two segments (the second one
 // 256-aligned behind the first), for the _take call that repeats its two counts. One record: a context holds at most one such result.
-enum class Parked { None, VoxelRows, Surface, HexMesh, Adjacency, Decimated };
+enum class Parked { None, VoxelRows, Surface, HexMesh, Adjacency, Decimated, RadiusRows };
 struct ParkedResult { Parked kind = Parked::None; int64_t n0 = 0, n1 = 0; size_t bytes0 = 0, bytes1 = 0; };
 struct pcu_hip_ctx {
     int device = 0;
@@ -2208,11 +2209,13 @@ static int aux_reserve(pcu_hip_ctx* c, size_t bytes) {
     }
     return 0;
 }
-// Parking a result: reserve its two segments, have them written and waited for, commit. Nothing is parked in between.
-static int park_reserve(pcu_hip_ctx* c, size_t bytes0, size_t bytes1, char** seg0, char** seg1) {
-    if (aux_reserve(c, align_up(bytes0, 256) + bytes1 + 256)) return -1;
+// Parking a result: reserve its two segments, have them written and waited for, commit. Nothing is parked in between. work / wk: that many
+// bytes more behind the segments, for the call that makes the result.
+static int park_reserve(pcu_hip_ctx* c, size_t bytes0, size_t bytes1, char** seg0, char** seg1, size_t work = 0, char** wk = nullptr) {
+    if (aux_reserve(c, align_up(bytes0, 256) + align_up(bytes1, 256) + work + 256)) return -1;
     c->parked.bytes0 = bytes0; c->parked.bytes1 = bytes1;
     *seg0 = c->aux; *seg1 = c->aux + align_up(bytes0, 256);
+    if (wk) *wk = *seg1 + align_up(bytes1, 256);
     return 0;
 }
 static void park_commit(pcu_hip_ctx* c, Parked kind, int64_t n0, int64_t n1) { c->parked.kind = kind; c->parked.n0 = n0; c->parked.n1 = n1; }
@@ -2469,6 +2472,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "mesh_smooth_host.h"
 #include "mesh_repair_host.h"
 #include "decimate_host.h"
+#include "radius_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2860,6 +2864,27 @@ int pcu_hip_decimate_triangle_mesh_f64(pcu_hip_ctx* c, const double* v, int64_t 
     CallGuard dg(c); return abi_rc(decimate_impl<double>(c, MeshGiven<double>{v, nv, f, nf, f_kind}, max_faces, out_nv, out_nf, flags, stream, st)); }
 int pcu_hip_decimate_triangle_mesh_take(pcu_hip_ctx* c, int64_t nv, int64_t nf, void* out_v, void* out_f, void* out_corr_v, void* out_corr_f, unsigned flags, void* stream) {
     CallGuard dg(c); return abi_rc(decimate_take_impl(c, nv, nf, out_v, out_f, out_corr_v, out_corr_f, flags, stream)); }
+// radius_search and radius_count (radius.h, radius_host.h)
+#define PCU_RADIUS_ABI(SUF, T)                                                                                                                        \
+int pcu_hip_radius_search_##SUF(pcu_hip_ctx* c, const T* q, int64_t nq, const T* r, int64_t nr, double radius, int sort_results, int64_t* out_offsets, \
+                                int64_t* out_total, unsigned flags, void* stream, pcu_hip_stats* st) {                                               \
+    CallGuard dg(c); return abi_rc(radius_impl<T>(c, q, nq, r, nr, nullptr, radius, sort_results, false, out_offsets, out_total, flags, stream, st)); } \
+int pcu_hip_radius_count_##SUF(pcu_hip_ctx* c, const T* q, int64_t nq, const T* r, int64_t nr, double radius, int64_t* out_counts, unsigned flags,    \
+                               void* stream, pcu_hip_stats* st) {                                                                                    \
+    CallGuard dg(c); return abi_rc(radius_impl<T>(c, q, nq, r, nr, nullptr, radius, 0, true, out_counts, nullptr, flags, stream, st)); }              \
+int pcu_hip_index_radius_search_##SUF(pcu_hip_ctx* c, const pcu_hip_index* ix, const T* q, int64_t nq, double radius, int sort_results,              \
+                                      int64_t* out_offsets, int64_t* out_total, unsigned flags, void* stream, pcu_hip_stats* st) {                   \
+    if (!ix) return fail(PCU_HIP_ERR_INVALID, "null index");                                                                                         \
+    CallGuard dg(c); return abi_rc(radius_impl<T>(c, q, nq, nullptr, ix->n, ix, radius, sort_results, false, out_offsets, out_total, flags, stream, st)); } \
+int pcu_hip_index_radius_count_##SUF(pcu_hip_ctx* c, const pcu_hip_index* ix, const T* q, int64_t nq, double radius, int64_t* out_counts,            \
+                                     unsigned flags, void* stream, pcu_hip_stats* st) {                                                              \
+    if (!ix) return fail(PCU_HIP_ERR_INVALID, "null index");                                                                                         \
+    CallGuard dg(c); return abi_rc(radius_impl<T>(c, q, nq, nullptr, ix->n, ix, radius, 0, true, out_counts, nullptr, flags, stream, st)); }
+PCU_RADIUS_ABI(f32, float)
+PCU_RADIUS_ABI(f64, double)
+#undef PCU_RADIUS_ABI
+int pcu_hip_radius_search_take(pcu_hip_ctx* c, int64_t nq, int64_t total, int64_t* out_indices, void* out_dists, unsigned flags, void* stream) {
+    CallGuard dg(c); return abi_rc(radius_take_impl(c, nq, total, out_indices, out_dists, flags, stream)); }
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
