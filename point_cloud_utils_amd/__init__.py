@@ -44,7 +44,7 @@ __all__ = ["k_nearest_neighbors", "one_sided_hausdorff_distance", "hausdorff_dis
            "marching_cubes_sparse_voxel_grid", "sparse_voxel_grid_to_hex_mesh",
            "adjacency_list", "mesh_vertex_adjacency", "estimate_mesh_vertex_normals", "laplacian_smooth_mesh",
            "remove_mesh_vertices", "remove_unreferenced_mesh_vertices", "deduplicate_mesh_vertices", "orient_mesh_faces", "decimate_triangle_mesh",
-           "radius_search", "radius_count",
+           "radius_search", "radius_count", "downsample_point_cloud_farthest_point",
            "last_stats", "set_timing", "set_cell_occupancy", "device_count", "DatasetIndex", "cancel"]
 
 def cancel():
@@ -268,7 +268,7 @@ class DatasetIndex(_Handle):
     `dataset_points`: (m, 3) float32 / float64, numpy or CUDA/HIP torch tensor (copied; the caller's array can go away).
     `k_hint` sizes the grid cells for the k that will mostly be asked for; any k > 0 is answered exactly.
     Queries must have the dataset's dtype. The index lives on one GPU; call close() (or use `with`) to free it.
-    radius_search / radius_count answer fixed-radius queries over the same grid."""
+    radius_search / radius_count answer fixed-radius queries over the same grid; farthest_point_sample downsamples the dataset itself."""
     _noun, _destroy = "index", "pcu_hip_index_destroy"
 
     def __init__(self, dataset_points, k_hint=1):
@@ -327,6 +327,13 @@ class DatasetIndex(_Handle):
         """See point_cloud_utils_amd.radius_count; the dataset is the indexed one (the note of radius_search on large radii holds here too)."""
         return _index_radius_count(self, query_points, radius)
 
+    def farthest_point_sample(self, num_samples, start_index=0, return_distances=False, squared_distances=False):
+        """See point_cloud_utils_amd.downsample_point_cloud_farthest_point; the cloud is the indexed dataset, nothing is rebuilt, and the bytes
+        returned are the free function's (numpy arrays if the index was built from one, tensors on its device otherwise). Above the one-block
+        size the sampling walks the index's own cell order: cells sized for a small k_hint make its buckets long and thin, which costs
+        speed, never exactness."""
+        return _index_farthest_point_sample(self, num_samples, start_index, return_distances, squared_distances)
+
 
 from ._normals import estimate_point_cloud_normals_knn, estimate_point_cloud_normals_ball  # noqa: E402,F401
 from ._voxel import (morton_encode, morton_decode, morton_add, morton_subtract, morton_knn,  # noqa: E402,F401
@@ -345,3 +352,4 @@ from ._mesh_smooth import adjacency_list, mesh_vertex_adjacency, estimate_mesh_v
 from ._mesh_repair import remove_mesh_vertices, remove_unreferenced_mesh_vertices, deduplicate_mesh_vertices, orient_mesh_faces  # noqa: E402,F401
 from ._mesh_decimate import decimate_triangle_mesh  # noqa: E402,F401
 from ._radius import radius_search, radius_count, _index_radius_search, _index_radius_count  # noqa: E402,F401
+from ._fps import downsample_point_cloud_farthest_point, _index_farthest_point_sample  # noqa: E402,F401

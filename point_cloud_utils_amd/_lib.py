@@ -14,6 +14,8 @@ TIME_PHASES = 8
 TIME_KERNELS = 16
 STREAM_GIVEN = 32
 MESH_MOMENTS = 64
+FPS_ONE_BLOCK = 128       # pcu_hip_*fps_* only: force a path (tests)
+FPS_GRID = 256
 
 ERR_INVALID = -1
 ERR_CANCELLED = -4
@@ -44,7 +46,8 @@ _COMPUTE_ENTRY_POINTS = [f"pcu_hip_{op}_{suf}" for suf in ("f32", "f64") for op 
     "point_cloud_fast_winding_number", "pc_winding_index_create", "pc_winding_index_query", "estimate_mesh_face_normals",
     "surfel_geometry", "surfel_rays", "surfel_index_create", "surfel_index_rays", "voxelize_triangle_mesh", "marching_cubes",
     "mesh_vertex_normals", "laplacian_smooth_mesh", "remove_mesh_vertices", "remove_unreferenced_mesh_vertices",
-    "deduplicate_mesh_vertices", "decimate_triangle_mesh", "radius_search", "radius_count", "index_radius_search", "index_radius_count")] + [
+    "deduplicate_mesh_vertices", "decimate_triangle_mesh", "radius_search", "radius_count", "index_radius_search", "index_radius_count", "fps",
+    "index_fps")] + [
     "pcu_hip_orient_mesh_faces", "pcu_hip_decimate_triangle_mesh_take", "pcu_hip_radius_search_take"] + [
     "pcu_hip_morton_encode", "pcu_hip_morton_decode", "pcu_hip_morton_addsub", "pcu_hip_morton_knn",
     "pcu_hip_voxelize_take", "pcu_hip_sparse_voxel_grid_boundary", "pcu_hip_voxel_grid_geometry",
@@ -160,6 +163,9 @@ def lib():
             getattr(L, "pcu_hip_radius_count_" + sp).argtypes = [vp, vp, i64, vp, i64, dbl, vp, u, vp, vp]
             getattr(L, "pcu_hip_index_radius_search_" + sp).argtypes = [vp, vp, vp, i64, dbl, ci, vp, vp, u, vp, vp]
             getattr(L, "pcu_hip_index_radius_count_" + sp).argtypes = [vp, vp, vp, i64, dbl, vp, u, vp, vp]
+            getattr(L, "pcu_hip_fps_" + sp).argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, u, vp, vp]
+            getattr(L, "pcu_hip_index_fps_" + sp).argtypes = [vp, vp, i64, i64, vp, vp, vp, u, vp, vp]
+        L.pcu_hip_fps_geometry.argtypes = [vp]
         L.pcu_hip_radius_search_take.argtypes = [vp, i64, i64, vp, vp, u, vp]
         L.pcu_hip_orient_mesh_faces.argtypes = [vp, vp, i64, ci, i64, vp, vp, vp, u, vp, vp]
         L.pcu_hip_decimate_triangle_mesh_take.argtypes = [vp, i64, i64, vp, vp, vp, vp, u, vp]

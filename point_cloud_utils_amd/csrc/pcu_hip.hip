@@ -49,6 +49,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "mesh_repair.h"
 #include "decimate.h"
 #include "radius.h"
+#include "fps.h"
 
 using namespace pcu;
 
@@ -241,6 +242,11 @@ struct pcu_hip_ctx {
     char* kd_ws = nullptr; size_t kd_ws_cap = 0, kd_ws_off = 0;
     struct KdGraph { hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; const void* key_ptr = nullptr; long long key_m = 0; int key_leaf = 0; } kd_graph[4];   // [type][with second planeSplit loop]
     bool kd_need_ph2 = false;                 // sticky: this context has seen data with elements equal to a cut value
+    // farthest-point downsampling (fps_host.h): the block its kernels read the call from and the host writes the chain's step to (a fixed
+    // address), one executable graph per scalar type with the layout it was captured for, the progress marks of the replays in flight
+    char* fps_dev = nullptr;
+    struct FpsGraph { hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; char key[256] = {}; } fps_graph[2];
+    hipEvent_t fps_ev[8] = {};
     // Speculative tree top (kd_build_device, mode 1): a call whose predecessor needed the tie-order resolver starts the top levels of
     // the tree -- which do not depend on which queries are tied -- on spec_stream while the searches run; the resolver adopts them.
     struct KdSpec {
@@ -2473,6 +2479,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "mesh_repair_host.h"
 #include "decimate_host.h"
 #include "radius_host.h"
+#include "fps_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2548,6 +2555,9 @@ void pcu_hip_ctx_destroy(pcu_hip_ctx* c) {
     if (c->arena.base) (void)hipFree(c->arena.base);
     for (hipEvent_t e : {c->kd_spec.ev_fork, c->kd_spec.ev_init, c->kd_spec.ev_done}) if (e) (void)hipEventDestroy(e);
     kd_graph_drop(c);
+    for (auto& g : c->fps_graph) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
+    if (c->fps_dev) (void)hipFree(c->fps_dev);
+    for (auto& e : c->fps_ev) if (e) (void)hipEventDestroy(e);
     if (c->kd_ws) (void)hipFree(c->kd_ws);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->kev) if (e) (void)hipEventDestroy(e);
@@ -2885,6 +2895,23 @@ PCU_RADIUS_ABI(f64, double)
 #undef PCU_RADIUS_ABI
 int pcu_hip_radius_search_take(pcu_hip_ctx* c, int64_t nq, int64_t total, int64_t* out_indices, void* out_dists, unsigned flags, void* stream) {
     CallGuard dg(c); return abi_rc(radius_take_impl(c, nq, total, out_indices, out_dists, flags, stream)); }
+// farthest-point downsampling (fps.h, fps_host.h)
+#define PCU_FPS_ABI(SUF, T)                                                                                                                           \
+int pcu_hip_fps_##SUF(pcu_hip_ctx* c, const T* pts, int64_t n, int64_t num_samples, int64_t start_index, int64_t* out_idx, T* out_dists,             \
+                      int64_t* out_counters, unsigned flags, void* stream, pcu_hip_stats* st) {                                                      \
+    CallGuard dg(c); return abi_rc(fps_impl<T>(c, pts, n, nullptr, num_samples, start_index, out_idx, out_dists, out_counters, flags, stream, st)); } \
+int pcu_hip_index_fps_##SUF(pcu_hip_ctx* c, const pcu_hip_index* ix, int64_t num_samples, int64_t start_index, int64_t* out_idx, T* out_dists,       \
+                            int64_t* out_counters, unsigned flags, void* stream, pcu_hip_stats* st) {                                                \
+    if (!ix) return fail(PCU_HIP_ERR_INVALID, "null index");                                                                                         \
+    CallGuard dg(c); return abi_rc(fps_impl<T>(c, nullptr, ix->n, ix, num_samples, start_index, out_idx, out_dists, out_counters, flags, stream, st)); }
+PCU_FPS_ABI(f32, float)
+PCU_FPS_ABI(f64, double)
+#undef PCU_FPS_ABI
+int pcu_hip_fps_geometry(int out[4]) {
+    if (!out) return fail(PCU_HIP_ERR_INVALID, "null output");
+    out[0] = kFpsBlockRows; out[1] = kFpsBucket; out[2] = kFpsBlocks; out[3] = kFpsChain;
+    return 0;
+}
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
