@@ -170,9 +170,9 @@ class _Handle:
             raise ValueError(f"{what} and {self._noun} live on different devices")
 
     def close(self):
-        if self._h is not None:
-            getattr(_lib.lib(), self._destroy)(self._h)
-            self._h = None
+        h, self._h = self._h, None
+        if isinstance(h, ctypes.c_void_p):       # what _open made; anything else (a stand-in) is dropped, never handed to the library as a pointer
+            getattr(_lib.lib(), self._destroy)(h)
 
     def __enter__(self):
         return self

@@ -1,5 +1,5 @@
 """The argument checks that more than one feature module uses, one copy each: scalar types, the reference's shape checks with its texts
-(src/common/common.h), this package's row limit, what the library checks on the device found on the host for host arrays, and the placing of
+(src/common/common.h) and the k-NN family's pair checks (src/point_cloud_distance.cpp), this package's row limit, what the library checks on the device found on the host for host arrays, and the placing of
 further arrays beside the resolved ones of a call. Order, texts and exception types are part of the contract (tests/test_check_texts.py).
 It imports _call only."""
 import numpy as np
@@ -8,6 +8,15 @@ from ._call import _FACE_KINDS, _Dev, _dtype_name, _is_torch, _shape2
 
 _MAX_ROWS = 2 ** 27 - 16
 _ROW_LIMIT = "meshes and point clouds with more than 2^27-16 rows are not supported"
+_KNN_ROW_LIMIT = "point clouds with more than 2^27-16 rows are not supported"       # the k-NN family's text (csrc/pcu_hip.hip: validate_sizes)
+_KNN_ZERO = ("Invalid input set with zero elements: query_points and dataset_points must have shape (n, 3) and (m, 3). "
+             "Got query_points.shape = ({}, {}), dataset_points.shape = ({}, {}).")
+_KNN_DIM = ("Only 3D inputs are supported: query_points and dataset_points must have shape (n, 3) and (m, 3). "
+            "Got query_points.shape = ({}, {}), dataset_points.shape = ({}, {}).")
+_HD_ZERO = ("Invalid input set with zero elements: source and targets must have shape (n, 3) and (m, 3). "
+            "Got source.shape = ({}, {}), target.shape = ({}, {}).")
+_HD_DIM = ("Only 3D inputs are supported: source and targets must have shape (n, 3) and (m, 3). "
+           "Got source.shape = ({}, {}), target.shape = ({}, {}).")
 _SAME_DEVICE = "torch inputs must all be CUDA/HIP tensors on the same device"
 _RAY_ROWS = ("ray_o and ray_d must have the same number of rows (one ray origin per ray direction). "
              "(Note: ray_o can have one row to use the same origin for all directions)")
@@ -29,9 +38,34 @@ def _match(x, name, want, what):
         raise ValueError(f"Invalid scalar type ({dx}) for argument '{name}'. Expected it to match {what} which is of type {want}.")
 
 
-def _check_rows(*counts):
+def _check_rows(*counts, text=_ROW_LIMIT):
     if max(counts) > _MAX_ROWS:
-        raise ValueError(_ROW_LIMIT)
+        raise ValueError(text)
+
+
+def _check_pair(a, b, aname, bname, zero_fmt, dim_fmt):
+    """dtype / shape validation of two clouds in the order of src/point_cloud_distance.cpp:136-149 (and :195-208)."""
+    da, db = _check_float(a, aname), _dtype_name(b)
+    if db != da:
+        raise ValueError(f"Invalid scalar type ({db}) for argument '{bname}'. Expected it to match argument "
+                         f"'{aname}' which is of type {da}.")
+    sa, sb = _shape2(a), _shape2(b)
+    if sa[0] == 0 or sb[0] == 0:
+        raise ValueError(zero_fmt.format(sa[0], sa[1], sb[0], sb[1]))
+    if sa[1] != 3 or sb[1] != 3:
+        raise ValueError(dim_fmt.format(sa[0], sa[1], sb[0], sb[1]))
+    return da
+
+
+def _check_finite(x, text):
+    """For the calls that have no stable meaning for non-finite coordinates: numpy or torch, refused with the caller's text before any work."""
+    if _is_torch(x):
+        import torch
+        finite = bool(torch.isfinite(x).all())
+    else:
+        finite = bool(np.isfinite(x).all())
+    if not finite:
+        raise ValueError(text)
 
 
 def _size(a):

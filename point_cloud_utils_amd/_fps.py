@@ -6,8 +6,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._call import _Dev, _call, _is_torch, _shape2
-from ._checks import _NOT_3D, _ZERO_POINTS, _check_float, _check_rows
+from ._call import _Dev, _call, _shape2
+from ._checks import _NOT_3D, _ZERO_POINTS, _check_finite, _check_float, _check_rows
 
 
 def _check_counts(n, num_samples, start_index):
@@ -28,13 +28,7 @@ def _check_cloud(points):
         raise ValueError(_ZERO_POINTS.format(*sp))
     _check_rows(sp[0])
     # the Poisson-disk call's rule: no stable meaning for non-finite coordinates, refused before any work on them
-    if _is_torch(points):
-        import torch
-        finite = bool(torch.isfinite(points).all())
-    else:
-        finite = bool(np.isfinite(points).all())
-    if not finite:
-        raise ValueError("points must not contain NaN or infinite coordinates")
+    _check_finite(points, "points must not contain NaN or infinite coordinates")
     return sp[0]
 
 
@@ -103,11 +97,6 @@ def downsample_point_cloud_farthest_point(points, num_samples, start_index=0, re
 def _index_farthest_point_sample(index, num_samples, start_index=0, return_distances=False, squared_distances=False):
     index._check_open()
     num_samples, start_index = _check_counts(index.num_points, num_samples, start_index)
-    # no array comes with the call: the results are of the kind the index was built from (numpy, or tensors on its device)
-    if index._torch:
-        import torch
-        like = torch.empty((0, 3), dtype=torch.float32 if index._suffix == "f32" else torch.float64, device=torch.device("cuda", index._device))
-    else:
-        like = np.empty((0, 3), np.float32 if index._suffix == "f32" else np.float64)
+    like = index._like_built()        # no array comes with the call: the results are of the kind the index was built from
     d = _Dev(like, like)
     return _sample("index_fps", d, (index._h,), num_samples, start_index, return_distances, squared_distances)

@@ -1,11 +1,8 @@
 """estimate_point_cloud_normals_knn / _ball: the reference's wrappers (point_cloud_utils/_pointcloud_normals.py:4-56, :59-125)
 over the HIP plane-fit kernels (csrc/normals.h) instead of `_pcu_internal`. Same arguments, checks and returns."""
-import ctypes
-
 import numpy as np
 
-from . import _lib
-from ._call import Stats, _Dev, _dtype_name, _is_torch, _record
+from ._call import _Dev, _call, _dtype_name, _int_out, _is_torch
 
 
 def _run(kind, points, view_directions, drop_angle_threshold, max_points_per_leaf, **kw):
@@ -35,26 +32,17 @@ def _run(kind, points, view_directions, drop_angle_threshold, max_points_per_lea
         raise ValueError(f"Invalid scalar type ({_dtype_name(view_directions)}) for argument 'view_dirs'. Expected it to match argument 'points' which is of type {da}.")
     d = _Dev(points, view_directions if has_dirs else points)
     normals = d.empty((n, 3), "T")
-    if d.torch:
-        import torch
-        keep = torch.empty((n,), dtype=torch.uint8, device=d.tdev)
-    else:
-        keep = np.empty((n,), dtype=np.uint8)
-    st = Stats()
+    keep = _int_out(d, (n,), np.uint8)
     pdirs = d.pb if has_dirs else None
     if kind == "knn":
-        rc = getattr(_lib.lib(), "pcu_hip_normals_knn_" + d.suffix)(d.ctx, d.pa, n, pdirs, int(kw["num_neighbors"]), int(max_points_per_leaf),
-                                                                    float(drop_angle_threshold), _Dev.ptr(normals), _Dev.ptr(keep), d.flags, d.stream,
-                                                                    ctypes.addressof(st))
+        _call("normals_knn", d, d.pa, n, pdirs, int(kw["num_neighbors"]), int(max_points_per_leaf), float(drop_angle_threshold), _Dev.ptr(normals),
+              _Dev.ptr(keep))
     else:
-        rc = getattr(_lib.lib(), "pcu_hip_normals_ball_" + d.suffix)(d.ctx, d.pa, n, pdirs, float(kw["ball_radius"]), int(kw["min_pts_per_ball"]),
-                                                                     int(kw["max_pts_per_ball"]), 1 if kw["weight_function"] == "rbf" else 0,
-                                                                     float(drop_angle_threshold), _Dev.ptr(normals), _Dev.ptr(keep), d.flags, d.stream,
-                                                                     ctypes.addressof(st))
-    _lib.check(rc)
-    _record(st)
+        _call("normals_ball", d, d.pa, n, pdirs, float(kw["ball_radius"]), int(kw["min_pts_per_ball"]), int(kw["max_pts_per_ball"]),
+              1 if kw["weight_function"] == "rbf" else 0, float(drop_angle_threshold), _Dev.ptr(normals), _Dev.ptr(keep))
     # the reference returns the kept points' indices (ascending in its serial driver, :250-272) and their normals
     if d.torch:
+        import torch
         idx = torch.nonzero(keep).reshape(-1)
         return idx, normals[idx]
     idx = np.flatnonzero(keep).astype(np.int64)

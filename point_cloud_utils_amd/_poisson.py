@@ -6,8 +6,8 @@ import time
 
 import numpy as np
 
-from . import _lib
-from ._call import Stats, _Dev, _dtype_name, _is_torch, _record
+from ._call import _Dev, _call, _dtype_name, _int_out
+from ._checks import _check_finite
 
 
 def downsample_point_cloud_poisson_disk(v, radius, target_num_samples=-1, random_seed=0, sample_num_tolerance=0.04):
@@ -49,27 +49,14 @@ def downsample_point_cloud_poisson_disk(v, radius, target_num_samples=-1, random
     if n == 0:
         raise ValueError("Invalid point set with zero elements: v must have shape (n, 3) with n > 0. Got v.shape = (0, 3).")
     # The reference has no stable behaviour for non-finite coordinates (README.md): refused before any work on the device.
-    if _is_torch(v):
-        import torch
-        finite = bool(torch.isfinite(v).all())
-    else:
-        finite = bool(np.isfinite(v).all())
-    if not finite:
-        raise ValueError("v must not contain NaN or infinite coordinates")
+    _check_finite(v, "v must not contain NaN or infinite coordinates")
     seed = int(random_seed)
     if seed < 0 or seed > 0xFFFFFFFF:
         raise ValueError(f"random_seed must be an unsigned 32-bit integer, got {seed}")
     if seed == 0:                                          # the reference's documented behaviour: a seed from the clock
         seed = (time.time_ns() & 0xFFFFFFFF) or 1
     d = _Dev(v, v)
-    if d.torch:
-        import torch
-        out = torch.empty((n,), dtype=torch.int32, device=d.tdev)
-    else:
-        out = np.empty((n,), dtype=np.int32)
+    out = _int_out(d, (n,), np.int32)
     cnt = ctypes.c_int64(0)
-    st = Stats()
-    _lib.check(getattr(_lib.lib(), "pcu_hip_poisson_disk_" + d.suffix)(d.ctx, d.pa, n, radius, target_num_samples, seed, tol, _Dev.ptr(out),
-                                                                       ctypes.byref(cnt), d.flags, d.stream, ctypes.addressof(st)))
-    _record(st)
+    _call("poisson_disk", d, d.pa, n, radius, target_num_samples, seed, tol, _Dev.ptr(out), ctypes.byref(cnt))
     return out[:int(cnt.value)]

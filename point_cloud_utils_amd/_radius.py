@@ -6,16 +6,9 @@ import math
 
 import numpy as np
 
-from . import _KNN_DIM, _KNN_ZERO, _check_pair, _lib
+from . import _lib
 from ._call import _Dev, _call, _shape2, _take
-from ._checks import _MAX_ROWS, _check_float
-
-_ROW_LIMIT = "point clouds with more than 2^27-16 rows are not supported"       # the k-NN calls' text (csrc/pcu_hip.hip: validate_sizes)
-
-
-def _check_rows(*counts):
-    if max(counts) > _MAX_ROWS:
-        raise ValueError(_ROW_LIMIT)
+from ._checks import _KNN_DIM, _KNN_ROW_LIMIT, _KNN_ZERO, _check_pair, _check_rows
 
 
 def _check_radius(radius):
@@ -23,26 +16,6 @@ def _check_radius(radius):
     if not (radius >= 0.0) or math.isinf(radius):
         raise ValueError(f"Invalid radius ({radius}): must be finite and not negative.")
     return radius
-
-
-def _check_index_query(index, query_points, radius):
-    """The checks of DatasetIndex.k_nearest_neighbors, with its texts, and the radius'. Returns the resolved query and the radius."""
-    index._check_open()
-    dq = _check_float(query_points, "query_points")
-    want = "float32" if index._suffix == "f32" else "float64"
-    if dq != want:
-        raise ValueError(f"Invalid scalar type ({dq}) for argument 'query_points'. Expected it to match the indexed dataset which is of type {want}.")
-    sq = _shape2(query_points)
-    if sq[0] == 0:
-        raise ValueError(_KNN_ZERO.format(sq[0], sq[1], index.num_points, 3))
-    if sq[1] != 3:
-        raise ValueError(_KNN_DIM.format(sq[0], sq[1], index.num_points, 3))
-    _check_rows(sq[0])
-    radius = _check_radius(radius)
-    d = _Dev(query_points, query_points)
-    if d.torch:
-        index._same_device(d, "query tensor")
-    return d, radius
 
 
 def _search(name, d, head, radius, squared_distances, sort_results):
@@ -66,7 +39,7 @@ def _count(name, d, head, radius):
 
 def _check_free(query_points, dataset_points, radius):
     _check_pair(query_points, dataset_points, "query_points", "dataset_points", _KNN_ZERO, _KNN_DIM)
-    _check_rows(_shape2(query_points)[0], _shape2(dataset_points)[0])
+    _check_rows(_shape2(query_points)[0], _shape2(dataset_points)[0], text=_KNN_ROW_LIMIT)
     return _check_radius(radius)
 
 
@@ -116,11 +89,18 @@ def radius_count(query_points, dataset_points, radius):
     return _count("radius_count", d, (d.pa, int(d.a.shape[0]), d.pb, int(d.b.shape[0])), radius)
 
 
+def _check_index(index, query_points, radius):
+    """The handle's checks of a query, then the radius' as in the free functions, then the resolved query."""
+    index._check_query(query_points)
+    radius = _check_radius(radius)
+    return index._resolve_query(query_points), radius
+
+
 def _index_radius_search(index, query_points, radius, squared_distances=False, sort_results=True):
-    d, radius = _check_index_query(index, query_points, radius)
+    d, radius = _check_index(index, query_points, radius)
     return _search("index_radius_search", d, (index._h, d.pa, int(d.a.shape[0])), radius, squared_distances, sort_results)
 
 
 def _index_radius_count(index, query_points, radius):
-    d, radius = _check_index_query(index, query_points, radius)
+    d, radius = _check_index(index, query_points, radius)
     return _count("index_radius_count", d, (index._h, d.pa, int(d.a.shape[0])), radius)

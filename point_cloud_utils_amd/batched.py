@@ -13,8 +13,9 @@ import ctypes
 
 import numpy as np
 
-from . import _HD_DIM, _HD_ZERO, _KNN_DIM, _KNN_ZERO, _check_pair, _lib
-from ._call import Stats, _Dev, _record
+from . import _lib
+from ._call import _Dev, _call
+from ._checks import _HD_DIM, _HD_ZERO, _KNN_DIM, _KNN_ZERO, _check_pair
 
 CHUNK = 64          # pairs handed to one library call (bounds how many input clouds are alive at once)
 
@@ -70,16 +71,12 @@ def _run_chunk(kind, pairs, lanes, squared=False, p_norm=2.0, max_points_per_lea
     vp, i64 = ctypes.c_void_p, ctypes.c_int64
     xs = (vp * n)(*[d.pa for d in devs]); ys = (vp * n)(*[d.pb for d in devs])
     nxs = (i64 * n)(*[int(d.a.shape[0]) for d in devs]); nys = (i64 * n)(*[int(d.b.shape[0]) for d in devs])
-    L = _lib.lib()
-    L.pcu_hip_ctx_set_batch_lanes(d0.ctx, int(lanes))
-    st = Stats()
-    flags = d0.flags | (_lib.SQUARED if squared else 0)
+    _lib.lib().pcu_hip_ctx_set_batch_lanes(d0.ctx, int(lanes))
+    if squared:
+        d0.flags |= _lib.SQUARED
     if kind == "hausdorff":
         od = np.zeros((n, 2), dtype=d0.np_dtype); oi = np.zeros((n, 2), dtype=np.int64); oj = np.zeros((n, 2), dtype=np.int64)
-        rc = getattr(L, "pcu_hip_hausdorff_batch_" + d0.suffix)(d0.ctx, n, xs, nxs, ys, nys, int(max_points_per_leaf), od.ctypes.data,
-                                                                oi.ctypes.data, oj.ctypes.data, flags, d0.stream, ctypes.addressof(st))
-        _lib.check(rc)
-        _record(st)
+        _call("hausdorff_batch", d0, n, xs, nxs, ys, nys, int(max_points_per_leaf), od.ctypes.data, oi.ctypes.data, oj.ctypes.data)
         rows = []
         for p in range(n):       # point_cloud_utils/__init__.py:69-81 on Python floats, exactly as hausdorff_distance does
             hxy, ix1, iy1 = float(od[p, 0]), int(oi[p, 0]), int(oj[p, 0])
@@ -87,10 +84,7 @@ def _run_chunk(kind, pairs, lanes, squared=False, p_norm=2.0, max_points_per_lea
             rows.append((max(hxy, hyx), float(ix1), float(iy1)) if hxy > hyx else (max(hxy, hyx), float(ix2), float(iy2)))
         return rows
     means = np.zeros((n, 2), dtype=np.float64)
-    rc = getattr(L, "pcu_hip_chamfer_batch_" + d0.suffix)(d0.ctx, n, xs, nxs, ys, nys, float(p_norm), int(max_points_per_leaf),
-                                                          means.ctypes.data, flags, d0.stream, ctypes.addressof(st))
-    _lib.check(rc)
-    _record(st)
+    _call("chamfer_batch", d0, n, xs, nxs, ys, nys, float(p_norm), int(max_points_per_leaf), means.ctypes.data)
     # __init__.py:112-115: both means are scalars of the input dtype; their sum, in that dtype, is the result
     return [(float(d0.np_dtype(means[p, 1]) + d0.np_dtype(means[p, 0])),) for p in range(n)]
 

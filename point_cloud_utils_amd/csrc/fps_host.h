@@ -36,27 +36,24 @@ static int fps_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const pcu_hip_index
                     int64_t* out_counters, unsigned flags, void* stream, pcu_hip_stats* st) {
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
     if (out_counters) out_counters[0] = out_counters[1] = 0;
-    if (pidx) {
-        if (pidx->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the index was built for the other floating-point type");
-        if (pidx->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the index lives on device %d, the context on device %d", pidx->device, c->device);
-        n = pidx->n; pts = static_cast<const T*>(pidx->pts);
-    }
+    if (pidx) if (int rc = index_check<T>(c, pidx, &n)) return rc;
     if (n <= 0) return fail(PCU_HIP_ERR_INVALID, "Invalid input point cloud with zero points: points must have shape (n, 3) (n > 0). Got points.shape =(%lld, 3).", (long long)n);
     if (n > kMeshMaxRows) return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported");
     if (m < 1 || m > n) return fail(PCU_HIP_ERR_INVALID, "Invalid num_samples (%lld): must be at least 1 and at most the number of points (%lld).", (long long)m, (long long)n);
     if (start < 0 || start >= n) return fail(PCU_HIP_ERR_INVALID, "Invalid start_index (%lld): must be a row of points, in [0, %lld).", (long long)start, (long long)n);
-    if (!pts || !out_idx) return fail(PCU_HIP_ERR_INVALID, "null points / out_idx");
+    if ((!pidx && !pts) || !out_idx) return fail(PCU_HIP_ERR_INVALID, "null points / out_idx");
     const unsigned force = flags & (PCU_HIP_FPS_ONE_BLOCK | PCU_HIP_FPS_GRID);
     if (force == (PCU_HIP_FPS_ONE_BLOCK | PCU_HIP_FPS_GRID)) return fail(PCU_HIP_ERR_INVALID, "both farthest-point paths forced");
     const bool fits = n <= fps_block_rows(sizeof(T));
     if ((force & PCU_HIP_FPS_ONE_BLOCK) && !fits) return fail(PCU_HIP_ERR_INVALID, "the one-block path holds at most %lld rows of this type", (long long)fps_block_rows(sizeof(T)));
     const bool one_block = force ? (force & PCU_HIP_FPS_ONE_BLOCK) != 0 : fits;
-    const bool on_dev = (flags & PCU_HIP_PTRS_ON_DEVICE) != 0, pts_on_dev = on_dev || pidx;
+    const bool on_dev = (flags & PCU_HIP_PTRS_ON_DEVICE) != 0;
     const size_t N = (size_t)n, M = (size_t)m;
     const int nb = (int)((n + kFpsBucket - 1) / kFpsBucket), per = (nb + kFpsBlocks - 1) / kFpsBlocks;
     const size_t slots = (size_t)kFpsBlocks * per;
-    size_t bytes = 65536 + (pts_on_dev ? 0 : align_up(N * 3 * sizeof(T), 256)) + (on_dev ? 0 : align_up(M * 8, 256) + align_up(M * sizeof(T), 256));
-    if (!one_block) bytes += (pidx ? 0 : index_bytes<T>(n, kFpsOcc)) + align_up(N * sizeof(T), 256) + align_up(slots * 6 * sizeof(T), 256) + 3 * align_up(slots * 8, 256) +
+    DatasetFrame<T> ds{pidx, pts, n, on_dev};                           // (the one-block path takes the rows and no grid)
+    size_t bytes = 65536 + ds.bytes(kFpsOcc, !one_block) + (on_dev ? 0 : align_up(M * 8, 256) + align_up(M * sizeof(T), 256));
+    if (!one_block) bytes += align_up(N * sizeof(T), 256) + align_up(slots * 6 * sizeof(T), 256) + 3 * align_up(slots * 8, 256) +
                              align_up(slots * 3 * sizeof(T), 256) + 3 * align_up(2 * kFpsBlocks * 8, 256) + align_up(6 * kFpsBlocks * sizeof(T), 256);
     return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev_, ar, tm] = fr;      // marks 0-1: staging, index, bucket state; 1-2: the iterations
@@ -65,8 +62,7 @@ static int fps_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const pcu_hip_index
             HIP_TRY(hipMalloc((void**)&c->fps_dev, kFpsDevBytes));
             for (auto& e : c->fps_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        const T* dp = nullptr;
-        if (stage_in(ar, pts, n, pts_on_dev, s, &dp)) return -1;
+        if (ds.stage(ar, s)) return -1;
         long long* d_idx = reinterpret_cast<long long*>(out_idx); T* d_d = out_d;
         if (!on_dev) { if (aalloc(ar, &d_idx, M) || (out_d && aalloc(ar, &d_d, M))) return -1; }
         int* const d_bad = reinterpret_cast<int*>(c->fps_dev + kFpsDevBad);
@@ -77,20 +73,16 @@ static int fps_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const pcu_hip_index
             HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
             tm.mark(1);
             constexpr int P = kFpsBlockRows / kFpsBlockThreads / (int)(sizeof(T) / 4);       // points per lane: 64 registers of (x, y, z, mind) in either type
-            hipLaunchKernelGGL((k_fps_block<T, P>), dim3(1), dim3(kFpsBlockThreads), 0, s, dp, (int)n, (int)m, (int)start, d_idx, d_d, squared, d_bad);
+            hipLaunchKernelGGL((k_fps_block<T, P>), dim3(1), dim3(kFpsBlockThreads), 0, s, ds.rows, (int)n, (int)m, (int)start, d_idx, d_d, squared, d_bad);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
         } else {
             GridIndex<T> gi;
-            if (pidx) gi = index_grid<T>(pidx);
-            else {
-                if (index_alloc(ar, gi, n, kFpsOcc, IndexFor::Atomic)) return -1;
-                if (int rc = index_build(gi, dp, kFpsOcc, s)) return rc;
-            }
+            if (int rc = ds.grid(ar, s, gi, kFpsOcc, IndexFor::Atomic)) return rc;
             // the rule of this call: no NaN, no infinity (an index object may hold single-signed infinities: refused here). Before the
             // iterations are enqueued, so that their arithmetic never sees one.
             int nf = 0;
-            HIP_TRY(hipMemcpyAsync(&nf, reinterpret_cast<const char*>(gi.gp) + offsetof(GridParams<T>, nonfinite), sizeof(int), hipMemcpyDeviceToHost, s));
+            if (int rc = nonfinite_fetch(gi.gp, &nf, s)) return rc;
             HIP_WAIT(s);
             if (nf) return fail(PCU_HIP_ERR_INVALID, "points must not contain NaN or infinite coordinates");
             FpsArgs<T> a;
@@ -135,7 +127,7 @@ static int fps_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const pcu_hip_index
         if (bad) return fail(PCU_HIP_ERR_INVALID, "points must not contain NaN or infinite coordinates");
         if (out_counters) { out_counters[0] = (int64_t)cnt[0]; out_counters[1] = (int64_t)cnt[1]; }
         if (st) {
-            st->n_queries = n; st->n_passes = one_block ? 1 : (int)((m + kFpsChain - 1) / kFpsChain); st->n_grid_builds = (one_block || pidx) ? 0 : 1;
+            st->n_queries = n; st->n_passes = one_block ? 1 : (int)((m + kFpsChain - 1) / kFpsChain); st->n_grid_builds = ds.built;
             st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_total = tm.span(0, 2);
         }
         return 0;

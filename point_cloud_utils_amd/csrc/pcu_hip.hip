@@ -1420,57 +1420,91 @@ template <typename T> static const GridIndex<T>& index_grid(const pcu_hip_index*
 template <> const GridIndex<float>& index_grid<float>(const pcu_hip_index* p) { return p->g32; }
 template <> const GridIndex<double>& index_grid<double>(const pcu_hip_index* p) { return p->g64; }
 
+// The check of every call that is given an index object (the wrappers refuse a null one): built for this scalar type, on this context's device.
+template <typename T>
+static int index_check(const pcu_hip_ctx* c, const pcu_hip_index* pidx, int64_t* n) {
+    if (pidx->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the index was built for the other floating-point type");
+    if (pidx->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the index lives on device %d, the context on device %d", pidx->device, c->device);
+    *n = pidx->n;
+    return 0;
+}
+// The non-finite flags of a built grid's cloud (GridParams::nonfinite) on their way to *nf: no wait, the caller says when.
+template <typename T>
+static int nonfinite_fetch(const GridParams<T>* gp, int* nf, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(nf, reinterpret_cast<const char*>(gp) + offsetof(GridParams<T>, nonfinite), sizeof(int), hipMemcpyDeviceToHost, s));
+    return 0;
+}
 // Operators that do not run the grid searches (which carry the check, search.h: index_not_ready) look at the flags themselves: one read-back.
 template <typename T>
 static int check_nonfinite(const GridParams<T>* gp, int mask, hipStream_t s) {
     int nf = 0;
-    HIP_TRY(hipMemcpyAsync(&nf, reinterpret_cast<const char*>(gp) + offsetof(GridParams<T>, nonfinite), sizeof(int), hipMemcpyDeviceToHost, s));
+    if (int rc = nonfinite_fetch(gp, &nf, s)) return rc;
     HIP_WAIT(s);
     return (nf & mask) ? nonfinite_error(false) : 0;
 }
+// The dataset of a call, in two steps: its rows on the device and a grid over them. With an index object (after index_check) both are the
+// object's, as they are; without one the caller's rows are staged into the call's arena and a grid is allocated and built there. bytes() is
+// what the two steps take from the arena; `built` is the call's n_grid_builds.
+template <typename T>
+struct DatasetFrame {
+    const pcu_hip_index* pidx; const T* given; int64_t n; bool on_dev;
+    const T* rows = nullptr;
+    int built = 0;
+    size_t bytes(double occ, bool with_grid = true) const {
+        if (pidx) return 0;
+        return (on_dev ? 0 : align_up((size_t)n * 3 * sizeof(T), 256)) + (with_grid ? index_bytes<T>(n, occ) : 0);
+    }
+    int stage(Arena& ar, hipStream_t s) {
+        if (pidx) { rows = static_cast<const T*>(pidx->pts); return 0; }
+        return stage_in(ar, given, n, on_dev, s, &rows);
+    }
+    // h_want > 0: cells at least this large (GridIndex::h_want)
+    int grid(Arena& ar, hipStream_t s, GridIndex<T>& gi, double occ, IndexFor form, double h_want = 0.0) {
+        if (pidx) { gi = index_grid<T>(pidx); return 0; }
+        if (index_alloc(ar, gi, n, occ, form)) return -1;
+        gi.h_want = h_want;
+        if (int rc = index_build(gi, rows, occ, s)) return rc;
+        built = 1;
+        return 0;
+    }
+};
 // k beyond the grid search's capacity (k > 127): the reference's own algorithm for every query -- its kd-tree, rebuilt on the GPU
 // (kd_order.h), and its traversal with a wave-cooperative result set of k slots (k_kd_search_all). Any k > 0 is answered, as
 // the reference does (src/point_cloud_distance.cpp:133-135); slots beyond the dataset size are padded (-1, -1.0) (:90-93).
 template <typename T>
 static int knn_big_k(pcu_hip_ctx* c, const T* query, int64_t nq, const T* dataset, int64_t nr, int k, int max_leaf,
                      T* out_d, int64_t* out_i, unsigned flags, void* stream, pcu_hip_stats* st, const pcu_hip_index* pidx) {
-    const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE, squared = flags & PCU_HIP_SQUARED;
-    hipStream_t s = (stream || (flags & PCU_HIP_STREAM_GIVEN)) ? (hipStream_t)stream : c->own_stream;
-    if (st) memset(st, 0, sizeof *st);
-    c->time_phases = false; c->time_kernels = false;
+    const bool squared = flags & PCU_HIP_SQUARED;
     const size_t slot_bytes = (size_t)k * (sizeof(T) + 4);
     const bool rs_lds = slot_bytes <= 64 * 1024;
     int grid = (int)std::min<int64_t>(nq, 8192);
     if (!rs_lds) grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)1 << 30) / slot_bytes));
     const size_t out_bytes = align_up((size_t)nq * k * sizeof(T), 256) + align_up((size_t)nq * k * 8, 256);
-    size_t need = (pidx ? 0 : index_bytes<T>(nr, 2.0)) + (rs_lds ? 0 : 2 * align_up((size_t)grid * slot_bytes, 256)) +
-                  align_up((size_t)grid * 512 * sizeof(KdFrame<T>), 256) + 65536;
-    if (!on_dev) need += align_up((size_t)nq * 3 * sizeof(T), 256) + (pidx ? 0 : align_up((size_t)nr * 3 * sizeof(T), 256)) + out_bytes;
-    if (ctx_begin(c, need)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
-        const T *dq, *dr;
-        if ((rc = stage_in(ar, query, nq, on_dev, s, &dq))) break;
-        if (pidx) dr = static_cast<const T*>(pidx->pts);
-        else if ((rc = stage_in(ar, dataset, nr, on_dev, s, &dr))) break;
+    DatasetFrame<T> ds{pidx, dataset, nr, (flags & PCU_HIP_PTRS_ON_DEVICE) != 0};
+    size_t need = ds.bytes(2.0) + (rs_lds ? 0 : 2 * align_up((size_t)grid * slot_bytes, 256)) + align_up((size_t)grid * 512 * sizeof(KdFrame<T>), 256) + 65536;
+    if (!ds.on_dev) need += align_up((size_t)nq * 3 * sizeof(T), 256) + out_bytes;
+    return op_run(c, flags, stream, st, need, [&](OpFrame& fr) -> int {
+        auto& [c, s, on_dev, ar, tm] = fr;      // (no phase of this path is timed: the ms fields stay 0)
+        const T* dq;
+        if (int rc = stage_in(ar, query, nq, on_dev, s, &dq)) return rc;
+        if (int rc = ds.stage(ar, s)) return rc;
         T* dd = out_d; long long* di = (long long*)out_i;
-        if (!on_dev) { if ((rc = aalloc(ar, &dd, (size_t)nq * k))) break; if ((rc = aalloc(ar, &di, (size_t)nq * k))) break; }
+        if (!on_dev) { if (int rc = aalloc(ar, &dd, (size_t)nq * k)) return rc; if (int rc = aalloc(ar, &di, (size_t)nq * k)) return rc; }
         GridIndex<T> gi;                          // only its exact bounding box is used (root of the kd-tree)
-        if (pidx) gi = index_grid<T>(pidx);
-        else { if ((rc = index_alloc(ar, gi, nr, 2.0, IndexFor::TwoPass))) break; if ((rc = index_build(gi, dr, 2.0, s))) break; if (st) st->n_grid_builds = 1; }
-        if ((rc = check_nonfinite<T>(gi.gp, kNfNaN | kNfBothInf, s))) break;
+        if (int rc = ds.grid(ar, s, gi, 2.0, IndexFor::TwoPass)) return rc;
+        if (st) st->n_grid_builds = ds.built;
+        if (int rc = check_nonfinite<T>(gi.gp, kNfNaN | kNfBothInf, s)) return rc;
         KdBuild<T> b; int* err = nullptr; int levels = 0;
-        if ((rc = kd_build_device(c, ar, s, dr, (int)nr, gi.gp, max_leaf > 0 ? max_leaf : 10, b, &err, &levels, nullptr))) break;
+        if (int rc = kd_build_device(c, ar, s, ds.rows, (int)nr, gi.gp, max_leaf > 0 ? max_leaf : 10, b, &err, &levels, nullptr)) return rc;
         KdSearchArgs<T> a;
         a.E = b.E; a.nodes = b.nodes; a.qsorted = nullptr; a.qlist = nullptr; a.qcount_dev = nullptr;
         a.k = k; a.squared = squared ? 1 : 0; a.out_d = dd; a.out_i = di; a.error_flag = err;
         a.qraw = dq; a.nq_raw = (int)nq; a.rs_d = nullptr; a.rs_i = nullptr;
         a.cancel_word = g_cancel_mirror.load(std::memory_order_relaxed); a.cancel_gen = t_call_gen;
-        if (!rs_lds && ((rc = aalloc(ar, &a.rs_d, (size_t)grid * k)) || (rc = aalloc(ar, &a.rs_i, (size_t)grid * k)))) break;
+        if (!rs_lds) { if (int rc = aalloc(ar, &a.rs_d, (size_t)grid * k)) return rc; if (int rc = aalloc(ar, &a.rs_i, (size_t)grid * k)) return rc; }
         KdFrame<T>* frames = nullptr;
         a.stack_cap = levels + 2;
-        if ((rc = aalloc(ar, &frames, (size_t)grid * a.stack_cap))) break;
+        if (int rc = aalloc(ar, &frames, (size_t)grid * a.stack_cap)) return rc;
         a.stack = frames;
         static std::atomic<unsigned long long> attr_set[2];
         if (attr_unset_here(attr_set[sizeof(T) == 4 ? 0 : 1]))
@@ -1485,10 +1519,10 @@ static int knn_big_k(pcu_hip_ctx* c, const T* query, int64_t nq, const T* datase
             HIP_TRY(hipMemcpyAsync(out_i, di, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
         }
         HIP_WAIT(s);
-        if (herr) { rc = fail(PCU_HIP_ERR_RUNTIME, "internal: kd traversal exceeded the tree depth (%d)", levels); break; }
+        if (herr) return fail(PCU_HIP_ERR_RUNTIME, "internal: kd traversal exceeded the tree depth (%d)", levels);
         if (st) { st->n_queries = nq; st->n_passes = 1; }
-    } while (0);
-    return attempt_exit(c, rc);
+        return 0;
+    });
 }
 
 // The Pt4 records of two lean indexes (grid2.h), for everything that is not a lean fast path: a k = 1 job's two clouds, or a pair's.
@@ -1515,11 +1549,7 @@ template <typename T>
 static int knn_attempt(pcu_hip_ctx* c, const T* query, int64_t nq, const T* dataset, int64_t nr, int k, int max_leaf,
                        T* out_d, int64_t* out_i, unsigned flags, void* stream, pcu_hip_stats* st, const pcu_hip_index* pidx, int restarts, Outcome& out) {
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
-    if (pidx) {
-        if (pidx->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the index was built for the other floating-point type");
-        if (pidx->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the index lives on device %d, the context on device %d", pidx->device, c->device);
-        nr = pidx->n;
-    }
+    if (pidx) if (int rc = index_check<T>(c, pidx, &nr)) return rc;
     if (k <= 0) return fail(PCU_HIP_ERR_INVALID, "Invalid value for k (%d) must be greater than 0.", k);
     if (validate_sizes(nq, nr, "query_points", "dataset_points")) return PCU_HIP_ERR_INVALID;
     if (k > kMaxK) return knn_big_k<T>(c, query, nq, dataset, nr, k, max_leaf, out_d, out_i, flags, stream, st, pidx);
@@ -1891,7 +1921,7 @@ template <typename T>
 static int pair_nonfinite_flags(hipStream_t s, const PairState<T>& P, int (&nf)[2]) {
     const GridParams<T>* gp[2] = {P.xy.qidx.gp, P.xy.ridx.gp};
     for (int d = 0; d < 2; ++d)
-        HIP_TRY(hipMemcpyAsync(&nf[d], reinterpret_cast<const char*>(gp[d]) + offsetof(GridParams<T>, nonfinite), sizeof(int), hipMemcpyDeviceToHost, s));
+        if (int rc = nonfinite_fetch(gp[d], &nf[d], s)) return rc;
     HIP_WAIT(s);
     return 0;
 }
@@ -2293,27 +2323,26 @@ static int normals_ball_impl(pcu_hip_ctx* c, const T* points, int64_t n, const T
     if (max_pts > 0 && max_pts < 3) return fail(PCU_HIP_ERR_INVALID, "Invalid max_pts_per_ball (%d) must either be negative (no max) or a number greater than 3.", max_pts);
     if (validate_normals_input(n, dirs ? n : 0)) return PCU_HIP_ERR_INVALID;
     const double occ = 8.0;
-    size_t need = index_bytes<T>(n, occ) + align_up((size_t)n * sizeof(Pt4<T>), 256) + 8192;
-    if (!(flags & PCU_HIP_PTRS_ON_DEVICE)) need += 3 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n, 256);
+    DatasetFrame<T> ds{nullptr, points, n, (flags & PCU_HIP_PTRS_ON_DEVICE) != 0};
+    size_t need = ds.bytes(occ) + align_up((size_t)n * sizeof(Pt4<T>), 256) + 8192;
+    if (!ds.on_dev) need += 2 * align_up((size_t)n * 3 * sizeof(T), 256) + align_up((size_t)n, 256);
     return op_run(c, flags, stream, st, need, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;
-        const T *d_pts, *d_dirs = dirs;
+        const T* d_dirs = dirs;
         Pt4<T>* by_row = nullptr;
         if (int rc = aalloc(ar, &by_row, (size_t)n)) return rc;
-        if (int rc = stage_in(ar, points, n, on_dev, s, &d_pts)) return rc;
+        if (int rc = ds.stage(ar, s)) return rc;
         if (dirs) if (int rc = stage_in(ar, dirs, n, on_dev, s, &d_dirs)) return rc;
         T* d_out = out_n; uint8_t* d_keep = out_keep;
         if (!on_dev) { if (int rc = aalloc(ar, &d_out, (size_t)n * 3)) return rc; if (int rc = aalloc(ar, &d_keep, (size_t)n)) return rc; }
-        GridIndex<T> gi;
-        if (int rc = index_alloc(ar, gi, n, occ, IndexFor::Atomic)) return rc;
         const T radius_t = (T)ball_radius;                          // RadiusResultSet<DistanceType = T>(radius, ...)
-        gi.h_want = sqrt((double)radius_t) / 1.98;                  // cells of about half the true search radius: 5^3 cells per point
-        if (int rc = index_build(gi, d_pts, occ, s)) return rc;
+        GridIndex<T> gi;                                            // cells of about half the true search radius: 5^3 cells per point
+        if (int rc = ds.grid(ar, s, gi, occ, IndexFor::Atomic, sqrt((double)radius_t) / 1.98)) return rc;
         // the rule of every searched cloud (nonfinite_error): NaN, or +inf and -inf along one axis, is refused -- the reference's tree over such a cloud
         // has no stable answer. A row with single-signed infinities stays: its d2 is +inf or NaN against every row (itself included), so it is nobody's
         // member, it has no members and is dropped, and it sits in a border cell of a grid laid over the finite values (grid.h).
         if (int rc = check_nonfinite<T>(gi.gp, kNfNaN | kNfBothInf, s)) return rc;
-        if (st) { st->n_grid_builds = 1; st->n_queries = n; st->n_passes = 1; }
+        if (st) { st->n_grid_builds = ds.built; st->n_queries = n; st->n_passes = 1; }
         hipLaunchKernelGGL(k_cells_by_row<T>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, gi.gp, gi.sorted, gi.cell_start, (int)n, by_row);
         const NormalsBallArgs<T> a{gi.gp, by_row, gi.cell_start, d_dirs, (int)n, radius_t, ball_radius, min_pts, max_pts, weight_rbf, drop, d_out, d_keep};
         hipLaunchKernelGGL(k_normals_ball<T>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
@@ -2446,24 +2475,20 @@ static int index_create_impl(pcu_hip_ctx* c, const T* dataset, int64_t nr, int k
 template <typename T>
 static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64_t* out_vacc, int64_t* out_nnodes) {
     if (!c || n <= 0) return fail(PCU_HIP_ERR_INVALID, "bad arguments");
-    hipStream_t s = c->own_stream;
-    if (ctx_begin(c, index_bytes<T>(n, 2.0) + (size_t)n * 3 * sizeof(T) + 8192)) return PCU_HIP_ERR_RUNTIME;
-    Arena ar{c};
-    int rc = 0;
-    do {
-        const T* dp;
-        if ((rc = stage_in(ar, pts, n, false, s, &dp))) break;
+    DatasetFrame<T> ds{nullptr, pts, n, /*on_dev=*/false};
+    return op_run(c, 0, nullptr, nullptr, ds.bytes(2.0) + 8192, [&](OpFrame& fr) -> int {       // (host rows, the context's own stream, no statistics)
+        auto& [c, s, on_dev, ar, tm] = fr;
+        if (int rc = ds.stage(ar, s)) return rc;
         GridIndex<T> gi;
-        if ((rc = index_alloc(ar, gi, n, 2.0, IndexFor::TwoPass))) break;
-        if ((rc = index_build(gi, dp, 2.0, s))) break;
+        if (int rc = ds.grid(ar, s, gi, 2.0, IndexFor::TwoPass)) return rc;
         KdBuild<T> b; int* err = nullptr; int levels = 0, nn = 0;
-        if ((rc = kd_build_device(c, ar, s, dp, (int)n, gi.gp, leaf_max > 0 ? leaf_max : 10, b, &err, &levels, &nn))) break;
+        if (int rc = kd_build_device(c, ar, s, ds.rows, (int)n, gi.gp, leaf_max > 0 ? leaf_max : 10, b, &err, &levels, &nn)) return rc;
         std::vector<Pt4<T>> h((size_t)n);
         HIP_TRY(hipMemcpy(h.data(), b.E, (size_t)n * sizeof(Pt4<T>), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < n; ++i) out_vacc[i] = (int64_t)h[(size_t)i].idx;
         *out_nnodes = nn;
-    } while (0);
-    return attempt_exit(c, rc);
+        return 0;
+    });
 }
 
 #include "voxel_host.h"

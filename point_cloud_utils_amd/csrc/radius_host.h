@@ -7,12 +7,12 @@ constexpr unsigned long long kRadMaxTotal = 1ull << 31; // a result holds fewer 
 
 static unsigned rad_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
+// What a call takes from the arena beside its dataset (DatasetFrame::bytes).
 template <typename T>
-static size_t radius_bytes(int64_t nq, int64_t nr, bool own_index, bool on_dev) {
+static size_t radius_bytes(int64_t nq, int64_t nr, bool on_dev) {
     const size_t NQ = (size_t)nq, NR = (size_t)nr;
     size_t b = align_up(NR * sizeof(Pt4<T>), 256) + sort_bytes(NQ) + 3 * align_up(NQ * 4, 256) + align_up(NQ * 8, 256) + align_up((NQ + 1) * 8, 256) + 2 * scan_bytes(NQ) + 16384;
-    if (own_index) b += index_bytes<T>(nr, kRadOcc);
-    if (!on_dev) b += align_up(NQ * 3 * sizeof(T), 256) + align_up(NR * 3 * sizeof(T), 256) + align_up(NQ * 8, 256);
+    if (!on_dev) b += align_up(NQ * 3 * sizeof(T), 256) + align_up(NQ * 8, 256);
     return b;
 }
 // Rows longer than kRadBlockRow: three stable sorts of their members (dataset row, bits of d2, query row). One wait: how many members they hold.
@@ -48,31 +48,22 @@ static int radius_impl(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
     if (!c) return fail(PCU_HIP_ERR_INVALID, "null context");
     if (out_total) *out_total = 0;
     if (!count_only) c->parked = ParkedResult();
-    if (pidx) {
-        if (pidx->elem_size != (int)sizeof(T)) return fail(PCU_HIP_ERR_INVALID, "the index was built for the other floating-point type");
-        if (pidx->device != c->device) return fail(PCU_HIP_ERR_INVALID, "the index lives on device %d, the context on device %d", pidx->device, c->device);
-        nr = pidx->n;
-    }
+    if (pidx) if (int rc = index_check<T>(c, pidx, &nr)) return rc;
     if (int rc = validate_sizes(nq, nr, "query_points", "dataset_points")) return rc;
     if (!(radius >= 0.0) || std::isinf(radius)) return fail(PCU_HIP_ERR_INVALID, "Invalid radius (%g): must be finite and not negative.", radius);
     if (!query || (!pidx && !dataset) || !out || (!count_only && !out_total)) return fail(PCU_HIP_ERR_INVALID, "null query / dataset / output");
     const T rt = (T)radius, r2 = rt * rt;                               // one multiply, rounded in T
     const T reach = (T)sqrt((double)r2) * ((T)1 + (T)8 * std::numeric_limits<T>::epsilon());
-    const size_t bytes = radius_bytes<T>(nq, nr, !pidx, (flags & PCU_HIP_PTRS_ON_DEVICE) != 0);
+    DatasetFrame<T> ds{pidx, dataset, nr, (flags & PCU_HIP_PTRS_ON_DEVICE) != 0};
+    const size_t bytes = ds.bytes(kRadOcc) + radius_bytes<T>(nq, nr, ds.on_dev);
     return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: index, record order, query order, 1-2: count pass, 2-3: scan, wait and fill pass, 3-4: row sort
         tm.mark(0);
         const T* dq = nullptr;
-        if (stage_in(ar, query, nq, on_dev, s, &dq)) return -1;
+        if (stage_in(ar, query, nq, on_dev, s, &dq) || ds.stage(ar, s)) return -1;
+        const double h = sqrt((double)r2) * 1.01;                       // the call's own grid: cells no smaller than the radius, a ball's box is 3^3 cells
         GridIndex<T> gi;
-        if (pidx) gi = index_grid<T>(pidx);
-        else {
-            const T* dr = nullptr;
-            if (stage_in(ar, dataset, nr, on_dev, s, &dr) || index_alloc(ar, gi, nr, kRadOcc, IndexFor::Atomic)) return -1;
-            const double h = sqrt((double)r2) * 1.01;                   // cells no smaller than the radius: a ball's box is 3^3 cells
-            gi.h_want = std::isfinite(h) ? h : 0.0;
-            if (int rc = index_build(gi, dr, kRadOcc, s)) return rc;
-        }
+        if (int rc = ds.grid(ar, s, gi, kRadOcc, IndexFor::Atomic, std::isfinite(h) ? h : 0.0)) return rc;
         // the records of every cell in ascending row order: the walk's order is then a function of the input (normals.h: k_cells_by_row)
         Pt4<T>* by_row = nullptr;
         if (aalloc(ar, &by_row, (size_t)nr)) return -1;
@@ -92,8 +83,8 @@ static int radius_impl(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         tm.mark(2);
         // the rule of every searched cloud (nonfinite_error): read with the call's one read-back; an index object was checked when it was made
         int nf = 0;
-        if (!pidx) HIP_TRY(hipMemcpyAsync(&nf, reinterpret_cast<const char*>(gi.gp) + offsetof(GridParams<T>, nonfinite), sizeof(int), hipMemcpyDeviceToHost, s));
-        if (st) { st->n_grid_builds = pidx ? 0 : 1; st->n_queries = nq; st->n_passes = 1; }
+        if (!pidx) if (int rc = nonfinite_fetch(gi.gp, &nf, s)) return rc;
+        if (st) { st->n_grid_builds = ds.built; st->n_queries = nq; st->n_passes = 1; }
         if (count_only) {
             long long* d_out = reinterpret_cast<long long*>(out);
             if (!on_dev && aalloc(ar, &d_out, (size_t)nq)) return -1;

@@ -222,7 +222,7 @@ def test_handles_refuse_another_device(no_device, monkeypatch):
             x._h = None                                                     # (nothing to destroy when the stub goes)
     # the dataset index compares devices for tensors only: a numpy query passes that line and goes on to the library
     x = stub(pcu.DatasetIndex, "handle", num_points=4)
-    monkeypatch.setattr(pcu, "_fn", lambda op, suffix: pytest.fail("reached " + op, pytrace=False))
+    monkeypatch.setattr("point_cloud_utils_amd._call._fn", lambda op, suffix: pytest.fail("reached " + op, pytrace=False))
     with pytest.raises(pytest.fail.Exception, match="reached index_knn"):
         x.k_nearest_neighbors(P, 1)
     x._h = None
@@ -238,3 +238,6 @@ def test_closing_is_idempotent_and_safe_without_a_handle(no_device):
             assert y is x
         x.__del__()
         object.__new__(cls).__del__()                                       # an object whose __init__ raised before the create call
+        x = stub(cls, "handle")                                             # not a handle the create call made: dropped, the library is not reached
+        x.close()
+        assert x._h is None

@@ -40,6 +40,10 @@ def _torch(*arrays):
     return tuple(torch.from_numpy(np.ascontiguousarray(a)).cuda() if isinstance(a, np.ndarray) else a for a in arrays)
 
 
+def _has_array(args):
+    return any(isinstance(a, np.ndarray) for a in args)
+
+
 class Kind:
     """One handle kind at one size and dtype: what it is built from, its queries, the one-shot twin of each query method."""
 
@@ -53,7 +57,12 @@ class Kind:
         if kind == "dataset":
             self.built, self.make = (pts,), pcu.DatasetIndex
             self.calls = [("k_nearest_neighbors", (q, 1), lambda b, a: pcu.k_nearest_neighbors(a[0], b[0], 1)),
-                          ("k_nearest_neighbors", (q, 3), lambda b, a: pcu.k_nearest_neighbors(a[0], b[0], 3))]
+                          ("k_nearest_neighbors", (q, 3), lambda b, a: pcu.k_nearest_neighbors(a[0], b[0], 3)),
+                          ("radius_search", (q, 0.5), lambda b, a: pcu.radius_search(a[0], b[0], 0.5)),
+                          ("radius_search", (q, 0.5, True, True), lambda b, a: pcu.radius_search(a[0], b[0], 0.5, squared_distances=True, sort_results=True)),
+                          ("radius_count", (q, 0.5), lambda b, a: pcu.radius_count(a[0], b[0], 0.5)),
+                          ("farthest_point_sample", (min(n, 64), 0, True),      # no array argument: the result is of the kind the index was built from
+                           lambda b, a: pcu.downsample_point_cloud_farthest_point(b[0], min(n, 64), 0, return_distances=True))]
         elif kind == "mesh":
             v = rng.random((n + 2, 3)).astype(dtype)
             f = np.stack([np.arange(n), np.arange(n) + 1, np.arange(n) + 2], axis=1).astype(np.int32)       # a strip of n faces
@@ -91,7 +100,8 @@ def test_a_handle_answers_as_the_one_shot_call_does(pcu, kind, n, dtype):
             for h in (from_numpy, from_torch):
                 _same(getattr(h, method)(*args), want)
                 got = getattr(h, method)(*t_args)
-                assert all(hasattr(x, "detach") for x in (got if isinstance(got, tuple) else (got,)))
+                tensors_out = _has_array(args) or h is from_torch               # tensors in, tensors out; without an array: what the handle was built from
+                assert all(hasattr(x, "detach") == tensors_out for x in (got if isinstance(got, tuple) else (got,)))
                 _same(got, want)
         size = {"dataset": "pcu_hip_index_size", "mesh": "pcu_hip_mesh_index_size", "surfel": "pcu_hip_surfel_index_size"}.get(kind)
         if size:
@@ -119,6 +129,8 @@ def test_life_cycle_and_closed_use(pcu, kind, dtype):
             h._device = real
         real, h._device = h._device, h._device + 1
         for method, args, _ in c.calls:
+            if not _has_array(args):                                            # (no tensor comes with the call: nothing to compare)
+                continue
             with pytest.raises(ValueError) as e:
                 getattr(h, method)(*_torch(*args))
             what = "query tensor" if kind == "dataset" else "rays" if method == "intersect_rays" else "query points"
@@ -141,13 +153,14 @@ def test_life_cycle_and_closed_use(pcu, kind, dtype):
 def _abi_queries(L, kind, suf, ctx, handle, n=3):
     """The query entry points of a family for the scalar suffix `suf`, as calls through the C ABI on `n` rows of zeros."""
     T = np.float32 if suf == "f32" else np.float64
-    arrays = np.zeros((n, 3), T), np.zeros(n, T), np.zeros((n, 3), T), np.zeros(n, np.int64)
-    q, val, bc, idx = (a.ctypes.data for a in arrays)
+    arrays = np.zeros((n, 3), T), np.zeros(n, T), np.zeros((n, 3), T), np.zeros(n + 1, np.int64), np.zeros(1, np.int64)
+    q, val, bc, idx, total = (a.ctypes.data for a in arrays)
 
     def fn(name, *args):
         return lambda keep=arrays: getattr(L, f"pcu_hip_{name}_{suf}")(ctx, handle, *args, 0, None, None)
     if kind == "dataset":
-        return [fn("index_knn", q, n, 1, 10, val, idx)]
+        return [fn("index_knn", q, n, 1, 10, val, idx), fn("index_radius_search", q, n, 0.5, 1, idx, total), fn("index_radius_count", q, n, 0.5, idx),
+                fn("index_fps", 1, 0, idx, val, None)]
     if kind == "mesh":
         return [fn("mesh_index_closest", q, n, val, idx, bc), fn("mesh_index_rays", q, n, q, n, 0.0, 1.0, idx, bc, val),
                 fn("mesh_index_winding", q, n, 2.0, val), fn("mesh_index_signed_distance", q, n, -1.0, 1.0, 2.0, val, idx, bc)]

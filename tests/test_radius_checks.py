@@ -62,8 +62,9 @@ def stub(num_points, suffix="f32", handle="handle"):
     return x
 
 
-@pytest.mark.parametrize("method", ["radius_search", "radius_count"])
+@pytest.mark.parametrize("method", ["radius_search", "radius_count", "k_nearest_neighbors"])
 def test_dataset_index_methods_check_before_the_device(method):
+    """The three query methods share one check of the query (1.0: the radius, or k = 1); each then refuses its own parameter."""
     refuses("the index has been closed", getattr(stub(5, handle=None), method), Q, 1.0)
     call = getattr(stub(5), method)
     refuses("Invalid scalar type (int32) for argument 'query_points'. Expected one of ['float32', 'float64'].", call, Q.astype(np.int32), 1.0)
@@ -73,6 +74,9 @@ def test_dataset_index_methods_check_before_the_device(method):
     refuses("Only 3D inputs are supported: query_points and dataset_points must have shape (n, 3) and (m, 3). "
             "Got query_points.shape = (4, 2), dataset_points.shape = (5, 3).", call, Q[:, :2], 1.0)
     refuses("point clouds with more than 2^27-16 rows are not supported", call, many_rows(np.float32), 1.0)
+    if method == "k_nearest_neighbors":
+        refuses("Invalid value for k (0) must be greater than 0.", call, Q, 0)
+        return
     for radius, shown in ((float("nan"), "nan"), (-2.0, "-2.0"), (float("inf"), "inf")):
         refuses(f"Invalid radius ({shown}): must be finite and not negative.", call, Q, radius)
 
