@@ -84,30 +84,19 @@ __global__ __launch_bounds__(kBlock) void k_cc_flatten(unsigned* parent, unsigne
 }
 
 // ---------------------------------------------------------------------------------------------------- connected_components
-// An index of any of the four integer types (kind 0 int32, 1 int64, 2 uint32, 3 uint64); a negative one becomes a huge unsigned one.
-__device__ __forceinline__ unsigned long long cc_index_in(const void* __restrict__ p, int kind, size_t at) {
-    if (kind == 0) return (unsigned long long)(long long)static_cast<const int*>(p)[at];
-    if (kind == 1) return (unsigned long long)static_cast<const long long*>(p)[at];
-    if (kind == 2) return (unsigned long long)static_cast<const unsigned*>(p)[at];
-    return static_cast<const unsigned long long*>(p)[at];
-}
-__device__ __forceinline__ void cc_index_out(void* __restrict__ p, int kind, size_t at, unsigned x) {
-    if (kind == 0 || kind == 2) static_cast<unsigned*>(p)[at] = x;
-    else static_cast<unsigned long long*>(p)[at] = x;
-}
 // One thread per face: (f0, f1) and (f1, f2); the third edge follows. A face with an index outside [0, nv) raises the flag and joins nothing.
 __global__ __launch_bounds__(kBlock) void k_cc_faces(const void* __restrict__ f, int kind, unsigned nf, unsigned nv, unsigned* parent, int* __restrict__ bad) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     bool out = false;
     if (i < nf) {
-        const unsigned long long a = cc_index_in(f, kind, 3 * (size_t)i), b = cc_index_in(f, kind, 3 * (size_t)i + 1), c = cc_index_in(f, kind, 3 * (size_t)i + 2);
-        out = a >= nv || b >= nv || c >= nv;
+        int id[3];
+        out = face_in(f, kind, (size_t)i, nv, id);
         if (!out) {
-            if (a != b) cc_union(parent, (unsigned)a, (unsigned)b);
-            if (b != c) cc_union(parent, (unsigned)b, (unsigned)c);
+            if (id[0] != id[1]) cc_union(parent, (unsigned)id[0], (unsigned)id[1]);
+            if (id[1] != id[2]) cc_union(parent, (unsigned)id[1], (unsigned)id[2]);
         }
     }
-    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
+    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, kMeshBadFace);
 }
 // cnt[label] += 1 for every active lane, as one add per run of equal labels among consecutive lanes. The active lanes are the wave's first ones.
 __device__ __forceinline__ void cc_count(unsigned label, bool active, unsigned* __restrict__ cnt) {
@@ -125,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_vertex_labels(const unsigned* __r
                                                              void* __restrict__ out_cv, unsigned* __restrict__ cnt) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     unsigned label = 0;
-    if (i < nv) { label = scan[parent[i]] - 1u; cc_index_out(out_cv, kind, i, label); }
+    if (i < nv) { label = scan[parent[i]] - 1u; index_out(out_cv, kind, i, label); }
     cc_count(label, i < nv, cnt);
 }
 // cf[i] = cv[f[i, 0]]
@@ -134,9 +123,9 @@ __global__ __launch_bounds__(kBlock) void k_cc_face_labels(const void* __restric
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     unsigned label = 0;
     if (i < nf) {
-        const unsigned long long a = cc_index_in(f, kind, 3 * (size_t)i);
+        const unsigned long long a = index_in(f, kind, 3 * (size_t)i);
         if (a < nv) label = scan[parent[a]] - 1u;             // (a call with an index outside [0, nv) is refused before this launch)
-        cc_index_out(out_cf, kind, i, label);
+        index_out(out_cf, kind, i, label);
     }
     cc_count(label, i < nf, cnt);
 }
@@ -144,8 +133,8 @@ __global__ __launch_bounds__(kBlock) void k_cc_counts_out(const unsigned* __rest
                                                           void* __restrict__ out_nv, void* __restrict__ out_nf) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= count) return;
-    cc_index_out(out_nv, kind, i, cnt_v[i]);
-    cc_index_out(out_nf, kind, i, cnt_f[i]);
+    index_out(out_nv, kind, i, cnt_v[i]);
+    index_out(out_nf, kind, i, cnt_f[i]);
 }
 
 // ---------------------------------------------------------------------------------------------------- flood_fill_3d

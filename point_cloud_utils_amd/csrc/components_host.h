@@ -1,8 +1,7 @@
 // csrc/components_host.h -- host orchestration of connected_components and flood_fill_3d (kernels and contract: components.h). Included by
-// pcu_hip.hip after the operator frame (op_run, stage_any), voxel_host.h (the scan) and mesh_host.h (mesh_validate, int_kind_bytes).
+// pcu_hip.hip after the operator frame (op_run, stage_faces, out_room / out_give, the flag word's helpers), voxel_host.h (the scan) and
+// mesh_host.h (mesh_validate).
 #pragma once
-
-static unsigned cc_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 // connected_components (src/connected_components.cpp:11-110). out_cv (nv), out_cf (nf), out_nv and out_nf (room for nv; *out_count rows are
 // written) in the integer type f_kind names. One wait for the component count and the range flag; with host pointers a second one for the copies.
@@ -19,41 +18,38 @@ static int connected_components_impl(pcu_hip_ctx* c, const void* f, int64_t nf, 
     return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: union, 1-2: flatten and rank, 3-4: labels and counts
         const char* d_f = nullptr;
-        if (stage_any(ar, static_cast<const char*>(f), NF * 3 * kb, on_dev, s, &d_f)) return -1;
+        if (stage_faces(ar, f, NF, f_kind, on_dev, s, &d_f)) return -1;
         unsigned *parent = nullptr, *flag = nullptr, *scan = nullptr, *cnt_v = nullptr, *cnt_f = nullptr; int* d_bad = nullptr;
-        if (aalloc(ar, &parent, NV) || aalloc(ar, &flag, NV) || aalloc(ar, &scan, NV) || aalloc(ar, &cnt_v, NV) || aalloc(ar, &cnt_f, NV) || aalloc(ar, &d_bad, 1)) return -1;
+        if (aalloc(ar, &parent, NV) || aalloc(ar, &flag, NV) || aalloc(ar, &scan, NV) || aalloc(ar, &cnt_v, NV) || aalloc(ar, &cnt_f, NV) || flag_word(ar, s, &d_bad)) return -1;
         const unsigned unv = (unsigned)nv, unf = (unsigned)nf;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
         HIP_TRY(hipMemsetAsync(cnt_v, 0, NV * 4, s));
         HIP_TRY(hipMemsetAsync(cnt_f, 0, NV * 4, s));
         tm.mark(0);
-        hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(NV)), dim3(kBlock), 0, s, parent, unv);
-        hipLaunchKernelGGL(k_cc_faces, dim3(cc_blocks(NF)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, unf, unv, parent, d_bad);
+        hipLaunchKernelGGL(k_cc_init, dim3(blocks_for(NV)), dim3(kBlock), 0, s, parent, unv);
+        hipLaunchKernelGGL(k_cc_faces, dim3(blocks_for(NF)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, unf, unv, parent, d_bad);
         tm.mark(1);
-        hipLaunchKernelGGL(k_cc_flatten, dim3(cc_blocks(NV)), dim3(kBlock), 0, s, parent, unv, flag);
+        hipLaunchKernelGGL(k_cc_flatten, dim3(blocks_for(NV)), dim3(kBlock), 0, s, parent, unv, flag);
         if (own_inclusive_scan(ar, s, (const unsigned*)flag, scan, NV)) return -1;
         tm.mark(2);
         int bad = 0; unsigned count = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+        if (flag_fetch(s, d_bad, &bad)) return -1;
         HIP_TRY(hipMemcpyAsync(&count, scan + (NV - 1), 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
-        if (bad) return fail(PCU_HIP_ERR_INVALID, "f must hold row indices of v: found a face index outside [0, %lld)", (long long)nv);
+        if (bad) return mesh_refusal(bad, nv);
         if (count == 0 || count > unv) return fail(PCU_HIP_ERR_RUNTIME, "internal: %u components of %lld vertices", count, (long long)nv);
-        char *d_cv = static_cast<char*>(out_cv), *d_cf = static_cast<char*>(out_cf), *d_nv = static_cast<char*>(out_nv), *d_nf = static_cast<char*>(out_nf);
-        if (!on_dev && (aalloc(ar, &d_cv, NV * kb) || aalloc(ar, &d_cf, NF * kb) || aalloc(ar, &d_nv, (size_t)count * kb) || aalloc(ar, &d_nf, (size_t)count * kb))) return -1;
+        char *const h_cv = static_cast<char*>(out_cv), *const h_cf = static_cast<char*>(out_cf), *const h_nv = static_cast<char*>(out_nv), *const h_nf = static_cast<char*>(out_nf);
+        char *d_cv = nullptr, *d_cf = nullptr, *d_nv = nullptr, *d_nf = nullptr;
+        if (out_room(ar, on_dev, h_cv, NV * kb, &d_cv) || out_room(ar, on_dev, h_cf, NF * kb, &d_cf) || out_room(ar, on_dev, h_nv, (size_t)count * kb, &d_nv) ||
+            out_room(ar, on_dev, h_nf, (size_t)count * kb, &d_nf)) return -1;
         tm.mark(3);
-        hipLaunchKernelGGL(k_cc_vertex_labels, dim3(cc_blocks(NV)), dim3(kBlock), 0, s, (const unsigned*)parent, (const unsigned*)scan, unv, f_kind, (void*)d_cv, cnt_v);
-        hipLaunchKernelGGL(k_cc_face_labels, dim3(cc_blocks(NF)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, unf, unv, (const unsigned*)parent, (const unsigned*)scan,
+        hipLaunchKernelGGL(k_cc_vertex_labels, dim3(blocks_for(NV)), dim3(kBlock), 0, s, (const unsigned*)parent, (const unsigned*)scan, unv, f_kind, (void*)d_cv, cnt_v);
+        hipLaunchKernelGGL(k_cc_face_labels, dim3(blocks_for(NF)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, unf, unv, (const unsigned*)parent, (const unsigned*)scan,
                            (void*)d_cf, cnt_f);
-        hipLaunchKernelGGL(k_cc_counts_out, dim3(cc_blocks(count)), dim3(kBlock), 0, s, (const unsigned*)cnt_v, (const unsigned*)cnt_f, count, f_kind, (void*)d_nv, (void*)d_nf);
+        hipLaunchKernelGGL(k_cc_counts_out, dim3(blocks_for(count)), dim3(kBlock), 0, s, (const unsigned*)cnt_v, (const unsigned*)cnt_f, count, f_kind, (void*)d_nv, (void*)d_nf);
         HIP_TRY(hipGetLastError());
         tm.mark(4);
-        if (!on_dev) {
-            HIP_TRY(hipMemcpyAsync(out_cv, d_cv, NV * kb, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_cf, d_cf, NF * kb, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_nv, d_nv, (size_t)count * kb, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_nf, d_nf, (size_t)count * kb, hipMemcpyDeviceToHost, s));
-        }
+        if (out_give(s, on_dev, h_cv, d_cv, NV * kb) || out_give(s, on_dev, h_cf, d_cf, NF * kb) || out_give(s, on_dev, h_nv, d_nv, (size_t)count * kb) ||
+            out_give(s, on_dev, h_nf, d_nf, (size_t)count * kb)) return -1;
         HIP_WAIT(s);
         *out_count = (int64_t)count;
         if (st) {
@@ -86,11 +82,11 @@ static int flood_fill_typed(pcu_hip_ctx* c, const void* grid, void* out, size_t 
     const size_t bytes = align_up(N * 4, 256) + (on_dev ? 0 : 2 * align_up(N * sizeof(V), 256)) + 8192;
     return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: runs and unions, 1-2: flatten, 2-3: the filled copy
-        const V* d_in = nullptr; V* d_out = static_cast<V*>(out);
-        if (stage_any(ar, static_cast<const V*>(grid), N, on_dev, s, &d_in) || (!on_dev && aalloc(ar, &d_out, N))) return -1;
+        const V* d_in = nullptr; V *const h_out = static_cast<V*>(out), *d_out = nullptr;
+        if (stage_any(ar, static_cast<const V*>(grid), N, on_dev, s, &d_in) || out_room(ar, on_dev, h_out, N, &d_out)) return -1;
         unsigned* parent = nullptr; unsigned long long* d_cnt = nullptr;
         if (aalloc(ar, &parent, N) || aalloc(ar, &d_cnt, 1)) return -1;
-        const unsigned n = (unsigned)N, nb = cc_blocks(N);
+        const unsigned n = (unsigned)N, nb = blocks_for(N);
         HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
         tm.mark(0);
         hipLaunchKernelGGL(k_fill_init<V>, dim3(nb), dim3(kBlock), 0, s, d_in, n, d, seed, parent);
@@ -103,7 +99,7 @@ static int flood_fill_typed(pcu_hip_ctx* c, const void* grid, void* out, size_t 
         tm.mark(3);
         unsigned long long filled = 0;
         HIP_TRY(hipMemcpyAsync(&filled, d_cnt, 8, hipMemcpyDeviceToHost, s));
-        if (!on_dev) HIP_TRY(hipMemcpyAsync(out, d_out, N * sizeof(V), hipMemcpyDeviceToHost, s));
+        if (out_give(s, on_dev, h_out, d_out, N)) return -1;
         HIP_WAIT(s);
         *out_filled = (int64_t)filled;
         if (st) {

@@ -35,7 +35,7 @@
 
 namespace pcu {
 
-constexpr int kDcBadFace = 1, kDcTwice = 2, kDcThreeFaces = 4;
+constexpr int kDcTwice = 4, kDcThreeFaces = 8;            // above kMeshBadVertex / kMeshBadFace in the call's flag word
 constexpr unsigned long long kDcNoKey = ~0ull;
 
 // Faces of any of the four integer types -> range-checked int32 triples and their rows. A face with an index outside [0, nv) or one that
@@ -45,13 +45,13 @@ __global__ __launch_bounds__(kBlock) void k_dc_faces_in(const void* __restrict__
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     int b = 0;
     if (i < nf) {
-        const unsigned long long x = cc_index_in(f, kind, 3 * (size_t)i), y = cc_index_in(f, kind, 3 * (size_t)i + 1), z = cc_index_in(f, kind, 3 * (size_t)i + 2);
-        if (x >= nv || y >= nv || z >= nv) b = kDcBadFace;
-        else if (x == y || y == z || x == z) b = kDcTwice;
-        cf[3 * (size_t)i] = b ? 0 : (int)x; cf[3 * (size_t)i + 1] = b ? 0 : (int)y; cf[3 * (size_t)i + 2] = b ? 0 : (int)z;
+        int id[3];
+        if (face_in(f, kind, (size_t)i, nv, id)) b = kMeshBadFace;
+        else if (id[0] == id[1] || id[1] == id[2] || id[0] == id[2]) { b = kDcTwice; id[0] = id[1] = id[2] = 0; }
+        cf[3 * (size_t)i] = id[0]; cf[3 * (size_t)i + 1] = id[1]; cf[3 * (size_t)i + 2] = id[2];
         rows[i] = i;
     }
-    const int any = (__ballot(b & kDcBadFace) ? kDcBadFace : 0) | (__ballot(b & kDcTwice) ? kDcTwice : 0);
+    const int any = (__ballot(b & kMeshBadFace) ? kMeshBadFace : 0) | (__ballot(b & kDcTwice) ? kDcTwice : 0);
     if (any && (threadIdx.x & 63) == 0) atomicOr(bad, any);
 }
 
@@ -231,8 +231,8 @@ __global__ __launch_bounds__(kBlock) void k_dc_faces_out(const int* __restrict__
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= m) return;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) cc_index_out(out_f, kind, 3 * (size_t)i + k, (unsigned)map[cf[3 * (size_t)i + k]]);
-    cc_index_out(out_rows, kind, i, rows[i]);
+    for (int k = 0; k < 3; ++k) index_out(out_f, kind, 3 * (size_t)i + k, (unsigned)map[cf[3 * (size_t)i + k]]);
+    index_out(out_rows, kind, i, rows[i]);
 }
 
 }  // namespace pcu

@@ -1,6 +1,6 @@
 // csrc/decimate_host.h -- host orchestration of decimate_triangle_mesh (kernels and contract: decimate.h). Included by pcu_hip.hip after the
-// operator frame and the parking functions, voxel_host.h (sort_bytes, scan_bytes, sort_keys, rank_flags, own_inclusive_scan), mesh_host.h
-// (mesh_validate, MeshGiven, int_kind_bytes), components_host.h (cc_blocks) and mesh_repair_host.h (mr_rank_bytes, mr_rank_referenced).
+// operator frame (stage_faces, flag_word, mesh_refusal) and the parking functions, voxel_host.h (sort_bytes, scan_bytes, sort_keys, rank_flags,
+// own_inclusive_scan), mesh_host.h (mesh_validate, MeshGiven) and mesh_repair_host.h (mr_rank_bytes, mr_rank_referenced).
 // Everything runs on the caller's stream out of the call's arena: the buffers that live through the call are taken first, and every round
 // starts its own at the same mark. The host waits once per round, for the flag word, the number of winners and the faces they remove.
 #pragma once
@@ -13,22 +13,19 @@ static size_t dc_round_bytes(size_t nv, size_t K) {
            mr_rank_bytes(K) + sort_bytes(K / 2 + 1) + 2 * align_up((K / 2 + 2) * 4, 256) + scan_bytes(K / 2 + 1) +                          // budget
            mr_rank_bytes(K / 6 + 1) + 16384;                                                                                               // faces
 }
-static size_t dc_parked_bytes(size_t nv, size_t nf, size_t elem, size_t kb) {
-    return align_up(nv * 3 * elem, 256) + align_up(nf * 3 * kb, 256) + align_up(nv * kb, 256) + align_up(nf * kb, 256);
-}
 
 // The sorted pairs of the m alive faces and their CSR. No wait.
 static int dc_structure(Arena& ar, hipStream_t s, const int* cf, unsigned m, unsigned nv, int hb, DcStructure& S) {
     const int K = (int)(6 * m);
     SortedRuns r; unsigned *pos = nullptr, *off = nullptr, *head_pos = nullptr; int* col = nullptr;
     if (aalloc(ar, &r.keys, (size_t)K) || aalloc(ar, &pos, (size_t)nv + 1) || aalloc(ar, &off, (size_t)nv + 1) || aalloc(ar, &head_pos, (size_t)K) || aalloc(ar, &col, (size_t)K)) return -1;
-    hipLaunchKernelGGL(k_ms_pairs, dim3(cc_blocks((size_t)K / 2)), dim3(kBlock), 0, s, cf, K / 2, hb, r.keys);
+    hipLaunchKernelGGL(k_ms_pairs, dim3(blocks_for((size_t)K / 2)), dim3(kBlock), 0, s, cf, K / 2, hb, r.keys);
     if (sort_keys(ar, s, r, K, 2 * hb)) return -1;
     const unsigned long long* keys = r.keys;
-    if (rank_flags(ar, s, r, K, [&](unsigned* flag) { hipLaunchKernelGGL(k_ms_pair_heads, dim3(cc_blocks((size_t)K)), dim3(kBlock), 0, s, keys, K, hb, flag); })) return -1;
-    hipLaunchKernelGGL(k_ms_row_starts, dim3(cc_blocks((size_t)nv + 1)), dim3(kBlock), 0, s, keys, K, hb, (int)nv, pos);
-    hipLaunchKernelGGL(k_ms_offsets, dim3(cc_blocks((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned*)pos, (const unsigned*)r.scan, (int)nv, off);
-    hipLaunchKernelGGL(k_ms_entries, dim3(cc_blocks((size_t)K)), dim3(kBlock), 0, s, keys, (const unsigned*)r.flag, (const unsigned*)r.scan, K, hb, head_pos, col);
+    if (rank_flags(ar, s, r, K, [&](unsigned* flag) { hipLaunchKernelGGL(k_ms_pair_heads, dim3(blocks_for((size_t)K)), dim3(kBlock), 0, s, keys, K, hb, flag); })) return -1;
+    hipLaunchKernelGGL(k_ms_row_starts, dim3(blocks_for((size_t)nv + 1)), dim3(kBlock), 0, s, keys, K, hb, (int)nv, pos);
+    hipLaunchKernelGGL(k_ms_offsets, dim3(blocks_for((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned*)pos, (const unsigned*)r.scan, (int)nv, off);
+    hipLaunchKernelGGL(k_ms_entries, dim3(blocks_for((size_t)K)), dim3(kBlock), 0, s, keys, (const unsigned*)r.flag, (const unsigned*)r.scan, K, hb, head_pos, col);
     HIP_TRY(hipGetLastError());
     S = DcStructure{keys, r.ids, off, head_pos, col, r.scan + (K - 1), cf, (unsigned)K, hb};
     return 0;
@@ -36,7 +33,7 @@ static int dc_structure(Arena& ar, hipStream_t s, const int* cf, unsigned m, uns
 
 // hi becomes lo in the m alive faces; the survivors flagged and ranked. No wait.
 static int dc_rank_alive(Arena& ar, hipStream_t s, SortedRuns& r, int* cf, unsigned m, const int* to) {
-    return rank_flags(ar, s, r, (int)m, [&](unsigned* keep) { hipLaunchKernelGGL(k_dc_faces_step, dim3(cc_blocks((size_t)m)), dim3(kBlock), 0, s, cf, m, to, keep); });
+    return rank_flags(ar, s, r, (int)m, [&](unsigned* keep) { hipLaunchKernelGGL(k_dc_faces_step, dim3(blocks_for((size_t)m)), dim3(kBlock), 0, s, cf, m, to, keep); });
 }
 
 // The budget where it binds: of the nw winners flagged in `win`, those stay that the contract takes. No wait.
@@ -44,11 +41,11 @@ static int dc_budget(Arena& ar, hipStream_t s, const DcStructure& S, const unsig
     SortedRuns r; unsigned *scan = nullptr, *wfaces = nullptr, *wscan = nullptr;
     if (aalloc(ar, &scan, (size_t)S.K + 1) || aalloc(ar, &r.keys, (size_t)nw) || aalloc(ar, &wfaces, (size_t)nw) || aalloc(ar, &wscan, (size_t)nw + 1)) return -1;
     if (own_inclusive_scan(ar, s, (const unsigned*)win, scan, (size_t)S.K)) return -1;
-    hipLaunchKernelGGL(k_dc_winner_keys, dim3(cc_blocks((size_t)S.K)), dim3(kBlock), 0, s, (const unsigned*)win, (const unsigned*)scan, S.K, ekey, r.keys);
+    hipLaunchKernelGGL(k_dc_winner_keys, dim3(blocks_for((size_t)S.K)), dim3(kBlock), 0, s, (const unsigned*)win, (const unsigned*)scan, S.K, ekey, r.keys);
     if (sort_keys(ar, s, r, (int)nw, 64)) return -1;
-    hipLaunchKernelGGL(k_dc_winner_faces, dim3(cc_blocks((size_t)nw)), dim3(kBlock), 0, s, S, (const unsigned long long*)r.keys, nw, wfaces);
+    hipLaunchKernelGGL(k_dc_winner_faces, dim3(blocks_for((size_t)nw)), dim3(kBlock), 0, s, S, (const unsigned long long*)r.keys, nw, wfaces);
     if (own_inclusive_scan(ar, s, (const unsigned*)wfaces, wscan, (size_t)nw)) return -1;
-    hipLaunchKernelGGL(k_dc_budget, dim3(cc_blocks((size_t)nw)), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, (const unsigned*)wfaces, (const unsigned*)wscan, nw, need, win, counts);
+    hipLaunchKernelGGL(k_dc_budget, dim3(blocks_for((size_t)nw)), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, (const unsigned*)wfaces, (const unsigned*)wscan, nw, need, win, counts);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -72,18 +69,17 @@ static int decimate_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64_t max_face
     return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: a round's structure, 1-2: cost, validity, claims and wins, 3-4: budget, apply and compaction, 5-6: the call
         const T* dv = nullptr; const char* d_f = nullptr;
-        if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(m.f), NF * 3 * kb, on_dev, s, &d_f)) return -1;
+        if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || stage_faces(ar, m.f, NF, m.f_kind, on_dev, s, &d_f)) return -1;
         T* P = nullptr; int *cf = nullptr, *cf_alt = nullptr, *to = nullptr, *d_bad = nullptr; unsigned *rows = nullptr, *rows_alt = nullptr, *counts = nullptr;
         unsigned long long* owner = nullptr;
+        tm.mark(5);
         if (aalloc(ar, &P, NV * 3) || aalloc(ar, &cf, NF * 3) || aalloc(ar, &cf_alt, NF * 3) || aalloc(ar, &rows, NF) || aalloc(ar, &rows_alt, NF) ||
-            aalloc(ar, &owner, NV) || aalloc(ar, &to, NV) || aalloc(ar, &d_bad, 1 + kDcCounts)) return -1;
+            aalloc(ar, &owner, NV) || aalloc(ar, &to, NV) || flag_word(ar, s, &d_bad, 1 + kDcCounts)) return -1;
         counts = reinterpret_cast<unsigned*>(d_bad + 1);
         const unsigned unv = (unsigned)m.nv, unf = (unsigned)m.nf;
         const int hb = std::max(bits_of((unsigned long long)(m.nv - 1)), 1);
-        tm.mark(5);
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
         HIP_TRY(hipMemcpyAsync(P, dv, NV * 3 * sizeof(T), hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_dc_faces_in, dim3(cc_blocks(NF)), dim3(kBlock), 0, s, (const void*)d_f, m.f_kind, unf, unv, cf, rows, d_bad);
+        hipLaunchKernelGGL(k_dc_faces_in, dim3(blocks_for(NF)), dim3(kBlock), 0, s, (const void*)d_f, m.f_kind, unf, unv, cf, rows, d_bad);
         const size_t mark = ar.a->off;
         unsigned alive = unf;
         int64_t rounds = 0, collapses = 0;
@@ -97,11 +93,11 @@ static int decimate_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64_t max_face
             if (dc_structure(ar, s, cf, alive, unv, hb, S)) return -1;
             tm.mark(1);
             if (first) {                        // what the call refuses whatever max_faces is
-                hipLaunchKernelGGL(k_dc_check_edges, dim3(cc_blocks((size_t)S.K)), dim3(kBlock), 0, s, S.head_pos, S.ne_ptr, S.K, d_bad);
+                hipLaunchKernelGGL(k_dc_check_edges, dim3(blocks_for((size_t)S.K)), dim3(kBlock), 0, s, S.head_pos, S.ne_ptr, S.K, d_bad);
                 int bad = 0;
-                HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+                if (flag_fetch(s, d_bad, &bad)) return -1;
                 HIP_WAIT(s);
-                if (bad & kDcBadFace) return mr_bad_face(m.nv);
+                if (int rc = mesh_refusal(bad, m.nv)) return rc;
                 if (bad & kDcTwice) return fail(PCU_HIP_ERR_INVALID, "f must not hold a face that lists a vertex twice");
                 if (bad & kDcThreeFaces) return fail(PCU_HIP_ERR_INVALID, "decimate_triangle_mesh_doc produced an empty mesh. This can happen if the input is non-manifold.");
                 if (alive <= (unsigned)max_faces) break;
@@ -110,8 +106,8 @@ static int decimate_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64_t max_face
             if (aalloc(ar, &ekey, (size_t)S.K) || aalloc(ar, &win, (size_t)S.K)) return -1;
             HIP_TRY(hipMemsetAsync(owner, 0xff, NV * 8, s));
             HIP_TRY(hipMemsetAsync(counts, 0, kDcCounts * sizeof(unsigned), s));
-            hipLaunchKernelGGL(k_dc_claim<T>, dim3(cc_blocks((size_t)S.K)), dim3(kBlock), 0, s, S, (const T*)P, ekey, owner);
-            hipLaunchKernelGGL(k_dc_wins, dim3(cc_blocks((size_t)S.K)), dim3(kBlock), 0, s, S, (const unsigned long long*)ekey, (const unsigned long long*)owner, win, counts);
+            hipLaunchKernelGGL(k_dc_claim<T>, dim3(blocks_for((size_t)S.K)), dim3(kBlock), 0, s, S, (const T*)P, ekey, owner);
+            hipLaunchKernelGGL(k_dc_wins, dim3(blocks_for((size_t)S.K)), dim3(kBlock), 0, s, S, (const unsigned long long*)ekey, (const unsigned long long*)owner, win, counts);
             HIP_TRY(hipGetLastError());
             tm.mark(2);
             unsigned got[kDcCounts] = {0, 0, 0, 0};
@@ -127,10 +123,10 @@ static int decimate_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64_t max_face
             const bool binds = faces > need;
             if (binds && dc_budget(ar, s, S, ekey, win, nw, need, counts)) return -1;
             HIP_TRY(hipMemsetAsync(to, 0xff, NV * 4, s));
-            hipLaunchKernelGGL(k_dc_apply<T>, dim3(cc_blocks((size_t)S.K)), dim3(kBlock), 0, s, S, (const unsigned*)win, P, to);
+            hipLaunchKernelGGL(k_dc_apply<T>, dim3(blocks_for((size_t)S.K)), dim3(kBlock), 0, s, S, (const unsigned*)win, P, to);
             SortedRuns fs;
             if (dc_rank_alive(ar, s, fs, cf, alive, to)) return -1;
-            hipLaunchKernelGGL(k_dc_compact, dim3(cc_blocks((size_t)alive)), dim3(kBlock), 0, s, (const int*)cf, (const unsigned*)rows, alive, (const unsigned*)fs.flag,
+            hipLaunchKernelGGL(k_dc_compact, dim3(blocks_for((size_t)alive)), dim3(kBlock), 0, s, (const int*)cf, (const unsigned*)rows, alive, (const unsigned*)fs.flag,
                                (const unsigned*)fs.scan, cf_alt, rows_alt);
             HIP_TRY(hipGetLastError());
             tm.mark(4);
@@ -152,24 +148,21 @@ static int decimate_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64_t max_face
         SortedRuns vs; int* map = nullptr;
         if (aalloc(ar, &map, NV)) return -1;
         if (mr_rank_referenced(ar, s, vs, cf, 0, alive, unv, d_bad)) return -1;
-        hipLaunchKernelGGL(k_mr_map, dim3(cc_blocks(NV)), dim3(kBlock), 0, s, (const unsigned*)vs.flag, (const unsigned*)vs.scan, unv, map);
+        hipLaunchKernelGGL(k_mr_map, dim3(blocks_for(NV)), dim3(kBlock), 0, s, (const unsigned*)vs.flag, (const unsigned*)vs.scan, unv, map);
         unsigned kept_v = 0;
         HIP_TRY(hipMemcpyAsync(&kept_v, vs.scan + (NV - 1), 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         if (kept_v == 0 || kept_v > unv || alive == 0) return fail(PCU_HIP_ERR_RUNTIME, "internal: %u of %lld vertices listed by %u faces", kept_v, (long long)m.nv, alive);
-        if (aux_reserve(c, dc_parked_bytes(kept_v, alive, sizeof(T), kb))) return -1;
-        char* seg = c->aux;
-        T* p_v = reinterpret_cast<T*>(seg); seg += align_up((size_t)kept_v * 3 * sizeof(T), 256);
-        char* p_f = seg; seg += align_up((size_t)alive * 3 * kb, 256);
-        char* p_cv = seg; seg += align_up((size_t)kept_v * kb, 256);
-        char* p_cf = seg;
-        hipLaunchKernelGGL(k_mr_rows<T>, dim3(cc_blocks(NV)), dim3(kBlock), 0, s, (const T*)P, (const int*)map, unv, p_v, m.f_kind, (void*)p_cv, (void*)nullptr);
-        hipLaunchKernelGGL(k_dc_faces_out, dim3(cc_blocks((size_t)alive)), dim3(kBlock), 0, s, (const int*)cf, (const unsigned*)rows, alive, (const int*)map, m.f_kind, (void*)p_f, (void*)p_cf);
+        char* seg[kParkSegs];       // v, f, corr_v, corr_f
+        if (park_reserve(c, {(size_t)kept_v * 3 * sizeof(T), (size_t)alive * 3 * kb, (size_t)kept_v * kb, (size_t)alive * kb}, seg)) return -1;
+        hipLaunchKernelGGL(k_mr_rows<T>, dim3(blocks_for(NV)), dim3(kBlock), 0, s, (const T*)P, (const int*)map, unv, reinterpret_cast<T*>(seg[0]), m.f_kind, (void*)seg[2],
+                           (void*)nullptr);
+        hipLaunchKernelGGL(k_dc_faces_out, dim3(blocks_for((size_t)alive)), dim3(kBlock), 0, s, (const int*)cf, (const unsigned*)rows, alive, (const int*)map, m.f_kind,
+                           (void*)seg[1], (void*)seg[3]);
         HIP_TRY(hipGetLastError());
         tm.mark(6);
         HIP_WAIT(s);
         if (apply_untimed) ms_apply += tm.span(3, 4);
-        c->parked.bytes0 = sizeof(T); c->parked.bytes1 = kb;
         park_commit(c, Parked::Decimated, (int64_t)kept_v, (int64_t)alive);
         *out_nv = (int64_t)kept_v; *out_nf = (int64_t)alive;
         if (st) {
@@ -183,18 +176,6 @@ static int decimate_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64_t max_face
 // out_corr_f (nf) in f's.
 static int decimate_take_impl(pcu_hip_ctx* c, int64_t nv, int64_t nf, void* out_v, void* out_f, void* out_corr_v, void* out_corr_f, unsigned flags, void* stream) {
     if (!c || !out_v || !out_f || !out_corr_v || !out_corr_f) return fail(PCU_HIP_ERR_INVALID, "null context / out_v / out_f / out_corr_v / out_corr_f");
-    const ParkedResult& p = c->parked;
-    if (p.kind != Parked::Decimated || nv != p.n0 || nf != p.n1)
-        return fail(PCU_HIP_ERR_INVALID, "pcu_hip_decimate_triangle_mesh_take: this context holds no decimated mesh of %lld vertices and %lld faces", (long long)nv, (long long)nf);
-    hipStream_t s = pick_stream(c, flags, stream);
-    const hipMemcpyKind dir = (flags & PCU_HIP_PTRS_ON_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const size_t elem = p.bytes0, kb = p.bytes1, NV = (size_t)nv, NF = (size_t)nf;          // (of this kind: the sizes of the two scalar types)
-    const char* seg = c->aux;
-    HIP_TRY(hipMemcpyAsync(out_v, seg, NV * 3 * elem, dir, s)); seg += align_up(NV * 3 * elem, 256);
-    HIP_TRY(hipMemcpyAsync(out_f, seg, NF * 3 * kb, dir, s)); seg += align_up(NF * 3 * kb, 256);
-    HIP_TRY(hipMemcpyAsync(out_corr_v, seg, NV * kb, dir, s)); seg += align_up(NV * kb, 256);
-    HIP_TRY(hipMemcpyAsync(out_corr_f, seg, NF * kb, dir, s));
-    HIP_WAIT(s);
-    c->parked = ParkedResult();
-    return 0;
+    return park_take(c, Parked::Decimated, nv, nf, {out_v, out_f, out_corr_v, out_corr_f}, flags, stream,
+                     "pcu_hip_decimate_triangle_mesh_take: this context holds no decimated mesh of %lld vertices and %lld faces");
 }

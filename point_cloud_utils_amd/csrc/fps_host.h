@@ -63,8 +63,8 @@ static int fps_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const pcu_hip_index
             for (auto& e : c->fps_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
         if (ds.stage(ar, s)) return -1;
-        long long* d_idx = reinterpret_cast<long long*>(out_idx); T* d_d = out_d;
-        if (!on_dev) { if (aalloc(ar, &d_idx, M) || (out_d && aalloc(ar, &d_d, M))) return -1; }
+        long long *const h_idx = reinterpret_cast<long long*>(out_idx), *d_idx = nullptr; T* d_d = nullptr;
+        if (out_room(ar, on_dev, h_idx, M, &d_idx) || (out_d && out_room(ar, on_dev, out_d, M, &d_d))) return -1;
         int* const d_bad = reinterpret_cast<int*>(c->fps_dev + kFpsDevBad);
         unsigned long long* const d_cnt = reinterpret_cast<unsigned long long*>(c->fps_dev + kFpsDevCounters);
         const int squared = (flags & PCU_HIP_SQUARED) ? 1 : 0;
@@ -75,7 +75,7 @@ static int fps_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const pcu_hip_index
             constexpr int P = kFpsBlockRows / kFpsBlockThreads / (int)(sizeof(T) / 4);       // points per lane: 64 registers of (x, y, z, mind) in either type
             hipLaunchKernelGGL((k_fps_block<T, P>), dim3(1), dim3(kFpsBlockThreads), 0, s, ds.rows, (int)n, (int)m, (int)start, d_idx, d_d, squared, d_bad);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+            if (flag_fetch(s, d_bad, &bad)) return -1;
         } else {
             GridIndex<T> gi;
             if (int rc = ds.grid(ar, s, gi, kFpsOcc, IndexFor::Atomic)) return rc;
@@ -119,10 +119,7 @@ static int fps_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const pcu_hip_index
         tm.mark(2);
         unsigned long long cnt[2] = {0, 0};
         if (!one_block && out_counters) HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
-        if (!on_dev) {
-            HIP_TRY(hipMemcpyAsync(out_idx, d_idx, M * 8, hipMemcpyDeviceToHost, s));
-            if (out_d) HIP_TRY(hipMemcpyAsync(out_d, d_d, M * sizeof(T), hipMemcpyDeviceToHost, s));
-        }
+        if (out_give(s, on_dev, h_idx, d_idx, M) || out_give(s, on_dev, out_d, d_d, M)) return -1;
         HIP_WAIT(s);
         if (bad) return fail(PCU_HIP_ERR_INVALID, "points must not contain NaN or infinite coordinates");
         if (out_counters) { out_counters[0] = (int64_t)cnt[0]; out_counters[1] = (int64_t)cnt[1]; }

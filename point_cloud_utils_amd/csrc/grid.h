@@ -24,6 +24,7 @@
 namespace pcu {
 
 constexpr int kBlock = 256;
+inline unsigned blocks_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }      // blocks of kBlock threads, one thread per item
 
 template <typename T>
 __device__ __forceinline__ T wave_min(T v) {

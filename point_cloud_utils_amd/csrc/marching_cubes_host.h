@@ -1,6 +1,6 @@
 // csrc/marching_cubes_host.h -- host orchestration of marching_cubes_sparse_voxel_grid and sparse_voxel_grid_to_hex_mesh (kernels and contract:
 // marching_cubes.h). Included by pcu_hip.hip after the operator frame and the parking functions, voxel_host.h (sort_keys, rank_runs, the
-// scan), mesh_host.h (int_kind_check, int_kind_bytes) and voxelize_host.h (vx_grid_check, kVxMaxRows).
+// scan), mesh_host.h (int_kind_check) and voxelize_host.h (vx_grid_check, kVxMaxRows).
 #pragma once
 
 // Both operators learn the size of their results late, so the results are parked for the matching _take call, as a voxelization's rows are
@@ -30,13 +30,12 @@ static int marching_cubes_impl(pcu_hip_ctx* c, const T* scalars, const T* coords
         const T *S = nullptr, *P = nullptr; const char* d_cubes = nullptr;
         tm.mark(0);
         if (stage_any(ar, scalars, N, on_dev, s, &S) || stage_any(ar, coords, N * 3, on_dev, s, &P) ||
-            stage_any(ar, static_cast<const char*>(cubes), M * 8 * ib, on_dev, s, &d_cubes)) return -1;
+            stage_ints(ar, cubes, M * 8, kind, on_dev, s, &d_cubes)) return -1;
         int *cidx = nullptr, *d_bad = nullptr; unsigned char* mask = nullptr; unsigned long long *cnt = nullptr, *C = nullptr;
-        if (aalloc(ar, &cidx, M * 8) || aalloc(ar, &mask, M) || aalloc(ar, &cnt, M) || aalloc(ar, &C, M) || aalloc(ar, &d_bad, 1)) return -1;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3((unsigned)((N * 3 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, P, (long long)N * 3, d_bad, kMeshBadVertex);
-        hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, S, (long long)N, d_bad, kMeshBadVertex);
-        hipLaunchKernelGGL(k_mc_classify<T>, dim3((unsigned)((M * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, (const void*)d_cubes, kind, (long long)m, S, (int)n, iso,
+        if (aalloc(ar, &cidx, M * 8) || aalloc(ar, &mask, M) || aalloc(ar, &cnt, M) || aalloc(ar, &C, M) || flag_word(ar, s, &d_bad)) return -1;
+        hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3(blocks_for(N * 3)), dim3(kBlock), 0, s, P, (long long)N * 3, d_bad, kMeshBadVertex);
+        hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3(blocks_for((size_t)N)), dim3(kBlock), 0, s, S, (long long)N, d_bad, kMeshBadVertex);
+        hipLaunchKernelGGL(k_mc_classify<T>, dim3(blocks_for(M * 8)), dim3(kBlock), 0, s, (const void*)d_cubes, kind, (long long)m, S, (int)n, iso,
                            cidx, mask, cnt, d_bad);
         if (own_inclusive_scan(ar, s, (const unsigned long long*)cnt, C, M)) return -1;
         tm.mark(1);
@@ -50,11 +49,11 @@ static int marching_cubes_impl(pcu_hip_ctx* c, const T* scalars, const T* coords
         if (3 * F > (unsigned long long)kVxMaxRows)
             return fail(PCU_HIP_ERR_INVALID, "marching_cubes_sparse_voxel_grid: more than (2^31-16)/3 triangles are not supported");
         // keys, sort, unique
-        const int K = (int)(3 * F), hb = bits_of((unsigned long long)(n - 1)), nbk = (K + kBlock - 1) / kBlock;
+        const int K = (int)(3 * F), hb = bits_of((unsigned long long)(n - 1)), nbk = blocks_for((size_t)K);
         SortedRuns r;
         if (aalloc(ar, &r.keys, (size_t)K)) return -1;
         tm.mark(2);
-        hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)((M + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, (const int*)cidx, (const unsigned char*)mask,
+        hipLaunchKernelGGL(k_mc_emit, dim3(blocks_for((size_t)M)), dim3(kBlock), 0, s, (const int*)cidx, (const unsigned char*)mask,
                            (const unsigned long long*)C, (long long)m, hb, r.keys);
         HIP_TRY(hipGetLastError());
         tm.mark(3);
@@ -66,10 +65,10 @@ static int marching_cubes_impl(pcu_hip_ctx* c, const T* scalars, const T* coords
         HIP_TRY(hipMemcpyAsync(&V, r.scan + (K - 1), 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         // vertices and faces, straight into the parked segments
-        char *d_v = nullptr, *d_f = nullptr;
-        if (park_reserve(c, (size_t)V * 3 * sizeof(T), (size_t)K * ib, &d_v, &d_f)) return -1;
+        char* seg[kParkSegs];
+        if (park_reserve(c, {(size_t)V * 3 * sizeof(T), (size_t)K * ib}, seg)) return -1;
         hipLaunchKernelGGL(k_mc_write<T>, dim3(nbk), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, (const unsigned*)r.ids, (const unsigned*)r.flag,
-                           (const unsigned*)r.scan, K, hb, S, P, iso, reinterpret_cast<T*>(d_v), (void*)d_f, kind);
+                           (const unsigned*)r.scan, K, hb, S, P, iso, reinterpret_cast<T*>(seg[0]), (void*)seg[1], kind);
         HIP_TRY(hipGetLastError());
         tm.mark(6);
         HIP_WAIT(s);
@@ -85,7 +84,7 @@ static int marching_cubes_impl(pcu_hip_ctx* c, const T* scalars, const T* coords
 // The result of this context's last pcu_hip_marching_cubes_*: out_v (nv, 3) of its scalar type, out_f (nf, 3) of its index type. Once.
 static int marching_cubes_take_impl(pcu_hip_ctx* c, int64_t nv, int64_t nf, void* out_v, void* out_f, unsigned flags, void* stream) {
     if (!c || !out_v || !out_f) return fail(PCU_HIP_ERR_INVALID, "null context / out_v / out_f");
-    return park_take(c, Parked::Surface, nv, nf, out_v, out_f, flags, stream,
+    return park_take(c, Parked::Surface, nv, nf, {out_v, out_f}, flags, stream,
                      "pcu_hip_marching_cubes_take: this context holds no surface of %lld vertices and %lld faces");
 }
 
@@ -108,11 +107,10 @@ static int hex_mesh_impl(pcu_hip_ctx* c, const void* ijk, int64_t k, int kind, c
         auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: codes, 1-2: sort, 2-3: unique, 3-4: vertices and cubes
         const char* d_in = nullptr;
         tm.mark(0);
-        if (stage_any(ar, static_cast<const char*>(ijk), (size_t)k * 3 * int_kind_bytes(kind), on_dev, s, &d_in)) return -1;
+        if (stage_faces(ar, ijk, (size_t)k, kind, on_dev, s, &d_in)) return -1;
         SortedRuns r; int* d_bad = nullptr;
-        if (aalloc(ar, &r.keys, K) || aalloc(ar, &d_bad, 1)) return -1;
-        const int KK = (int)K, nb = (KK + kBlock - 1) / kBlock;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+        if (aalloc(ar, &r.keys, K) || flag_word(ar, s, &d_bad)) return -1;
+        const int KK = (int)K, nb = blocks_for((size_t)KK);
         hipLaunchKernelGGL(k_hx_codes, dim3(nb), dim3(kBlock), 0, s, (const void*)d_in, kind, (long long)K, r.keys, d_bad);
         tm.mark(1);
         if (sort_keys(ar, s, r, KK, 63)) return -1;
@@ -123,12 +121,12 @@ static int hex_mesh_impl(pcu_hip_ctx* c, const void* ijk, int64_t k, int kind, c
         if (read_flag_and_last(s, d_bad, r.scan, K, &bad, &V)) return -1;
         HIP_WAIT(s);
         if (bad) return fail(PCU_HIP_ERR_INVALID, "Invalid vertex leads to an overflow integer. Perhaps grid_size is too small.");
-        char *d_v = nullptr, *d_c = nullptr;
-        if (park_reserve(c, (size_t)V * 3 * (out_f64 ? 8 : 4), K * 8, &d_v, &d_c)) return -1;
+        char* seg[kParkSegs];
+        if (park_reserve(c, {(size_t)V * 3 * (out_f64 ? 8 : 4), K * 8}, seg)) return -1;
         if (out_f64) hipLaunchKernelGGL(k_hx_write<double>, dim3(nb), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, (const unsigned*)r.ids, (const unsigned*)r.flag,
-                                        (const unsigned*)r.scan, KK, g, reinterpret_cast<double*>(d_v), reinterpret_cast<long long*>(d_c));
+                                        (const unsigned*)r.scan, KK, g, reinterpret_cast<double*>(seg[0]), reinterpret_cast<long long*>(seg[1]));
         else hipLaunchKernelGGL(k_hx_write<float>, dim3(nb), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, (const unsigned*)r.ids, (const unsigned*)r.flag,
-                                (const unsigned*)r.scan, KK, g, reinterpret_cast<float*>(d_v), reinterpret_cast<long long*>(d_c));
+                                (const unsigned*)r.scan, KK, g, reinterpret_cast<float*>(seg[0]), reinterpret_cast<long long*>(seg[1]));
         HIP_TRY(hipGetLastError());
         tm.mark(4);
         HIP_WAIT(s);
@@ -144,6 +142,6 @@ static int hex_mesh_impl(pcu_hip_ctx* c, const void* ijk, int64_t k, int kind, c
 // The result of this context's last pcu_hip_sparse_voxel_grid_to_hex_mesh: out_v (nv, 3) float or double, out_cubes (k, 8) int64. Once.
 static int hex_mesh_take_impl(pcu_hip_ctx* c, int64_t nv, int64_t k, void* out_v, int64_t* out_cubes, unsigned flags, void* stream) {
     if (!c || !out_v || !out_cubes) return fail(PCU_HIP_ERR_INVALID, "null context / out_v / out_cubes");
-    return park_take(c, Parked::HexMesh, nv, k, out_v, out_cubes, flags, stream,
+    return park_take(c, Parked::HexMesh, nv, k, {out_v, out_cubes}, flags, stream,
                      "pcu_hip_sparse_voxel_grid_to_hex_mesh_take: this context holds no hex mesh of %lld vertices and %lld cubes");
 }

@@ -37,7 +37,6 @@ namespace pcu {
 constexpr int kMeshLeaf = 4;            // faces per leaf
 constexpr int kMeshStack = 26;          // >= tree depth + 1 (P <= 2^25 leaves: 2^27 faces)
 constexpr int kMeshBlock = 256;
-constexpr int kMeshBadVertex = 1, kMeshBadFace = 2;
 
 template <typename T>
 struct MeshHead {
@@ -71,7 +70,7 @@ __global__ void k_mesh_head_init(MeshHead<T>* h) {
     if (threadIdx.x < 3) { h->elo[threadIdx.x] = ~(E)0; h->ehi[threadIdx.x] = (E)0; }
     if (threadIdx.x == 0) h->bad = 0;
 }
-// Face indices of any of the four integer types (kind 0 int32, 1 int64, 2 uint32, 3 uint64) -> the index's own int32 triples, range-checked;
+// Face indices of any of the four integer types (index_kinds.h) -> the index's own int32 triples, range-checked;
 // and the bounding box of the vertices that faces refer to.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_mesh_faces(const void* __restrict__ f, int kind, int nf, int nv, const T* __restrict__ v,
@@ -82,17 +81,7 @@ __global__ __launch_bounds__(kBlock) void k_mesh_faces(const void* __restrict__ 
     bool bad = false;
     if (i < nf) {
         int id[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            unsigned long long u;               // (a negative index becomes a huge unsigned one)
-            if (kind == 0) u = (unsigned long long)(long long)static_cast<const int*>(f)[3 * (size_t)i + j];
-            else if (kind == 1) u = (unsigned long long)static_cast<const long long*>(f)[3 * (size_t)i + j];
-            else if (kind == 2) u = (unsigned long long)static_cast<const unsigned*>(f)[3 * (size_t)i + j];
-            else u = static_cast<const unsigned long long*>(f)[3 * (size_t)i + j];
-            bad |= u >= (unsigned long long)nv;
-            id[j] = (int)u;
-        }
-        if (bad) id[0] = id[1] = id[2] = 0;
+        bad = face_in(f, kind, (size_t)i, (unsigned)nv, id);
         fidx[3 * (size_t)i] = id[0]; fidx[3 * (size_t)i + 1] = id[1]; fidx[3 * (size_t)i + 2] = id[2];
         if (!bad) {
 #pragma unroll

@@ -1,7 +1,7 @@
 // csrc/mesh_host.h -- host orchestration of closest_points_on_mesh, ray_mesh_intersection (kernels, contracts and index layout: mesh.h),
 // triangle_soup_fast_winding_number and signed_distance_to_mesh (mesh_winding.h), and the frames of every index that is an element tree
 // (TreeIndex, tree_index_create, tree_index_check, tree_call), which pc_winding_host.h and surfel_host.h use too. Included by pcu_hip.hip
-// after the operator frame (op_run, stage_any, index_out_begin) and voxel_host.h (sort_bytes, the radix sort).
+// after the operator frame (op_run, stage_any, stage_faces, out_room / out_give, the flag word's helpers, index_out_begin) and voxel_host.h (sort_bytes, the radix sort).
 #pragma once
 
 // An element tree kept on the GPU as a search index: one block owned by the object, not by a call's arena. The three handle types of the ABI
@@ -36,8 +36,6 @@ static size_t mesh_index_bytes(int64_t nf, bool moments) {
     if (moments) b += align_up(2 * P * 4 * sizeof(T), 256) + align_up(2 * P * 30 * sizeof(T), 256);
     return b;
 }
-// the integer types of faces, cubes and grid coordinates: PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64
-static int int_kind_bytes(int kind) { return (kind == 0 || kind == 2) ? 4 : 8; }
 static int int_kind_check(int kind) {
     return (kind < 0 || kind > 3) ? fail(PCU_HIP_ERR_INVALID, "kind must be one of PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64") : 0;
 }
@@ -73,36 +71,35 @@ template <typename T>
 static int mesh_build(Arena& ari, Arena& ar, hipStream_t s, const T* v, int64_t nv, const void* f, int64_t nf, int f_kind, bool on_dev, bool moments,
                       MeshIdx<T>& M) {
     const T* dv = nullptr; const char* df = nullptr;
-    if (stage_in(ar, v, nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(f), (size_t)nf * 3 * int_kind_bytes(f_kind), on_dev, s, &df)) return -1;
+    if (stage_in(ar, v, nv, on_dev, s, &dv) || stage_faces(ar, f, (size_t)nf, f_kind, on_dev, s, &df)) return -1;
     M.nf = (int)nf; M.P = leaves_pow2(nf, kMeshLeaf);
     int* fidx = nullptr;
     if (aalloc(ari, &M.head, 1) || aalloc(ari, &M.tri, (size_t)nf * 9) || aalloc(ari, &M.face, (size_t)nf) || aalloc(ari, &M.box, (size_t)M.P * 12) ||
         aalloc(ar, &fidx, (size_t)nf * 3)) return -1;
-    const int nbf = (int)((nf + kBlock - 1) / kBlock);
+    const unsigned nbf = blocks_for((size_t)nf);
     hipLaunchKernelGGL(k_mesh_head_init<T>, dim3(1), dim3(64), 0, s, M.head);
-    int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
-    hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3((unsigned)((nv * 3 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, dv, (long long)nv * 3, d_bad, kMeshBadVertex);
+    int* d_bad = mesh_head_flag(M.head);
+    hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3(blocks_for((size_t)nv * 3)), dim3(kBlock), 0, s, dv, (long long)nv * 3, d_bad, kMeshBadVertex);
     hipLaunchKernelGGL(k_mesh_faces<T>, dim3(nbf), dim3(kBlock), 0, s, (const void*)df, f_kind, (int)nf, (int)nv, dv, fidx, M.head);
     hipLaunchKernelGGL(k_mesh_frame<T>, dim3(1), dim3(64), 0, s, M.head);
     HIP_TRY(hipGetLastError());
     int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (flag_fetch(s, d_bad, &bad)) return -1;
     HIP_WAIT(s);
-    if (bad & kMeshBadVertex) return fail(PCU_HIP_ERR_INVALID, "v must not contain NaN or infinite coordinates");
-    if (bad & kMeshBadFace) return fail(PCU_HIP_ERR_INVALID, "f must hold row indices of v: found a face index outside [0, %lld)", (long long)nv);
+    if (bad) return mesh_refusal(bad, nv);
     unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
     if (aalloc(ar, &ka, (size_t)nf) || aalloc(ar, &kb, (size_t)nf) || aalloc(ar, &ia, (size_t)nf) || aalloc(ar, &ib, (size_t)nf)) return -1;
     hipLaunchKernelGGL(k_mesh_codes<T>, dim3(nbf), dim3(kBlock), 0, s, dv, (const int*)fidx, (int)nf, (const MeshHead<T>*)M.head, ka);
     if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)nf, 63)) return -1;
     hipLaunchKernelGGL(k_mesh_gather<T>, dim3(nbf), dim3(kBlock), 0, s, dv, (const int*)fidx, (const unsigned*)ia, (int)nf, M.tri, M.face);
-    hipLaunchKernelGGL(k_mesh_leaves<T>, dim3((M.P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const T*)M.tri, (int)nf, M.P, (const MeshHead<T>*)M.head, M.box);
-    for (int m = M.P / 2; m >= 1; m /= 2) hipLaunchKernelGGL(k_mesh_refit<T>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, M.box, m);
+    hipLaunchKernelGGL(k_mesh_leaves<T>, dim3(blocks_for((size_t)M.P)), dim3(kBlock), 0, s, (const T*)M.tri, (int)nf, M.P, (const MeshHead<T>*)M.head, M.box);
+    for (int m = M.P / 2; m >= 1; m /= 2) hipLaunchKernelGGL(k_mesh_refit<T>, dim3(blocks_for((size_t)m)), dim3(kBlock), 0, s, M.box, m);
     if (moments) {
         double* area = nullptr;
         if (aalloc(ari, &M.ctr, (size_t)M.P * 8) || aalloc(ari, &M.mom, (size_t)M.P * 60) || aalloc(ar, &area, (size_t)M.P * 2)) return -1;
-        hipLaunchKernelGGL(k_mesh_mleaves<T>, dim3((M.P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const T*)M.tri, (int)nf, M.P, (const T*)M.box, M.ctr, M.mom, area);
+        hipLaunchKernelGGL(k_mesh_mleaves<T>, dim3(blocks_for((size_t)M.P)), dim3(kBlock), 0, s, (const T*)M.tri, (int)nf, M.P, (const T*)M.box, M.ctr, M.mom, area);
         for (int m = M.P / 2; m >= 1; m /= 2)
-            hipLaunchKernelGGL(k_mesh_mrefit<T>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const T*)M.box, M.ctr, M.mom, area, m);
+            hipLaunchKernelGGL(k_mesh_mrefit<T>, dim3(blocks_for((size_t)m)), dim3(kBlock), 0, s, (const T*)M.box, M.ctr, M.mom, area, m);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -123,7 +120,7 @@ struct MeshPointsOp {                           // closest_points_on_mesh (src/c
     int validate(int64_t) const { return 0; }
     int stage(Arena& ar, hipStream_t s, int64_t n, bool on_dev) { return stage_in(ar, p, n, on_dev, s, &p); }
     void keys(hipStream_t s, int64_t n, const MeshHead<T>* h, unsigned long long* k, int* d_bad) const {
-        hipLaunchKernelGGL(k_mesh_qcodes<T>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p, (int)n, h, k, d_bad);
+        hipLaunchKernelGGL(k_mesh_qcodes<T>, dim3(blocks_for((size_t)n)), dim3(kBlock), 0, s, p, (int)n, h, k, d_bad);
     }
     void walk(hipStream_t s, MeshQuery<T> a, T* val, int64_t n) const {
         a.p = p; a.np = (int)n; a.out_d = val;
@@ -149,7 +146,7 @@ struct MeshRaysOp {                             // ray_mesh_intersection (src/ra
     int o_stride(int64_t n) const { return o_rows == 1 && n != 1 ? 0 : 3; }
     int stage(Arena& ar, hipStream_t s, int64_t n, bool on_dev) { return (stage_in(ar, o, o_rows, on_dev, s, &o) || stage_in(ar, d, n, on_dev, s, &d)) ? -1 : 0; }
     void keys(hipStream_t s, int64_t n, const MeshHead<T>* h, unsigned long long* k, int* d_bad) const {
-        hipLaunchKernelGGL(k_mesh_rkeys<T>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, o, o_stride(n), d, (int)n, h, k, d_bad);
+        hipLaunchKernelGGL(k_mesh_rkeys<T>, dim3(blocks_for((size_t)n)), dim3(kBlock), 0, s, o, o_stride(n), d, (int)n, h, k, d_bad);
     }
     void walk(hipStream_t s, MeshRays<T> a, T* val, int64_t n) const {
         a.o = o; a.o_stride = o_stride(n); a.d = d; a.n = (int)n; a.near = (T)ray_near; a.far = (T)ray_far; a.out_t = val;
@@ -199,10 +196,10 @@ static int mesh_run(Arena& ar, hipStream_t s, const MeshIdx<T>& M, Op op, int64_
     if (op.stage(ar, s, n, on_dev)) return -1;
     int* d_bad = nullptr;
     unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr;
-    if (aalloc(ar, &d_bad, 1) || aalloc(ar, &ka, (size_t)n) || aalloc(ar, &kb, (size_t)n) || aalloc(ar, &ia, (size_t)n) || aalloc(ar, &ib, (size_t)n)) return -1;
-    T *d_val = out_val, *d_bc = out_bc; long long* d_fi = reinterpret_cast<long long*>(out_fi);
-    if (!on_dev && (aalloc(ar, &d_val, (size_t)n) || (Op::kFaces && (aalloc(ar, &d_fi, (size_t)n) || (Op::kBary && aalloc(ar, &d_bc, (size_t)n * 3)))))) return -1;
-    HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    if (flag_word(ar, s, &d_bad) || aalloc(ar, &ka, (size_t)n) || aalloc(ar, &kb, (size_t)n) || aalloc(ar, &ia, (size_t)n) || aalloc(ar, &ib, (size_t)n)) return -1;
+    T *d_val = nullptr, *d_bc = out_bc; long long *const h_fi = reinterpret_cast<long long*>(out_fi), *d_fi = h_fi;
+    if (out_room(ar, on_dev, out_val, (size_t)n, &d_val) || (Op::kFaces && (out_room(ar, on_dev, h_fi, (size_t)n, &d_fi) ||
+                                                                          (Op::kBary && out_room(ar, on_dev, out_bc, (size_t)n * 3, &d_bc))))) return -1;
     op.keys(s, n, M.head, ka, d_bad);
     if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)n, Op::kKeyBits)) return -1;
     typename Op::Params a{};
@@ -212,14 +209,8 @@ static int mesh_run(Arena& ar, hipStream_t s, const MeshIdx<T>& M, Op op, int64_
     HIP_TRY(hipGetLastError());
     tm.mark(2);
     int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (!on_dev) {
-        HIP_TRY(hipMemcpyAsync(out_val, d_val, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, s));
-        if (Op::kFaces) {
-            HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            if (Op::kBary) HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)n * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
-        }
-    }
+    if (flag_fetch(s, d_bad, &bad) || out_give(s, on_dev, out_val, d_val, (size_t)n) || out_give(s, on_dev, h_fi, d_fi, (size_t)n) ||
+        out_give(s, on_dev, out_bc, d_bc, (size_t)n * 3)) return -1;
     HIP_WAIT(s);
     return bad ? Op::message(bad) : 0;
 }

@@ -51,11 +51,11 @@ __global__ __launch_bounds__(kBlock) void k_mr_referenced(const void* __restrict
     const unsigned c = blockIdx.x * kBlock + threadIdx.x;
     bool out = false;
     if (c < ncorners) {
-        const unsigned long long a = cc_index_in(f, kind, c);
+        const unsigned long long a = index_in(f, kind, c);
         out = a >= nv;
         if (!out) ref[a] = 1u;
     }
-    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
+    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, kMeshBadFace);
 }
 // scan: the inclusive scan of the keep flags. map[i] = the number of kept vertices before i, or -1.
 __global__ __launch_bounds__(kBlock) void k_mr_map(const unsigned* __restrict__ flag, const unsigned* __restrict__ scan, unsigned nv, int* __restrict__ map) {
@@ -70,13 +70,10 @@ __global__ __launch_bounds__(kBlock) void k_mr_rows(const T* __restrict__ v, con
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nv) return;
     const int m = map[i];
-    if (corr_f) {
-        if (kind == 0 || kind == 2) static_cast<int*>(corr_f)[i] = m;
-        else static_cast<long long*>(corr_f)[i] = (long long)m;
-    }
+    if (corr_f) index_out_signed(corr_f, kind, i, m);
     if (m < 0) return;
     out_v[3 * (size_t)m] = v[3 * (size_t)i]; out_v[3 * (size_t)m + 1] = v[3 * (size_t)i + 1]; out_v[3 * (size_t)m + 2] = v[3 * (size_t)i + 2];
-    if (corr_v) cc_index_out(corr_v, kind, (size_t)m, i);
+    if (corr_v) index_out(corr_v, kind, (size_t)m, i);
 }
 // One thread per face: keep[i] = 1 where every corner maps to a vertex (and, with `distinct`, to three different ones). A face with an index
 // outside [0, nv) raises the flag and is not kept.
@@ -85,16 +82,16 @@ __global__ __launch_bounds__(kBlock) void k_mr_face_flags(const void* __restrict
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     bool out = false;
     if (i < nf) {
-        const unsigned long long a = cc_index_in(f, kind, 3 * (size_t)i), b = cc_index_in(f, kind, 3 * (size_t)i + 1), c = cc_index_in(f, kind, 3 * (size_t)i + 2);
-        out = a >= nv || b >= nv || c >= nv;
+        int id[3];
+        out = face_in(f, kind, (size_t)i, nv, id);
         bool k = false;
         if (!out) {
-            const int ma = map[a], mb = map[b], mc = map[c];
+            const int ma = map[id[0]], mb = map[id[1]], mc = map[id[2]];
             k = ma >= 0 && mb >= 0 && mc >= 0 && !(distinct && (ma == mb || mb == mc || ma == mc));
         }
         keep[i] = k ? 1u : 0u;
     }
-    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
+    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, kMeshBadFace);
 }
 // The kept faces with mapped indices, in input order. keep == nullptr: every face, in its own row. (A call with an index outside [0, nv) is
 // refused before this launch; such a face would not be kept, and is passed by where all are.)
@@ -102,12 +99,11 @@ __global__ __launch_bounds__(kBlock) void k_mr_faces_out(const void* __restrict_
                                                          const unsigned* __restrict__ keep, const unsigned* __restrict__ scan, void* __restrict__ out_f) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nf || (keep && !keep[i])) return;
-    const unsigned long long a = cc_index_in(f, kind, 3 * (size_t)i), b = cc_index_in(f, kind, 3 * (size_t)i + 1), c = cc_index_in(f, kind, 3 * (size_t)i + 2);
-    if (a >= nv || b >= nv || c >= nv) return;
+    int id[3];
+    if (face_in(f, kind, (size_t)i, nv, id)) return;
     const size_t r = keep ? (size_t)(scan[i] - 1u) : (size_t)i;
-    cc_index_out(out_f, kind, 3 * r, (unsigned)map[a]);
-    cc_index_out(out_f, kind, 3 * r + 1, (unsigned)map[b]);
-    cc_index_out(out_f, kind, 3 * r + 2, (unsigned)map[c]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) index_out(out_f, kind, 3 * r + k, (unsigned)map[id[k]]);
 }
 
 // ---------------------------------------------------------------------------------------------------- orient_mesh_faces
@@ -118,22 +114,21 @@ __global__ __launch_bounds__(kBlock) void k_mr_edge_keys(const void* __restrict_
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     bool out = false;
     if (i < nf) {
-        unsigned long long x[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { x[k] = cc_index_in(f, kind, 3 * (size_t)i + k); out |= x[k] >= nv; }
+        int x[3];
+        out = face_in(f, kind, (size_t)i, nv, x);
         const bool none = out || x[0] == x[1] || x[1] == x[2] || x[2] == x[0];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const unsigned long long a = x[k], b = x[(k + 1) % 3];
+            const unsigned long long a = (unsigned long long)x[k], b = (unsigned long long)x[(k + 1) % 3];
             keys[3 * (size_t)i + k] = none ? kMrNoEdge : ((a < b ? a : b) << hb) | (a < b ? b : a);
         }
     }
-    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
+    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, kMeshBadFace);
 }
 // Does corner id (3 i + k) run from the smaller index of its edge to the larger one?
 __device__ __forceinline__ bool mr_corner_ascends(const void* __restrict__ f, int kind, unsigned id) {
     const unsigned i = id / 3u, k = id - 3u * i;
-    return cc_index_in(f, kind, 3 * (size_t)i + k) < cc_index_in(f, kind, 3 * (size_t)i + (k + 1u) % 3u);
+    return index_in(f, kind, 3 * (size_t)i + k) < index_in(f, kind, 3 * (size_t)i + (k + 1u) % 3u);
 }
 // One thread per sorted position: the head of a run of exactly two equal keys, of two different faces, joins them in the double cover.
 __global__ __launch_bounds__(kBlock) void k_mr_edge_unions(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ ids, unsigned n,
@@ -170,11 +165,11 @@ __global__ __launch_bounds__(kBlock) void k_mr_orient_out(const void* __restrict
     if (i >= nf) return;
     const unsigned p = parent[2 * (size_t)i], m = p >> 1;
     const bool rev = p & 1u;
-    const unsigned a = (unsigned)cc_index_in(f, kind, 3 * (size_t)i), b = (unsigned)cc_index_in(f, kind, 3 * (size_t)i + 1), c = (unsigned)cc_index_in(f, kind, 3 * (size_t)i + 2);
-    cc_index_out(out_f, kind, 3 * (size_t)i, rev ? c : a);
-    cc_index_out(out_f, kind, 3 * (size_t)i + 1, b);
-    cc_index_out(out_f, kind, 3 * (size_t)i + 2, rev ? a : c);
-    cc_index_out(out_c, kind, i, m < nf ? scan[m] - 1u : 0u);
+    const unsigned a = (unsigned)index_in(f, kind, 3 * (size_t)i), b = (unsigned)index_in(f, kind, 3 * (size_t)i + 1), c = (unsigned)index_in(f, kind, 3 * (size_t)i + 2);
+    index_out(out_f, kind, 3 * (size_t)i, rev ? c : a);
+    index_out(out_f, kind, 3 * (size_t)i + 1, b);
+    index_out(out_f, kind, 3 * (size_t)i + 2, rev ? a : c);
+    index_out(out_c, kind, i, m < nf ? scan[m] - 1u : 0u);
 }
 
 }  // namespace pcu

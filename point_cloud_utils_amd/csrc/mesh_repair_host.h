@@ -1,21 +1,15 @@
 // csrc/mesh_repair_host.h -- host orchestration of remove_mesh_vertices, remove_unreferenced_mesh_vertices, deduplicate_mesh_vertices and
-// orient_mesh_faces (kernels and contract: mesh_repair.h). Included by pcu_hip.hip after the operator frame, voxel_host.h (dedup_device,
-// sort_keys, rank_flags, scan_bytes, read_flag_and_last), mesh_host.h (mesh_validate, MeshGiven, int_kind_bytes) and components_host.h (cc_blocks).
+// orient_mesh_faces (kernels and contract: mesh_repair.h). Included by pcu_hip.hip after the operator frame (stage_faces, out_room / out_give,
+// flag_word, mesh_refusal), voxel_host.h (dedup_device, sort_keys, rank_flags, scan_bytes, read_flag_and_last) and mesh_host.h (mesh_validate, MeshGiven).
 // Every output's size depends on the data: the caller gives room for the upper bound (#v rows, #f rows), the counts come back through
 // int64_t*, and nothing is written to an output before the face indices have passed their range check.
 #pragma once
 
-static int mr_bad_face(int64_t nv) { return fail(PCU_HIP_ERR_INVALID, "f must hold row indices of v: found a face index outside [0, %lld)", (long long)nv); }
 // flags and their scan (n * 8 + 4), the scan's tile sums
 static size_t mr_rank_bytes(size_t n) { return 2 * align_up((n + 1) * 4, 256) + scan_bytes(n) + 512; }
 // what a call with host pointers stages: v, f and the outputs of the same sizes
 template <typename T>
 static size_t mr_staged_bytes(size_t nv, size_t nf, size_t kb) { return 2 * (align_up(nv * 3 * sizeof(T), 256) + align_up(nf * 3 * kb, 256)); }
-// to an output on the caller's side, from the arena
-static int mr_give(hipStream_t s, bool on_dev, void* out, const void* from, size_t bytes) {
-    if (bytes) HIP_TRY(hipMemcpyAsync(out, from, bytes, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    return 0;
-}
 static void mr_stats(pcu_hip_stats* st, Timer& tm, int64_t nf, int64_t escalated) {
     if (!st) return;
     st->n_queries = nf; st->n_escalated = escalated; st->n_passes = 1;
@@ -24,21 +18,21 @@ static void mr_stats(pcu_hip_stats* st, Timer& tm, int64_t nf, int64_t escalated
 
 // The flag-and-scan steps (rank_flags of voxel_host.h with this file's kernels). No wait in any.
 static int mr_rank_mask(Arena& ar, hipStream_t s, SortedRuns& r, const unsigned char* d_mask, unsigned nv) {
-    return rank_flags(ar, s, r, (int)nv, [&](unsigned* flag) { hipLaunchKernelGGL(k_mr_mask_flags, dim3(cc_blocks(nv)), dim3(kBlock), 0, s, d_mask, nv, flag); });
+    return rank_flags(ar, s, r, (int)nv, [&](unsigned* flag) { hipLaunchKernelGGL(k_mr_mask_flags, dim3(blocks_for(nv)), dim3(kBlock), 0, s, d_mask, nv, flag); });
 }
 static int mr_rank_referenced(Arena& ar, hipStream_t s, SortedRuns& r, const void* d_f, int f_kind, unsigned nf, unsigned nv, int* d_bad) {
     return rank_flags(ar, s, r, (int)nv, [&](unsigned* ref) {
         (void)hipMemsetAsync(ref, 0, (size_t)nv * 4, s);
-        hipLaunchKernelGGL(k_mr_referenced, dim3(cc_blocks((size_t)nf * 3)), dim3(kBlock), 0, s, d_f, f_kind, 3u * nf, nv, ref, d_bad);
+        hipLaunchKernelGGL(k_mr_referenced, dim3(blocks_for((size_t)nf * 3)), dim3(kBlock), 0, s, d_f, f_kind, 3u * nf, nv, ref, d_bad);
     });
 }
 static int mr_rank_faces(Arena& ar, hipStream_t s, SortedRuns& r, const void* d_f, int f_kind, unsigned nf, unsigned nv, const int* map, int distinct, int* d_bad) {
     return rank_flags(ar, s, r, (int)nf, [&](unsigned* keep) {
-        hipLaunchKernelGGL(k_mr_face_flags, dim3(cc_blocks(nf)), dim3(kBlock), 0, s, d_f, f_kind, nf, nv, map, distinct, keep, d_bad);
+        hipLaunchKernelGGL(k_mr_face_flags, dim3(blocks_for(nf)), dim3(kBlock), 0, s, d_f, f_kind, nf, nv, map, distinct, keep, d_bad);
     });
 }
 static int mr_rank_roots(Arena& ar, hipStream_t s, SortedRuns& r, const unsigned* parent, unsigned nf, unsigned* d_tw) {
-    return rank_flags(ar, s, r, (int)nf, [&](unsigned* root) { hipLaunchKernelGGL(k_mr_patch_roots, dim3(cc_blocks(nf)), dim3(kBlock), 0, s, parent, nf, root, d_tw); });
+    return rank_flags(ar, s, r, (int)nf, [&](unsigned* root) { hipLaunchKernelGGL(k_mr_patch_roots, dim3(blocks_for(nf)), dim3(kBlock), 0, s, parent, nf, root, d_tw); });
 }
 
 // remove_mesh_vertices (src/remove_mesh_vertices.cpp:22-73). mask: nv bytes, non-zero keeps. out_v (nv,3) and out_f (nf,3) are sized for the
@@ -56,33 +50,31 @@ static int remove_mesh_vertices_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, cons
     return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: flags, scans, map and the wait, 2-3: rows and faces
         const T* dv = nullptr; const char* d_f = nullptr; const unsigned char* d_mask = nullptr;
-        if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(m.f), NF * 3 * kb, on_dev, s, &d_f) ||
-            stage_any(ar, mask, NV, on_dev, s, &d_mask)) return -1;
+        if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || stage_faces(ar, m.f, NF, m.f_kind, on_dev, s, &d_f) || stage_any(ar, mask, NV, on_dev, s, &d_mask)) return -1;
         int *map = nullptr, *d_bad = nullptr;
-        if (aalloc(ar, &map, NV) || aalloc(ar, &d_bad, 1)) return -1;
+        if (aalloc(ar, &map, NV) || flag_word(ar, s, &d_bad)) return -1;
         const unsigned unv = (unsigned)m.nv, unf = (unsigned)m.nf;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
         tm.mark(0);
         SortedRuns vs, fs;
         if (mr_rank_mask(ar, s, vs, d_mask, unv)) return -1;
-        hipLaunchKernelGGL(k_mr_map, dim3(cc_blocks(NV)), dim3(kBlock), 0, s, (const unsigned*)vs.flag, (const unsigned*)vs.scan, unv, map);
+        hipLaunchKernelGGL(k_mr_map, dim3(blocks_for(NV)), dim3(kBlock), 0, s, (const unsigned*)vs.flag, (const unsigned*)vs.scan, unv, map);
         if (mr_rank_faces(ar, s, fs, d_f, m.f_kind, unf, unv, map, 0, d_bad)) return -1;
         int bad = 0; unsigned kept_v = 0, kept_f = 0;
         if (read_flag_and_last(s, d_bad, (const unsigned*)fs.scan, NF, &bad, &kept_f)) return -1;
         HIP_TRY(hipMemcpyAsync(&kept_v, vs.scan + (NV - 1), 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         tm.mark(1);
-        if (bad) return mr_bad_face(m.nv);
+        if (bad) return mesh_refusal(bad, m.nv);
         if (kept_v > unv || kept_f > unf) return fail(PCU_HIP_ERR_RUNTIME, "internal: %u of %lld vertices, %u of %lld faces kept", kept_v, (long long)m.nv, kept_f, (long long)m.nf);
-        T* d_ov = out_v; char* d_of = static_cast<char*>(out_f);
-        if (!on_dev && (aalloc(ar, &d_ov, (size_t)kept_v * 3) || aalloc(ar, &d_of, (size_t)kept_f * 3 * kb))) return -1;
+        T* d_ov = nullptr; char *const h_of = static_cast<char*>(out_f), *d_of = nullptr;
+        if (out_room(ar, on_dev, out_v, (size_t)kept_v * 3, &d_ov) || out_room(ar, on_dev, h_of, (size_t)kept_f * 3 * kb, &d_of)) return -1;
         tm.mark(2);
-        hipLaunchKernelGGL(k_mr_rows<T>, dim3(cc_blocks(NV)), dim3(kBlock), 0, s, dv, (const int*)map, unv, d_ov, m.f_kind, (void*)nullptr, (void*)nullptr);
-        hipLaunchKernelGGL(k_mr_faces_out, dim3(cc_blocks(NF)), dim3(kBlock), 0, s, (const void*)d_f, m.f_kind, unf, unv, (const int*)map, (const unsigned*)fs.flag,
+        hipLaunchKernelGGL(k_mr_rows<T>, dim3(blocks_for(NV)), dim3(kBlock), 0, s, dv, (const int*)map, unv, d_ov, m.f_kind, (void*)nullptr, (void*)nullptr);
+        hipLaunchKernelGGL(k_mr_faces_out, dim3(blocks_for(NF)), dim3(kBlock), 0, s, (const void*)d_f, m.f_kind, unf, unv, (const int*)map, (const unsigned*)fs.flag,
                            (const unsigned*)fs.scan, (void*)d_of);
         HIP_TRY(hipGetLastError());
         tm.mark(3);
-        if (!on_dev && (mr_give(s, false, out_v, d_ov, (size_t)kept_v * 3 * sizeof(T)) || mr_give(s, false, out_f, d_of, (size_t)kept_f * 3 * kb))) return -1;
+        if (out_give(s, on_dev, out_v, d_ov, (size_t)kept_v * 3) || out_give(s, on_dev, h_of, d_of, (size_t)kept_f * 3 * kb)) return -1;
         HIP_WAIT(s);
         *out_nv = (int64_t)kept_v; *out_nf = (int64_t)kept_f;
         mr_stats(st, tm, m.nf, m.nf - (int64_t)kept_f);
@@ -105,31 +97,32 @@ static int remove_unreferenced_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, T* ou
     return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: referenced flags, scan, map and the wait, 2-3: rows and faces
         const T* dv = nullptr; const char* d_f = nullptr;
-        if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(m.f), NF * 3 * kb, on_dev, s, &d_f)) return -1;
+        if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || stage_faces(ar, m.f, NF, m.f_kind, on_dev, s, &d_f)) return -1;
         int *map = nullptr, *d_bad = nullptr;
-        if (aalloc(ar, &map, NV) || aalloc(ar, &d_bad, 1)) return -1;
+        if (aalloc(ar, &map, NV) || flag_word(ar, s, &d_bad)) return -1;
         const unsigned unv = (unsigned)m.nv, unf = (unsigned)m.nf;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
         tm.mark(0);
         SortedRuns vs;
         if (mr_rank_referenced(ar, s, vs, d_f, m.f_kind, unf, unv, d_bad)) return -1;
-        hipLaunchKernelGGL(k_mr_map, dim3(cc_blocks(NV)), dim3(kBlock), 0, s, (const unsigned*)vs.flag, (const unsigned*)vs.scan, unv, map);
+        hipLaunchKernelGGL(k_mr_map, dim3(blocks_for(NV)), dim3(kBlock), 0, s, (const unsigned*)vs.flag, (const unsigned*)vs.scan, unv, map);
         int bad = 0; unsigned kept_v = 0;
         if (read_flag_and_last(s, d_bad, (const unsigned*)vs.scan, NV, &bad, &kept_v)) return -1;
         HIP_WAIT(s);
         tm.mark(1);
-        if (bad) return mr_bad_face(m.nv);
+        if (bad) return mesh_refusal(bad, m.nv);
         if (kept_v == 0 || kept_v > unv) return fail(PCU_HIP_ERR_RUNTIME, "internal: %u of %lld vertices referenced", kept_v, (long long)m.nv);
-        T* d_ov = out_v; char *d_of = static_cast<char*>(out_f), *d_cv = static_cast<char*>(out_corr_v), *d_cf = static_cast<char*>(out_corr_f);
-        if (!on_dev && (aalloc(ar, &d_ov, (size_t)kept_v * 3) || aalloc(ar, &d_of, NF * 3 * kb) || aalloc(ar, &d_cv, (size_t)kept_v * kb) || aalloc(ar, &d_cf, NV * kb))) return -1;
+        T* d_ov = nullptr; char *const h_of = static_cast<char*>(out_f), *const h_cv = static_cast<char*>(out_corr_v), *const h_cf = static_cast<char*>(out_corr_f);
+        char *d_of = nullptr, *d_cv = nullptr, *d_cf = nullptr;
+        if (out_room(ar, on_dev, out_v, (size_t)kept_v * 3, &d_ov) || out_room(ar, on_dev, h_of, NF * 3 * kb, &d_of) || out_room(ar, on_dev, h_cv, (size_t)kept_v * kb, &d_cv) ||
+            out_room(ar, on_dev, h_cf, NV * kb, &d_cf)) return -1;
         tm.mark(2);
-        hipLaunchKernelGGL(k_mr_rows<T>, dim3(cc_blocks(NV)), dim3(kBlock), 0, s, dv, (const int*)map, unv, d_ov, m.f_kind, (void*)d_cv, (void*)d_cf);
-        hipLaunchKernelGGL(k_mr_faces_out, dim3(cc_blocks(NF)), dim3(kBlock), 0, s, (const void*)d_f, m.f_kind, unf, unv, (const int*)map, (const unsigned*)nullptr,
+        hipLaunchKernelGGL(k_mr_rows<T>, dim3(blocks_for(NV)), dim3(kBlock), 0, s, dv, (const int*)map, unv, d_ov, m.f_kind, (void*)d_cv, (void*)d_cf);
+        hipLaunchKernelGGL(k_mr_faces_out, dim3(blocks_for(NF)), dim3(kBlock), 0, s, (const void*)d_f, m.f_kind, unf, unv, (const int*)map, (const unsigned*)nullptr,
                            (const unsigned*)nullptr, (void*)d_of);
         HIP_TRY(hipGetLastError());
         tm.mark(3);
-        if (!on_dev && (mr_give(s, false, out_v, d_ov, (size_t)kept_v * 3 * sizeof(T)) || mr_give(s, false, out_f, d_of, NF * 3 * kb) ||
-                        mr_give(s, false, out_corr_v, d_cv, (size_t)kept_v * kb) || mr_give(s, false, out_corr_f, d_cf, NV * kb))) return -1;
+        if (out_give(s, on_dev, out_v, d_ov, (size_t)kept_v * 3) || out_give(s, on_dev, h_of, d_of, NF * 3 * kb) || out_give(s, on_dev, h_cv, d_cv, (size_t)kept_v * kb) ||
+            out_give(s, on_dev, h_cf, d_cf, NV * kb)) return -1;
         HIP_WAIT(s);
         *out_nv = (int64_t)kept_v;
         mr_stats(st, tm, m.nf, 0);
@@ -154,11 +147,10 @@ static int dedup_mesh_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, double epsilon
     return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: the vertices' keys, sort and runs, the face flags, their scan and the wait, 2-3: faces and copies
         const T* dv = nullptr; const char* d_f = nullptr;
-        if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || stage_any(ar, static_cast<const char*>(m.f), NF * 3 * kb, on_dev, s, &d_f)) return -1;
+        if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || stage_faces(ar, m.f, NF, m.f_kind, on_dev, s, &d_f)) return -1;
         T* t_v = nullptr; int *t_svi = nullptr, *t_svj = nullptr, *d_bad = nullptr;
-        if (aalloc(ar, &t_v, NV * 3) || aalloc(ar, &t_svi, NV) || aalloc(ar, &t_svj, NV) || aalloc(ar, &d_bad, 1)) return -1;
+        if (aalloc(ar, &t_v, NV * 3) || aalloc(ar, &t_svi, NV) || aalloc(ar, &t_svj, NV) || flag_word(ar, s, &d_bad)) return -1;
         const unsigned unv = (unsigned)m.nv, unf = (unsigned)m.nf;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
         tm.mark(0);
         const unsigned* n_out_dev = nullptr;
         if (dedup_device<T>(ar, s, dv, (int)m.nv, epsilon, t_v, t_svi, t_svj, &n_out_dev)) return -1;
@@ -169,17 +161,17 @@ static int dedup_mesh_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, double epsilon
         HIP_TRY(hipMemcpyAsync(&kept_v, n_out_dev, 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         tm.mark(1);
-        if (bad) return mr_bad_face(m.nv);
+        if (bad) return mesh_refusal(bad, m.nv);
         if (kept_v == 0 || kept_v > unv || kept_f > unf) return fail(PCU_HIP_ERR_RUNTIME, "internal: %u of %lld vertices, %u of %lld faces kept", kept_v, (long long)m.nv, kept_f, (long long)m.nf);
-        char* d_of = static_cast<char*>(out_f);
-        if (!on_dev && aalloc(ar, &d_of, (size_t)kept_f * 3 * kb)) return -1;
+        char *const h_of = static_cast<char*>(out_f), *d_of = nullptr;
+        if (out_room(ar, on_dev, h_of, (size_t)kept_f * 3 * kb, &d_of)) return -1;
         tm.mark(2);
-        hipLaunchKernelGGL(k_mr_faces_out, dim3(cc_blocks(NF)), dim3(kBlock), 0, s, (const void*)d_f, m.f_kind, unf, unv, (const int*)t_svj, (const unsigned*)fs.flag,
+        hipLaunchKernelGGL(k_mr_faces_out, dim3(blocks_for(NF)), dim3(kBlock), 0, s, (const void*)d_f, m.f_kind, unf, unv, (const int*)t_svj, (const unsigned*)fs.flag,
                            (const unsigned*)fs.scan, (void*)d_of);
         HIP_TRY(hipGetLastError());
-        if (mr_give(s, on_dev, out_v, t_v, (size_t)kept_v * 3 * sizeof(T)) || mr_give(s, on_dev, out_svi, t_svi, (size_t)kept_v * 4) || mr_give(s, on_dev, out_svj, t_svj, NV * 4)) return -1;
+        if (out_give(s, on_dev, out_v, t_v, (size_t)kept_v * 3) || out_give(s, on_dev, out_svi, t_svi, (size_t)kept_v) || out_give(s, on_dev, out_svj, t_svj, NV)) return -1;
         tm.mark(3);
-        if (!on_dev && mr_give(s, false, out_f, d_of, (size_t)kept_f * 3 * kb)) return -1;
+        if (out_give(s, on_dev, h_of, d_of, (size_t)kept_f * 3 * kb)) return -1;
         HIP_WAIT(s);
         *out_nv = (int64_t)kept_v; *out_nf = (int64_t)kept_f;
         mr_stats(st, tm, m.nf, m.nf - (int64_t)kept_f);
@@ -204,38 +196,37 @@ static int orient_mesh_faces_impl(pcu_hip_ctx* c, const void* f, int64_t nf, int
     return op_run(c, flags, stream, st, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;      // marks 0-1: keys, sort and unions, 1-2: flatten, roots and their ranks, 3-4: rows and labels
         const char* d_f = nullptr;
-        if (stage_any(ar, static_cast<const char*>(f), NF * 3 * kb, on_dev, s, &d_f)) return -1;
+        if (stage_faces(ar, f, NF, f_kind, on_dev, s, &d_f)) return -1;
         SortedRuns es, ps;
         unsigned *parent = nullptr, *d_tw = nullptr; int* d_bad = nullptr;
-        if (aalloc(ar, &es.keys, 3 * NF) || aalloc(ar, &parent, 2 * NF) || aalloc(ar, &d_tw, 1) || aalloc(ar, &d_bad, 1)) return -1;
+        if (aalloc(ar, &es.keys, 3 * NF) || aalloc(ar, &parent, 2 * NF) || aalloc(ar, &d_tw, 1) || flag_word(ar, s, &d_bad)) return -1;
         const unsigned unf = (unsigned)nf, unv = (unsigned)nv;
         const int hb = std::max(bits_of((unsigned long long)(nv - 1)), 1);
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
         HIP_TRY(hipMemsetAsync(d_tw, 0, sizeof(unsigned), s));
         tm.mark(0);
-        hipLaunchKernelGGL(k_mr_edge_keys, dim3(cc_blocks(NF)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, unf, unv, hb, es.keys, d_bad);
+        hipLaunchKernelGGL(k_mr_edge_keys, dim3(blocks_for(NF)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, unf, unv, hb, es.keys, d_bad);
         if (sort_keys(ar, s, es, (int)(3 * nf), 2 * hb)) return -1;
-        hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(2 * NF)), dim3(kBlock), 0, s, parent, 2u * unf);
-        hipLaunchKernelGGL(k_mr_edge_unions, dim3(cc_blocks(3 * NF)), dim3(kBlock), 0, s, (const unsigned long long*)es.keys, (const unsigned*)es.ids, 3u * unf, (const void*)d_f,
+        hipLaunchKernelGGL(k_cc_init, dim3(blocks_for(2 * NF)), dim3(kBlock), 0, s, parent, 2u * unf);
+        hipLaunchKernelGGL(k_mr_edge_unions, dim3(blocks_for(3 * NF)), dim3(kBlock), 0, s, (const unsigned long long*)es.keys, (const unsigned*)es.ids, 3u * unf, (const void*)d_f,
                            f_kind, parent);
         tm.mark(1);
-        hipLaunchKernelGGL(k_cc_flatten, dim3(cc_blocks(2 * NF)), dim3(kBlock), 0, s, parent, 2u * unf, (unsigned*)nullptr);
+        hipLaunchKernelGGL(k_cc_flatten, dim3(blocks_for(2 * NF)), dim3(kBlock), 0, s, parent, 2u * unf, (unsigned*)nullptr);
         if (mr_rank_roots(ar, s, ps, parent, unf, d_tw)) return -1;
         tm.mark(2);
         int bad = 0; unsigned count = 0, twisted = 0;
         if (read_flag_and_last(s, d_bad, (const unsigned*)ps.scan, NF, &bad, &count)) return -1;
         HIP_TRY(hipMemcpyAsync(&twisted, d_tw, 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
-        if (bad) return mr_bad_face(nv);
+        if (bad) return mesh_refusal(bad, nv);
         if (count == 0 || count > unf || twisted > count) return fail(PCU_HIP_ERR_RUNTIME, "internal: %u patches (%u not orientable) of %lld faces", count, twisted, (long long)nf);
-        char *d_of = static_cast<char*>(out_f), *d_oc = static_cast<char*>(out_c);
-        if (!on_dev && (aalloc(ar, &d_of, NF * 3 * kb) || aalloc(ar, &d_oc, NF * kb))) return -1;
+        char *const h_of = static_cast<char*>(out_f), *const h_oc = static_cast<char*>(out_c), *d_of = nullptr, *d_oc = nullptr;
+        if (out_room(ar, on_dev, h_of, NF * 3 * kb, &d_of) || out_room(ar, on_dev, h_oc, NF * kb, &d_oc)) return -1;
         tm.mark(3);
-        hipLaunchKernelGGL(k_mr_orient_out, dim3(cc_blocks(NF)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, unf, (const unsigned*)parent, (const unsigned*)ps.scan,
+        hipLaunchKernelGGL(k_mr_orient_out, dim3(blocks_for(NF)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, unf, (const unsigned*)parent, (const unsigned*)ps.scan,
                            (void*)d_of, (void*)d_oc);
         HIP_TRY(hipGetLastError());
         tm.mark(4);
-        if (!on_dev && (mr_give(s, false, out_f, d_of, NF * 3 * kb) || mr_give(s, false, out_c, d_oc, NF * kb))) return -1;
+        if (out_give(s, on_dev, h_of, d_of, NF * 3 * kb) || out_give(s, on_dev, h_oc, d_oc, NF * kb)) return -1;
         HIP_WAIT(s);
         *out_patches = (int64_t)count;
         if (st) {

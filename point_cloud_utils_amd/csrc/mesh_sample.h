@@ -41,11 +41,14 @@ __device__ __forceinline__ T ms_len(const T* __restrict__ p, const T* __restrict
 template <typename T> __device__ __forceinline__ T ms_max0(T x) { return x < (T)0 ? (T)0 : x; }
 
 // One lane per face, through the range-checked int32 triples of k_mesh_faces. The largest area: a wave reduction and one integer atomic.
+// bad (optional): the finished flag word of the launches before, where `area` is the caller's own memory: with a vertex or face bit raised
+// the call will be refused, and no area is written.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_mesh_areas(const T* __restrict__ v, const int* __restrict__ fidx, int nf, T* __restrict__ area,
-                                                       MsHead<T>* __restrict__ h) {
+                                                       MsHead<T>* __restrict__ h, const int* __restrict__ bad) {
     using E = typename EncT<T>::type;
     const int t = blockIdx.x * kBlock + threadIdx.x;
+    const bool refused = bad && (*bad & (kMeshBadVertex | kMeshBadFace)) != 0;
     E key = 0;
     if (t < nf) {
         const T* v1 = v + 3 * (size_t)fidx[3 * (size_t)t];
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void k_mesh_areas(const T* __restrict__ v, 
         const T a = ms_len(v2, v1), b = ms_len(v3, v2), c = ms_len(v1, v3);
         const T p = (T)0.5 * ((a + b) + c);
         const T A = sqrt(((p * ms_max0(p - a)) * ms_max0(p - b)) * ms_max0(p - c));
-        area[t] = A;
+        if (!refused) area[t] = A;
         key = ms_bits(A);
     }
 #pragma unroll

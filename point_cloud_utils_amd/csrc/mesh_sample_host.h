@@ -1,6 +1,6 @@
 // csrc/mesh_sample_host.h -- host orchestration of mesh_face_areas, sample_mesh_random and sample_mesh_poisson_disk (kernels and contract:
 // mesh_sample.h; the greedy: poisson_host.h). Included by pcu_hip.hip after the operator frame, voxel_host.h (the scan), poisson_host.h and
-// mesh_host.h (mesh_validate, MeshGiven, int_kind_bytes).
+// mesh_host.h (mesh_validate, MeshGiven).
 #pragma once
 
 // The mesh side of one call on the device: staged vertices, range-checked faces, areas, the scan of the weights.
@@ -21,27 +21,27 @@ static size_t ms_mesh_bytes(const MeshGiven<T>& m, bool on_dev) {
 template <typename T>
 static int ms_mesh_stage(Arena& ar, hipStream_t s, const MeshGiven<T>& m, bool on_dev, MsMesh<T>& M) {
     const char* df = nullptr;
-    if (stage_in(ar, m.v, m.nv, on_dev, s, &M.v) ||
-        stage_any(ar, static_cast<const char*>(m.f), (size_t)m.nf * 3 * int_kind_bytes(m.f_kind), on_dev, s, &df)) return -1;
+    if (stage_in(ar, m.v, m.nv, on_dev, s, &M.v) || stage_faces(ar, m.f, (size_t)m.nf, m.f_kind, on_dev, s, &df)) return -1;
     M.nf = (int)m.nf;
     if (aalloc(ar, &M.head, 1) || aalloc(ar, &M.fidx, (size_t)m.nf * 3)) return -1;
     hipLaunchKernelGGL(k_mesh_head_init<T>, dim3(1), dim3(64), 0, s, M.head);
-    int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
-    hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3((unsigned)((m.nv * 3 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, M.v, (long long)m.nv * 3, d_bad, kMeshBadVertex);
-    hipLaunchKernelGGL(k_mesh_faces<T>, dim3((unsigned)((m.nf + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, (const void*)df, m.f_kind, (int)m.nf, (int)m.nv, M.v,
+    hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3(blocks_for((size_t)m.nv * 3)), dim3(kBlock), 0, s, M.v, (long long)m.nv * 3, mesh_head_flag(M.head), kMeshBadVertex);
+    hipLaunchKernelGGL(k_mesh_faces<T>, dim3(blocks_for((size_t)m.nf)), dim3(kBlock), 0, s, (const void*)df, m.f_kind, (int)m.nf, (int)m.nv, M.v,
                        M.fidx, M.head);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-// ms_mesh_stage, then the areas (into d_area if given) and, with `weights`, the weights and their scan. No wait.
+// ms_mesh_stage, then the areas and, with `weights`, the weights and their scan. The areas go into d_area if given: the caller's own memory,
+// which k_mesh_areas leaves as it is when the checks of ms_mesh_stage have raised the flag word. No wait.
 template <typename T>
 static int ms_mesh_enqueue(Arena& ar, hipStream_t s, const MeshGiven<T>& m, bool on_dev, bool weights, T* d_area, MsMesh<T>& M) {
     if (ms_mesh_stage(ar, s, m, on_dev, M)) return -1;
     M.area = d_area;
     if (aalloc(ar, &M.mh, 1) || (!M.area && aalloc(ar, &M.area, (size_t)m.nf))) return -1;
-    const int nbf = (int)((m.nf + kBlock - 1) / kBlock);
+    const unsigned nbf = blocks_for((size_t)m.nf);
     HIP_TRY(hipMemsetAsync(M.mh, 0, sizeof(MsHead<T>), s));
-    hipLaunchKernelGGL(k_mesh_areas<T>, dim3(nbf), dim3(kBlock), 0, s, M.v, (const int*)M.fidx, (int)m.nf, M.area, M.mh);
+    hipLaunchKernelGGL(k_mesh_areas<T>, dim3(nbf), dim3(kBlock), 0, s, M.v, (const int*)M.fidx, (int)m.nf, M.area, M.mh,
+                       (const int*)(d_area ? mesh_head_flag(M.head) : nullptr));
     if (weights) {
         unsigned long long* w = nullptr;
         if (aalloc(ar, &w, (size_t)m.nf) || aalloc(ar, &M.C, (size_t)m.nf)) return -1;
@@ -58,8 +58,7 @@ struct MsSeen {
 };
 template <typename T>
 static int ms_mesh_readback(hipStream_t s, const MsMesh<T>& M, bool weights, MsSeen<T>* h) {
-    int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
-    HIP_TRY(hipMemcpyAsync(&h->bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (flag_fetch(s, mesh_head_flag(M.head), &h->bad)) return -1;
     if (weights) {
         HIP_TRY(hipMemcpyAsync(&h->amax, M.mh, sizeof(T), hipMemcpyDeviceToHost, s));       // (the bit pattern of a non-negative T, or of a NaN)
         HIP_TRY(hipMemcpyAsync(&h->W, M.C + (M.nf - 1), 8, hipMemcpyDeviceToHost, s));
@@ -68,8 +67,7 @@ static int ms_mesh_readback(hipStream_t s, const MsMesh<T>& M, bool weights, MsS
 }
 template <typename T>
 static int ms_mesh_refuse(const MsSeen<T>& h, int64_t nv, bool weights) {
-    if (h.bad & kMeshBadVertex) return fail(PCU_HIP_ERR_INVALID, "v must not contain NaN or infinite coordinates");
-    if (h.bad & kMeshBadFace) return fail(PCU_HIP_ERR_INVALID, "f must hold row indices of v: found a face index outside [0, %lld)", (long long)nv);
+    if (h.bad) return mesh_refusal(h.bad, nv);
     if (!weights) return 0;
     if (!std::isfinite(h.amax)) return fail(PCU_HIP_ERR_INVALID, "face areas overflow the scalar type of v");
     if (h.amax == (T)0) return fail(PCU_HIP_ERR_INVALID, "Mesh has zero area");
@@ -85,8 +83,8 @@ static int mesh_face_areas_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, T* out_ar
     return op_run(c, flags, stream, st, ms_mesh_bytes(m, on_dev), [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;
         MsMesh<T> M; MsSeen<T> seen;
-        if (ms_mesh_enqueue<T>(ar, s, m, on_dev, false, on_dev ? out_area : nullptr, M) || ms_mesh_readback(s, M, false, &seen)) return -1;
-        if (!on_dev) HIP_TRY(hipMemcpyAsync(out_area, M.area, (size_t)m.nf * sizeof(T), hipMemcpyDeviceToHost, s));
+        if (ms_mesh_enqueue<T>(ar, s, m, on_dev, false, on_dev ? out_area : nullptr, M) || ms_mesh_readback(s, M, false, &seen) ||
+            out_give(s, on_dev, out_area, (const T*)M.area, (size_t)m.nf)) return -1;
         HIP_WAIT(s);
         if (int rc = ms_mesh_refuse(seen, m.nv, false)) return rc;
         if (st) { st->n_queries = m.nf; st->n_passes = 1; }
@@ -113,15 +111,12 @@ static int sample_mesh_random_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64_
         auto& [c, s, on_dev, ar, tm] = fr;
         MsMesh<T> M; MsSeen<T> seen;
         if (ms_mesh_enqueue<T>(ar, s, m, on_dev, true, nullptr, M)) return -1;
-        long long* d_fi = reinterpret_cast<long long*>(out_fi); T* d_bc = out_bc;
-        if (!on_dev && (aalloc(ar, &d_fi, (size_t)n) || aalloc(ar, &d_bc, (size_t)n * 3))) return -1;
+        long long *const h_fi = reinterpret_cast<long long*>(out_fi), *d_fi = nullptr; T* d_bc = nullptr;
+        if (out_room(ar, on_dev, h_fi, (size_t)n, &d_fi) || out_room(ar, on_dev, out_bc, (size_t)n * 3, &d_bc)) return -1;
         ms_sample_launch(s, M, seed, n, d_fi, d_bc);              // (writes nothing for a mesh that is refused below: W = 0)
         HIP_TRY(hipGetLastError());
-        if (ms_mesh_readback(s, M, true, &seen)) return -1;
-        if (!on_dev) {
-            HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)n * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
-        }
+        if (ms_mesh_readback(s, M, true, &seen) || out_give(s, on_dev, h_fi, (const long long*)d_fi, (size_t)n) ||
+            out_give(s, on_dev, out_bc, (const T*)d_bc, (size_t)n * 3)) return -1;
         HIP_WAIT(s);
         if (int rc = ms_mesh_refuse(seen, m.nv, true)) return rc;
         if (st) { st->n_queries = n; st->n_passes = 1; }
@@ -173,23 +168,20 @@ static int sample_mesh_poisson_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int64
         long long *c_fi = nullptr; T *c_bc = nullptr, *P = nullptr; int32_t* idx = nullptr;
         if (aalloc(ar, &c_fi, (size_t)nc) || aalloc(ar, &c_bc, (size_t)nc * 3) || aalloc(ar, &P, (size_t)nc * 3) || aalloc(ar, &idx, (size_t)nc)) return -1;
         ms_sample_launch(s, M, seed, nc, c_fi, c_bc);
-        hipLaunchKernelGGL(k_mesh_positions<T>, dim3((unsigned)((nc + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, M.v, (const int*)M.fidx, (const long long*)c_fi,
+        hipLaunchKernelGGL(k_mesh_positions<T>, dim3(blocks_for((size_t)nc)), dim3(kBlock), 0, s, M.v, (const int*)M.fidx, (const long long*)c_fi,
                            (const T*)c_bc, (int)nc, P);
         HIP_TRY(hipGetLastError());
         PdRun<T> R;
         int64_t cnt = 0;
         if (int rc = pd_body<T>(ar, s, P, nc, radius, target, seed, tol, idx, &cnt, R)) return rc;
         if (cnt > capacity) return fail(PCU_HIP_ERR_INVALID, "sample_mesh_poisson_disk keeps %lld rows: the output arrays hold %lld", (long long)cnt, (long long)capacity);
-        long long* d_fi = reinterpret_cast<long long*>(out_fi); T* d_bc = out_bc;
-        if (!on_dev && (aalloc(ar, &d_fi, (size_t)cnt) || aalloc(ar, &d_bc, (size_t)cnt * 3))) return -1;
+        long long *const h_fi = reinterpret_cast<long long*>(out_fi), *d_fi = nullptr; T* d_bc = nullptr;
+        if (out_room(ar, on_dev, h_fi, (size_t)cnt, &d_fi) || out_room(ar, on_dev, out_bc, (size_t)cnt * 3, &d_bc)) return -1;
         if (cnt > 0) {
-            hipLaunchKernelGGL(k_mesh_keep<T>, dim3((unsigned)((cnt + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, (const int32_t*)idx, (int)cnt, (const long long*)c_fi,
+            hipLaunchKernelGGL(k_mesh_keep<T>, dim3(blocks_for((size_t)cnt)), dim3(kBlock), 0, s, (const int32_t*)idx, (int)cnt, (const long long*)c_fi,
                                (const T*)c_bc, d_fi, d_bc);
             HIP_TRY(hipGetLastError());
-            if (!on_dev) {
-                HIP_TRY(hipMemcpyAsync(out_fi, d_fi, (size_t)cnt * 8, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipMemcpyAsync(out_bc, d_bc, (size_t)cnt * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
-            }
+            if (out_give(s, on_dev, h_fi, (const long long*)d_fi, (size_t)cnt) || out_give(s, on_dev, out_bc, (const T*)d_bc, (size_t)cnt * 3)) return -1;
         }
         HIP_WAIT(s);
         *out_count = cnt;

@@ -88,17 +88,7 @@ __global__ __launch_bounds__(kBlock) void k_ms_corners(const void* __restrict__ 
     bool b = false;
     if (t < nf) {
         int id[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            unsigned long long u;               // (a negative index becomes a huge unsigned one)
-            if (kind == 0) u = (unsigned long long)(long long)static_cast<const int*>(f)[3 * (size_t)t + j];
-            else if (kind == 1) u = (unsigned long long)static_cast<const long long*>(f)[3 * (size_t)t + j];
-            else if (kind == 2) u = (unsigned long long)static_cast<const unsigned*>(f)[3 * (size_t)t + j];
-            else u = static_cast<const unsigned long long*>(f)[3 * (size_t)t + j];
-            b |= u >= (unsigned long long)nv;
-            id[j] = (int)u;
-        }
-        if (b) id[0] = id[1] = id[2] = 0;
+        b = face_in(f, kind, (size_t)t, (unsigned)nv, id);
 #pragma unroll
         for (int j = 0; j < 3; ++j) { fidx[3 * (size_t)t + j] = id[j]; ck[3 * (size_t)t + j] = (unsigned long long)id[j]; }
     }
@@ -152,10 +142,7 @@ __global__ __launch_bounds__(kBlock) void k_ms_adj_out(const unsigned* __restric
                                                        long long* __restrict__ out_off, void* __restrict__ out_nb) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i <= (unsigned)nv) out_off[i] = (long long)off[i];
-    if (i < ne) {
-        if (kind == 0 || kind == 2) static_cast<int*>(out_nb)[i] = col[i];
-        else static_cast<long long*>(out_nb)[i] = (long long)col[i];
-    }
+    if (i < ne) index_out_signed(out_nb, kind, i, col[i]);
 }
 
 // ---------------------------------------------------------------------------------------------------- geometry
@@ -207,11 +194,14 @@ __global__ __launch_bounds__(kBlock) void k_ms_face_vec(const T* __restrict__ v,
     }
 }
 // One lane per vertex: its corners' contributions in incidence order, then the division by the length. A non-finite length is flagged.
+// `bad` holds the finished vertex and face checks of the launches before: with one of them raised the call will be refused, and nothing is
+// written to out (the caller's own memory when the call's pointers are device memory).
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_ms_vnormals(const unsigned* __restrict__ inc_pos, const unsigned* __restrict__ inc_ids, const T* __restrict__ fn,
                                                         const T* __restrict__ ang, int mode, int nv, T* __restrict__ out, int* __restrict__ bad) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     bool nfin = false;
+    const bool refused = (__atomic_load_n(bad, __ATOMIC_RELAXED) & (kMeshBadVertex | kMeshBadFace)) != 0;
     if (i < nv) {
         T s[3] = {(T)0, (T)0, (T)0};
         const unsigned end = inc_pos[i + 1];
@@ -230,7 +220,7 @@ __global__ __launch_bounds__(kBlock) void k_ms_vnormals(const unsigned* __restri
         nfin = !(r - r == (T)0);
         const bool zero = r == (T)0;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) out[3 * (size_t)i + k] = zero ? (T)0 : s[k] / r;
+        for (int k = 0; k < 3; ++k) if (!refused) out[3 * (size_t)i + k] = zero ? (T)0 : s[k] / r;
     }
     if (__ballot(nfin) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, kMeshBadNormal);
 }

@@ -1,12 +1,11 @@
 // csrc/mesh_smooth_host.h -- host orchestration of mesh_vertex_adjacency / adjacency_list, estimate_mesh_vertex_normals and
 // laplacian_smooth_mesh (kernels and contract: mesh_smooth.h). Included by pcu_hip.hip after the operator frame and the parking functions,
-// voxel_host.h (sort_bytes, scan_bytes, sort_keys, rank_flags) and mesh_host.h (mesh_validate, MeshGiven, int_kind_bytes).
+// voxel_host.h (sort_bytes, scan_bytes, sort_keys, rank_flags) and mesh_host.h (mesh_validate, MeshGiven).
 #pragma once
 
 constexpr int kMsCgMaxIters = 4096;             // a chosen cap that nobody has timed
 constexpr int kMsCgPoll = 8;                    // the host reads the solver's flag word every so many iterations
 
-static unsigned ms_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 // faces and incidence
 static size_t ms_incidence_bytes(size_t nv, size_t nf) { return align_up(nf * 12, 256) + sort_bytes(3 * nf) + align_up((nv + 1) * 4, 256) + 4096; }
 // the pair sort and the CSR (with room for every pair to be an entry)
@@ -27,11 +26,10 @@ struct MsStructure {
 // Stages f, checks its range and writes the corner keys. No wait.
 static int ms_faces(Arena& ar, hipStream_t s, const void* f, int64_t nf, int f_kind, int64_t nv, bool on_dev, MsStructure& S) {
     const char* d_f = nullptr;
-    if (stage_any(ar, static_cast<const char*>(f), (size_t)nf * 3 * int_kind_bytes(f_kind), on_dev, s, &d_f)) return -1;
-    if (aalloc(ar, &S.fidx, (size_t)nf * 3) || aalloc(ar, &S.ckeys, (size_t)nf * 3) || aalloc(ar, &S.d_bad, 1)) return -1;
-    HIP_TRY(hipMemsetAsync(S.d_bad, 0, sizeof(int), s));
+    if (stage_faces(ar, f, (size_t)nf, f_kind, on_dev, s, &d_f)) return -1;
+    if (aalloc(ar, &S.fidx, (size_t)nf * 3) || aalloc(ar, &S.ckeys, (size_t)nf * 3) || flag_word(ar, s, &S.d_bad)) return -1;
     S.hb = bits_of((unsigned long long)(nv - 1));
-    hipLaunchKernelGGL(k_ms_corners, dim3(ms_blocks((size_t)nf)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, (int)nf, (int)nv, S.fidx, S.ckeys, S.d_bad);
+    hipLaunchKernelGGL(k_ms_corners, dim3(blocks_for((size_t)nf)), dim3(kBlock), 0, s, (const void*)d_f, f_kind, (int)nf, (int)nv, S.fidx, S.ckeys, S.d_bad);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -41,7 +39,7 @@ static int ms_incidence(Arena& ar, hipStream_t s, int64_t nf, int64_t nv, MsStru
     SortedRuns r; r.keys = S.ckeys;
     if (aalloc(ar, &S.inc_pos, (size_t)nv + 1) || sort_keys(ar, s, r, C, std::max(S.hb, 1))) return -1;
     S.ckeys = r.keys; S.inc_ids = r.ids;
-    hipLaunchKernelGGL(k_ms_row_starts, dim3(ms_blocks((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned long long*)S.ckeys, C, 0, (int)nv, S.inc_pos);
+    hipLaunchKernelGGL(k_ms_row_starts, dim3(blocks_for((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned long long*)S.ckeys, C, 0, (int)nv, S.inc_pos);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -51,25 +49,24 @@ static int ms_adjacency(Arena& ar, hipStream_t s, int64_t nf, int64_t nv, MsStru
     S.K = K;
     SortedRuns r; unsigned* pos = nullptr;
     if (aalloc(ar, &r.keys, (size_t)K) || aalloc(ar, &pos, (size_t)nv + 1) || aalloc(ar, &S.off, (size_t)nv + 1)) return -1;
-    hipLaunchKernelGGL(k_ms_pairs, dim3(ms_blocks((size_t)K / 2)), dim3(kBlock), 0, s, (const int*)S.fidx, K / 2, S.hb, r.keys);
+    hipLaunchKernelGGL(k_ms_pairs, dim3(blocks_for((size_t)K / 2)), dim3(kBlock), 0, s, (const int*)S.fidx, K / 2, S.hb, r.keys);
     if (sort_keys(ar, s, r, K, std::max(2 * S.hb, 1))) return -1;
     S.pkeys = r.keys; S.pids = r.ids;
     if (rank_flags(ar, s, r, K, [&](unsigned* flag) {
-            hipLaunchKernelGGL(k_ms_pair_heads, dim3(ms_blocks((size_t)K)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, K, S.hb, flag);
+            hipLaunchKernelGGL(k_ms_pair_heads, dim3(blocks_for((size_t)K)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, K, S.hb, flag);
         })) return -1;
     unsigned *flag = r.flag, *scan = r.scan;
-    hipLaunchKernelGGL(k_ms_row_starts, dim3(ms_blocks((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, K, S.hb, (int)nv, pos);
-    hipLaunchKernelGGL(k_ms_offsets, dim3(ms_blocks((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned*)pos, (const unsigned*)scan, (int)nv, S.off);
+    hipLaunchKernelGGL(k_ms_row_starts, dim3(blocks_for((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, K, S.hb, (int)nv, pos);
+    hipLaunchKernelGGL(k_ms_offsets, dim3(blocks_for((size_t)nv + 1)), dim3(kBlock), 0, s, (const unsigned*)pos, (const unsigned*)scan, (int)nv, S.off);
     HIP_TRY(hipGetLastError());
     int bad = 0; unsigned ne = 0;
     if (read_flag_and_last(s, S.d_bad, scan, (size_t)K, &bad, &ne)) return -1;
     HIP_WAIT(s);
-    if (bad & kMeshBadVertex) return fail(PCU_HIP_ERR_INVALID, "v must not contain NaN or infinite coordinates");
-    if (bad & kMeshBadFace) return fail(PCU_HIP_ERR_INVALID, "f must hold row indices of v: found a face index outside [0, %lld)", (long long)nv);
+    if (bad) return mesh_refusal(bad, nv);
     S.ne = ne;
     if (aalloc(ar, &S.head_pos, (size_t)ne) || aalloc(ar, &S.col, (size_t)ne)) return -1;
     if (ne > 0) {
-        hipLaunchKernelGGL(k_ms_entries, dim3(ms_blocks((size_t)K)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, (const unsigned*)flag, (const unsigned*)scan, K, S.hb,
+        hipLaunchKernelGGL(k_ms_entries, dim3(blocks_for((size_t)K)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, (const unsigned*)flag, (const unsigned*)scan, K, S.hb,
                            S.head_pos, S.col);
         HIP_TRY(hipGetLastError());
     }
@@ -94,10 +91,10 @@ static int mesh_adjacency_impl(pcu_hip_ctx* c, const void* f, int64_t nf, int f_
         if (ms_faces(ar, s, f, nf, f_kind, nv, on_dev, S)) return -1;
         if (int rc = ms_adjacency(ar, s, nf, nv, S)) return rc;
         tm.mark(1);
-        char *d_off = nullptr, *d_nbr = nullptr;
-        if (park_reserve(c, (NV + 1) * 8, (size_t)S.ne * kb, &d_off, &d_nbr)) return -1;
-        hipLaunchKernelGGL(k_ms_adj_out, dim3(ms_blocks(std::max(NV + 1, (size_t)S.ne))), dim3(kBlock), 0, s, (const unsigned*)S.off, (int)nv, (const int*)S.col, S.ne, f_kind,
-                           reinterpret_cast<long long*>(d_off), (void*)d_nbr);
+        char* seg[kParkSegs];
+        if (park_reserve(c, {(NV + 1) * 8, (size_t)S.ne * kb}, seg)) return -1;
+        hipLaunchKernelGGL(k_ms_adj_out, dim3(blocks_for(std::max(NV + 1, (size_t)S.ne))), dim3(kBlock), 0, s, (const unsigned*)S.off, (int)nv, (const int*)S.col, S.ne, f_kind,
+                           reinterpret_cast<long long*>(seg[0]), (void*)seg[1]);
         HIP_TRY(hipGetLastError());
         tm.mark(2);
         HIP_WAIT(s);
@@ -110,7 +107,7 @@ static int mesh_adjacency_impl(pcu_hip_ctx* c, const void* f, int64_t nf, int f_
 // The result of this context's last pcu_hip_mesh_adjacency. Once.
 static int mesh_adjacency_take_impl(pcu_hip_ctx* c, int64_t nv, int64_t count, int64_t* out_offsets, void* out_neighbours, unsigned flags, void* stream) {
     if (!c || !out_offsets || (!out_neighbours && count > 0)) return fail(PCU_HIP_ERR_INVALID, "null context / out_offsets / out_neighbours");
-    return park_take(c, Parked::Adjacency, nv, count, out_offsets, out_neighbours, flags, stream,
+    return park_take(c, Parked::Adjacency, nv, count, {out_offsets, out_neighbours}, flags, stream,
                      "pcu_hip_mesh_adjacency_take: this context holds no adjacency of %lld vertices and %lld entries");
 }
 
@@ -131,22 +128,20 @@ static int mesh_vertex_normals_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int w
         const T* dv = nullptr;
         tm.mark(0);
         if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || ms_faces(ar, s, m.f, m.nf, m.f_kind, m.nv, on_dev, S)) return -1;
-        hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3(ms_blocks(NV * 3)), dim3(kBlock), 0, s, dv, (long long)NV * 3, S.d_bad, kMeshBadVertex);
+        hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3(blocks_for(NV * 3)), dim3(kBlock), 0, s, dv, (long long)NV * 3, S.d_bad, kMeshBadVertex);
         if (ms_incidence(ar, s, m.nf, m.nv, S)) return -1;
         tm.mark(1);
-        T *fn = nullptr, *ang = nullptr, *d_n = out_n;
-        if (aalloc(ar, &fn, NF * 3) || (weighting == 2 && aalloc(ar, &ang, NF * 3)) || (!on_dev && aalloc(ar, &d_n, NV * 3))) return -1;
-        hipLaunchKernelGGL(k_ms_face_vec<T>, dim3(ms_blocks(NF)), dim3(kBlock), 0, s, dv, (const int*)S.fidx, (int)m.nf, weighting, fn, ang);
-        hipLaunchKernelGGL(k_ms_vnormals<T>, dim3(ms_blocks(NV)), dim3(kBlock), 0, s, (const unsigned*)S.inc_pos, (const unsigned*)S.inc_ids, (const T*)fn, (const T*)ang,
+        T *fn = nullptr, *ang = nullptr, *d_n = nullptr;
+        if (aalloc(ar, &fn, NF * 3) || (weighting == 2 && aalloc(ar, &ang, NF * 3)) || out_room(ar, on_dev, out_n, NV * 3, &d_n)) return -1;
+        hipLaunchKernelGGL(k_ms_face_vec<T>, dim3(blocks_for(NF)), dim3(kBlock), 0, s, dv, (const int*)S.fidx, (int)m.nf, weighting, fn, ang);
+        hipLaunchKernelGGL(k_ms_vnormals<T>, dim3(blocks_for(NV)), dim3(kBlock), 0, s, (const unsigned*)S.inc_pos, (const unsigned*)S.inc_ids, (const T*)fn, (const T*)ang,
                            weighting, (int)m.nv, d_n, S.d_bad);
         HIP_TRY(hipGetLastError());
         tm.mark(2);
         int bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, S.d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-        if (!on_dev) HIP_TRY(hipMemcpyAsync(out_n, d_n, NV * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+        if (flag_fetch(s, S.d_bad, &bad) || out_give(s, on_dev, out_n, d_n, NV * 3)) return -1;
         HIP_WAIT(s);
-        if (bad & kMeshBadVertex) return fail(PCU_HIP_ERR_INVALID, "v must not contain NaN or infinite coordinates");
-        if (bad & kMeshBadFace) return fail(PCU_HIP_ERR_INVALID, "f must hold row indices of v: found a face index outside [0, %lld)", (long long)m.nv);
+        if (int rc = mesh_refusal(bad, m.nv)) return rc;
         if (bad & kMeshBadNormal) return fail(PCU_HIP_ERR_INVALID, "vertex normals overflow the scalar type of v");
         if (st) { st->n_queries = m.nv; st->n_passes = 1; st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_total = tm.span(0, 2); }
         return 0;
@@ -160,7 +155,7 @@ struct MsSolve {
 };
 template <typename T>
 static int ms_solve(hipStream_t s, const MsSolve<T>& q, T* x) {
-    const unsigned nb = ms_blocks((size_t)q.nv);
+    const unsigned nb = blocks_for((size_t)q.nv);
     hipLaunchKernelGGL(k_ms_cg_init<T>, dim3(nb), dim3(kBlock), 0, s, q.off, q.col, q.val, q.diag, (const T*)q.M, q.h, (const T*)x, q.nv, q.b, q.D, q.r, q.z, q.p, q.part);
     hipLaunchKernelGGL(k_ms_cg_fold_init<T>, dim3(1), dim3(kBlock), 0, s, (const T*)q.part, (int)nb, q.cg);
     int seen[2] = {0, 0};           // flag, iters
@@ -195,7 +190,7 @@ static int laplacian_smooth_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int num_
     if (!(step_size >= 0.0) || !std::isfinite(step_size)) return fail(PCU_HIP_ERR_INVALID, "step_size must be finite and not negative");
     if (!m.v || !m.f || !out) return fail(PCU_HIP_ERR_INVALID, "null v / f / out");
     const bool on_dev = flags & PCU_HIP_PTRS_ON_DEVICE;
-    const size_t NV = (size_t)m.nv, NF = (size_t)m.nf, nb = ms_blocks(NV), nbf = ms_blocks(NF);
+    const size_t NV = (size_t)m.nv, NF = (size_t)m.nf, nb = blocks_for(NV), nbf = blocks_for(NF);
     size_t bytes = ms_incidence_bytes(NV, NF) + align_up(NF * 24, 256) + ms_adjacency_bytes(NV, NF) + align_up(NF * 3 * sizeof(T), 256) + align_up(NF * 6 * sizeof(T), 256) +
                    align_up(NF * sizeof(T), 256) + 7 * align_up(NV * 3 * sizeof(T), 256) + 3 * align_up(NV * sizeof(T), 256) +
                    align_up(std::max(nb * kMsFoldMax, nbf * 4) * sizeof(T), 256) + 16384;
@@ -206,12 +201,12 @@ static int laplacian_smooth_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int num_
         const T* dv = nullptr;
         tm.mark(0);
         if (stage_in(ar, m.v, m.nv, on_dev, s, &dv) || ms_faces(ar, s, m.f, m.nf, m.f_kind, m.nv, on_dev, S)) return -1;
-        hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3(ms_blocks(NV * 3)), dim3(kBlock), 0, s, dv, (long long)NV * 3, S.d_bad, kMeshBadVertex);
+        hipLaunchKernelGGL(k_mesh_vcheck<T>, dim3(blocks_for(NV * 3)), dim3(kBlock), 0, s, dv, (long long)NV * 3, S.d_bad, kMeshBadVertex);
         if (ms_incidence(ar, s, m.nf, m.nv, S)) return -1;
         if (int rc = ms_adjacency(ar, s, m.nf, m.nv, S)) return rc;
         tm.mark(1);
-        T* u = out;
-        if (!on_dev && aalloc(ar, &u, NV * 3)) return -1;
+        T* u = nullptr;
+        if (out_room(ar, on_dev, out, NV * 3, &u)) return -1;
         if (u != dv) HIP_TRY(hipMemcpyAsync(u, dv, NV * 3 * sizeof(T), hipMemcpyDeviceToDevice, s));
         int iters = 0;
         if (num_iters > 0) {
@@ -221,9 +216,9 @@ static int laplacian_smooth_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int num_
                 aalloc(ar, &q.r, NV * 3) || aalloc(ar, &q.z, NV * 3) || aalloc(ar, &q.p, NV * 3) || aalloc(ar, &q.Ap, NV * 3) ||
                 aalloc(ar, &q.part, std::max(nb * kMsFoldMax, nbf * 4)) || aalloc(ar, &q.cg, 1) || (use_cotan && (aalloc(ar, &len, NF) || aalloc(ar, &ac, 4)))) return -1;
             HIP_TRY(hipMemsetAsync(q.cg, 0, sizeof(MsCg<T>), s));
-            hipLaunchKernelGGL(k_ms_corner_w<T>, dim3(ms_blocks(NF * 3)), dim3(kBlock), 0, s, dv, (const int*)S.fidx, (int)(3 * m.nf), w);
+            hipLaunchKernelGGL(k_ms_corner_w<T>, dim3(blocks_for(NF * 3)), dim3(kBlock), 0, s, dv, (const int*)S.fidx, (int)(3 * m.nf), w);
             if (S.ne > 0)
-                hipLaunchKernelGGL(k_ms_run_sums<T>, dim3(ms_blocks((size_t)S.ne)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, (const unsigned*)S.pids, S.K,
+                hipLaunchKernelGGL(k_ms_run_sums<T>, dim3(blocks_for((size_t)S.ne)), dim3(kBlock), 0, s, (const unsigned long long*)S.pkeys, (const unsigned*)S.pids, S.K,
                                    (const unsigned*)S.head_pos, S.ne, (const T*)w, val);
             hipLaunchKernelGGL(k_ms_diag<T>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const unsigned*)S.off, (const T*)val, (int)m.nv, diag);
             if (!use_cotan) hipLaunchKernelGGL(k_ms_fill<T>, dim3((unsigned)nb), dim3(kBlock), 0, s, q.M, (int)m.nv, (T)1);
@@ -249,7 +244,7 @@ static int laplacian_smooth_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, int num_
             tm.mark(2);
         }
         tm.mark(3);
-        if (!on_dev) HIP_TRY(hipMemcpyAsync(out, u, NV * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+        if (out_give(s, on_dev, out, u, NV * 3)) return -1;
         HIP_WAIT(s);
         if (st) {
             st->n_queries = m.nv; st->n_escalated = (int64_t)S.ne; st->n_passes = iters;

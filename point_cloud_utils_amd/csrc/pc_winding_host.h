@@ -39,8 +39,8 @@ static int pc_build(Arena& ari, Arena& ar, hipStream_t s, const T* p, const T* n
     if (aalloc(ari, &M.head, 1) || aalloc(ari, &M.tri, (size_t)np * 6) || aalloc(ari, &M.box, (size_t)M.P * 12) || aalloc(ari, &M.ctr, (size_t)M.P * 8) ||
         aalloc(ari, &M.mom, (size_t)M.P * 60) || aalloc(ar, &weight, (size_t)M.P * 2) ||
         aalloc(ar, &ka, (size_t)np) || aalloc(ar, &kb, (size_t)np) || aalloc(ar, &ia, (size_t)np) || aalloc(ar, &ib, (size_t)np)) return -1;
-    const int nbp = (int)((np + kBlock - 1) / kBlock), nbl = (M.P + kBlock - 1) / kBlock;
-    int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
+    const unsigned nbp = blocks_for((size_t)np), nbl = blocks_for((size_t)M.P);
+    int* d_bad = mesh_head_flag(M.head);
     hipLaunchKernelGGL(k_mesh_head_init<T>, dim3(1), dim3(64), 0, s, M.head);
     hipLaunchKernelGGL(k_pc_check<T>, dim3(nbp), dim3(kBlock), 0, s, dp, dn, da, (int)np, M.head);
     hipLaunchKernelGGL(k_mesh_frame<T>, dim3(1), dim3(64), 0, s, M.head);
@@ -49,13 +49,13 @@ static int pc_build(Arena& ari, Arena& ar, hipStream_t s, const T* p, const T* n
     if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)np, 63)) return -1;
     hipLaunchKernelGGL(k_pc_gather<T>, dim3(nbp), dim3(kBlock), 0, s, dp, dn, da, (const unsigned*)ia, (int)np, M.tri, d_bad);
     hipLaunchKernelGGL(k_pc_leaves<T>, dim3(nbl), dim3(kBlock), 0, s, (const T*)M.tri, (int)np, M.P, M.box);
-    for (int m = M.P / 2; m >= 1; m /= 2) hipLaunchKernelGGL(k_mesh_refit<T>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, M.box, m);
+    for (int m = M.P / 2; m >= 1; m /= 2) hipLaunchKernelGGL(k_mesh_refit<T>, dim3(blocks_for((size_t)m)), dim3(kBlock), 0, s, M.box, m);
     hipLaunchKernelGGL(k_pc_mleaves<T>, dim3(nbl), dim3(kBlock), 0, s, (const T*)M.tri, (int)np, M.P, (const T*)M.box, M.ctr, M.mom, weight);
     for (int m = M.P / 2; m >= 1; m /= 2)
-        hipLaunchKernelGGL(k_mesh_mrefit<T>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const T*)M.box, M.ctr, M.mom, weight, m);
+        hipLaunchKernelGGL(k_mesh_mrefit<T>, dim3(blocks_for((size_t)m)), dim3(kBlock), 0, s, (const T*)M.box, M.ctr, M.mom, weight, m);
     HIP_TRY(hipGetLastError());
     int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (flag_fetch(s, d_bad, &bad)) return -1;
     HIP_WAIT(s);
     if (bad & kPcBadP) return fail(PCU_HIP_ERR_INVALID, "p must not contain NaN or infinite coordinates");
     if (bad & kPcBadN) return fail(PCU_HIP_ERR_INVALID, "n must not contain NaN or infinite coordinates");
@@ -117,13 +117,11 @@ static int mesh_face_normals_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, T* out_
         auto& [c, s, on_dev, ar, tm] = fr;
         MsMesh<T> M; MsSeen<T> seen;
         if (ms_mesh_stage<T>(ar, s, m, on_dev, M)) return -1;
-        T* d_n = out_n;
-        if (!on_dev && aalloc(ar, &d_n, (size_t)m.nf * 3)) return -1;
-        int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
-        hipLaunchKernelGGL(k_mesh_fnormals<T>, dim3((unsigned)((m.nf + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, M.v, (const int*)M.fidx, (int)m.nf, d_n, d_bad);
+        T* d_n = nullptr;
+        if (out_room(ar, on_dev, out_n, (size_t)m.nf * 3, &d_n)) return -1;
+        hipLaunchKernelGGL(k_mesh_fnormals<T>, dim3(blocks_for((size_t)m.nf)), dim3(kBlock), 0, s, M.v, (const int*)M.fidx, (int)m.nf, d_n, mesh_head_flag(M.head));
         HIP_TRY(hipGetLastError());
-        if (ms_mesh_readback(s, M, false, &seen)) return -1;
-        if (!on_dev) HIP_TRY(hipMemcpyAsync(out_n, d_n, (size_t)m.nf * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
+        if (ms_mesh_readback(s, M, false, &seen) || out_give(s, on_dev, out_n, d_n, (size_t)m.nf * 3)) return -1;
         HIP_WAIT(s);
         if (int rc = ms_mesh_refuse(seen, m.nv, false)) return rc;
         if (seen.bad & kMeshBadNormal) return fail(PCU_HIP_ERR_INVALID, "face normals overflow the scalar type of v");

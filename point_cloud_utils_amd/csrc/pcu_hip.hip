@@ -215,10 +215,11 @@ struct ArenaState {
     std::vector<void*> extra;                 // overflow allocations (of the current call)
     size_t extra_bytes = 0;
 };
-// A result whose size the caller learns from the call that made it waits in the context's `aux` block, as two segments (the second one
-// 256-aligned behind the first), for the _take call that repeats its two counts. One record: a context holds at most one such result.
+// A result whose size the caller learns from the call that made it waits in the context's `aux` block, as up to four segments (each one
+// 256-aligned behind the one before), for the _take call that repeats its two counts. One record: a context holds at most one such result.
 enum class Parked { None, VoxelRows, Surface, HexMesh, Adjacency, Decimated, RadiusRows };
-struct ParkedResult { Parked kind = Parked::None; int64_t n0 = 0, n1 = 0; size_t bytes0 = 0, bytes1 = 0; };
+constexpr int kParkSegs = 4;
+struct ParkedResult { Parked kind = Parked::None; int64_t n0 = 0, n1 = 0; size_t bytes[kParkSegs] = {0, 0, 0, 0}; };
 struct pcu_hip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -1404,6 +1405,48 @@ static int op_run(pcu_hip_ctx* c, unsigned flags, void* stream, pcu_hip_stats* s
     OpFrame fr{c, s, (flags & PCU_HIP_PTRS_ON_DEVICE) != 0, Arena{c}, Timer{c, s, st}};
     return attempt_exit(c, body(fr));
 }
+// The way out of an operator, in the argument order of stage_any. out_room: the device-side room for an output of `count` elements -- the
+// caller's own pointer when the call's pointers are device memory, room in the arena otherwise. out_give: `count` elements of it go back to
+// the caller -- nothing where the kernels wrote to the caller's pointer, else one copy on the call's stream, not waited for (device to
+// device for a result that was built in the workspace of a call with device pointers).
+template <typename U>
+static int out_room(Arena& ar, bool on_dev, U* given, size_t count, U** room) {
+    if (on_dev) { *room = given; return 0; }
+    return aalloc(ar, room, count);
+}
+template <typename U>
+static int out_give(hipStream_t s, bool on_dev, U* out, const U* room, size_t count, bool* copied = nullptr) {
+    if (room == out || count == 0) return 0;
+    HIP_TRY(hipMemcpyAsync(out, room, count * sizeof(U), on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (copied) *copied = true;             // (for a call that has waited already and has to wait again only for this copy)
+    return 0;
+}
+// The integer types of faces, cubes and grid coordinates: PCU_HIP_FACE_INT32 / INT64 / UINT32 / UINT64 (on the device: index_kinds.h);
+// stage_ints: `count` of them on the device; stage_faces: nf x 3 (faces, or any rows of three).
+static int int_kind_bytes(int kind) { return (kind == 0 || kind == 2) ? 4 : 8; }
+static int stage_ints(Arena& ar, const void* p, size_t count, int kind, bool on_dev, hipStream_t s, const char** out) {
+    return stage_any(ar, static_cast<const char*>(p), count * (size_t)int_kind_bytes(kind), on_dev, s, out);
+}
+static int stage_faces(Arena& ar, const void* f, size_t nf, int kind, bool on_dev, hipStream_t s, const char** out) { return stage_ints(ar, f, nf * 3, kind, on_dev, s, out); }
+// The flag word of an operator: kernels raise bits in it, the host reads it with the first counts it waits for and refuses the call before
+// anything is written to an output. kMeshBadVertex and kMeshBadFace (index_kinds.h) mean the same in every operator and have one text each
+// (mesh_refusal: the vertex text first); an operator's own bits lie above them. flag_word: a zeroed word (the first of `words` ints) in the
+// arena. mesh_head_flag: the word inside a tree's head. flag_fetch: its copy to the host, enqueued, not waited for.
+static int flag_word(Arena& ar, hipStream_t s, int** d_bad, size_t words = 1) {
+    if (aalloc(ar, d_bad, words)) return -1;
+    HIP_TRY(hipMemsetAsync(*d_bad, 0, sizeof(int), s));
+    return 0;
+}
+template <typename T> static int* mesh_head_flag(MeshHead<T>* head) { return &head->bad; }      // (an address on the device: computed, not read)
+static int flag_fetch(hipStream_t s, const int* d_bad, int* bad) {
+    HIP_TRY(hipMemcpyAsync(bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+static int mesh_refusal(int bad, int64_t nv) {
+    if (bad & kMeshBadVertex) return fail(PCU_HIP_ERR_INVALID, "v must not contain NaN or infinite coordinates");
+    if (bad & kMeshBadFace) return fail(PCU_HIP_ERR_INVALID, "f must hold row indices of v: found a face index outside [0, %lld)", (long long)nv);
+    return 0;
+}
 
 // ------------------------------------------------------------------------------------------------ knn
 // A dataset kept on the GPU together with its grid index (pcu_hip_index_*): memory owned by the object, not by a call's arena.
@@ -2245,25 +2288,30 @@ static int aux_reserve(pcu_hip_ctx* c, size_t bytes) {
     }
     return 0;
 }
-// Parking a result: reserve its two segments, have them written and waited for, commit. Nothing is parked in between. work / wk: that many
-// bytes more behind the segments, for the call that makes the result.
-static int park_reserve(pcu_hip_ctx* c, size_t bytes0, size_t bytes1, char** seg0, char** seg1, size_t work = 0, char** wk = nullptr) {
-    if (aux_reserve(c, align_up(bytes0, 256) + align_up(bytes1, 256) + work + 256)) return -1;
-    c->parked.bytes0 = bytes0; c->parked.bytes1 = bytes1;
-    *seg0 = c->aux; *seg1 = c->aux + align_up(bytes0, 256);
-    if (wk) *wk = *seg1 + align_up(bytes1, 256);
+// Parking a result: reserve its segments (byte counts in, pointers out; a result of fewer than four leaves the rest 0), have them written
+// and waited for, commit. Nothing is parked in between. work / wk: that many bytes more behind the segments, for the call that makes the result.
+static int park_reserve(pcu_hip_ctx* c, const size_t (&bytes)[kParkSegs], char* (&seg)[kParkSegs], size_t work = 0, char** wk = nullptr) {
+    size_t total = work + 256;
+    for (size_t b : bytes) total += align_up(b, 256);
+    if (aux_reserve(c, total)) return -1;
+    char* p = c->aux;
+    for (int i = 0; i < kParkSegs; ++i) { c->parked.bytes[i] = bytes[i]; seg[i] = p; p += align_up(bytes[i], 256); }
+    if (wk) *wk = p;
     return 0;
 }
 static void park_commit(pcu_hip_ctx* c, Parked kind, int64_t n0, int64_t n1) { c->parked.kind = kind; c->parked.n0 = n0; c->parked.n1 = n1; }
-// The parked result goes to out0 / out1, once, and only to the call that names its kind and both counts (`refusal`: the operator's text
-// with the two counts as %lld). A cancelled copy leaves it where it is: the call can be issued again.
-static int park_take(pcu_hip_ctx* c, Parked kind, int64_t n0, int64_t n1, void* out0, void* out1, unsigned flags, void* stream, const char* refusal) {
+// The parked result goes to out[], segment by segment, once, and only to the call that names its kind and both counts (`refusal`: the
+// operator's text with the two counts as %lld). A cancelled copy leaves it where it is: the call can be issued again.
+static int park_take(pcu_hip_ctx* c, Parked kind, int64_t n0, int64_t n1, void* const (&out)[kParkSegs], unsigned flags, void* stream, const char* refusal) {
     const ParkedResult& p = c->parked;
     if (p.kind != kind || n0 != p.n0 || n1 != p.n1) return fail(PCU_HIP_ERR_INVALID, refusal, (long long)n0, (long long)n1);
     hipStream_t s = pick_stream(c, flags, stream);
     const hipMemcpyKind dir = (flags & PCU_HIP_PTRS_ON_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (p.bytes0) HIP_TRY(hipMemcpyAsync(out0, c->aux, p.bytes0, dir, s));
-    if (p.bytes1) HIP_TRY(hipMemcpyAsync(out1, c->aux + align_up(p.bytes0, 256), p.bytes1, dir, s));
+    const char* seg = c->aux;
+    for (int i = 0; i < kParkSegs; ++i) {
+        if (p.bytes[i]) HIP_TRY(hipMemcpyAsync(out[i], seg, p.bytes[i], dir, s));
+        seg += align_up(p.bytes[i], 256);
+    }
     HIP_WAIT(s);
     c->parked = ParkedResult();
     return 0;

@@ -31,7 +31,7 @@ static int pd_run(PdRun<T>& R, T r, hipStream_t s, int64_t* count) {
     // cells at least r wide (slightly more: the reach of a close pair includes rounding), capped where the grid arithmetic stays finite
     const double hcap = sizeof(T) == 4 ? 1e30 : 1e300;
     if (pd_build<T>(R, std::min((double)r * 1.01, hcap), s, nullptr)) return -1;
-    const int n = R.gi.n, nb = (n + kBlock - 1) / kBlock;
+    const int n = R.gi.n, nb = blocks_for((size_t)n);
     PdArgs<T>& a = R.a;
     a.gp = R.gi.gp; a.sorted = R.gi.sorted; a.cell_start = R.gi.cell_start;
     a.r2 = r * r;
@@ -86,7 +86,7 @@ template <typename T>
 static int pd_body(Arena& ar, hipStream_t s, const T* d_pts, int64_t n, double radius, int64_t target, unsigned seed, float tol, int32_t* d_out,
                    int64_t* count, PdRun<T>& R) {
     const size_t N = (size_t)n;
-    const int nb = (int)((n + kBlock - 1) / kBlock);
+    const int nb = blocks_for((size_t)n);
     if (target > 0 && target >= n) {                           // :275-279
         hipLaunchKernelGGL(k_pd_iota, dim3(nb), dim3(kBlock), 0, s, (int)n, d_out);
         HIP_TRY(hipGetLastError());
@@ -165,11 +165,11 @@ static int poisson_disk_impl(pcu_hip_ctx* c, const T* pts, int64_t n, double rad
         PdRun<T> R;
         const T* d_pts = nullptr;
         if (!all_rows) if (int rc = stage_in(ar, pts, n, on_dev, s, &d_pts)) return rc;
-        int32_t* d_out = out_idx;
-        if (!on_dev) if (int rc = aalloc(ar, &d_out, N)) return rc;
+        int32_t* d_out = nullptr;
+        if (int rc = out_room(ar, on_dev, out_idx, N, &d_out)) return rc;
         int64_t cnt = 0;
         if (int rc = pd_body<T>(ar, s, d_pts, n, radius, target, seed, tol, d_out, &cnt, R)) return rc;
-        if (!on_dev && cnt > 0) HIP_TRY(hipMemcpyAsync(out_idx, d_out, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
+        if (out_give(s, on_dev, out_idx, d_out, (size_t)cnt)) return -1;
         HIP_WAIT(s);
         *out_count = cnt;
         if (st && !all_rows) { st->n_queries = n; st->n_passes = R.rounds; st->n_grid_builds = R.radii; }

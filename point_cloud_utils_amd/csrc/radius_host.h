@@ -5,7 +5,6 @@
 constexpr double kRadOcc = 4.0;                         // the free functions' grid: cells of about the radius, no finer than this many points per cell
 constexpr unsigned long long kRadMaxTotal = 1ull << 31; // a result holds fewer neighbours than this: positions inside it fit 32 bits
 
-static unsigned rad_blocks(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 // What a call takes from the arena beside its dataset (DatasetFrame::bytes).
 template <typename T>
@@ -30,12 +29,12 @@ static int radius_sort_long(Arena& ar, hipStream_t s, const unsigned* long_len, 
     bool identity = true;
     for (int stage = 0; stage < 3; ++stage) {
         if (!bits[stage]) continue;
-        hipLaunchKernelGGL(k_radius_long_key<T>, dim3(rad_blocks(nl)), dim3(kBlock), 0, s, L, identity ? (const unsigned*)nullptr : (const unsigned*)ia, stage, (const T*)d2, (const int*)row, ka);
+        hipLaunchKernelGGL(k_radius_long_key<T>, dim3(blocks_for(nl)), dim3(kBlock), 0, s, L, identity ? (const unsigned*)nullptr : (const unsigned*)ia, stage, (const T*)d2, (const int*)row, ka);
         if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, identity, (int)nl, bits[stage])) return -1;
         identity = false;
     }
-    hipLaunchKernelGGL(k_radius_long_move<T>, dim3(rad_blocks(nl)), dim3(kBlock), 0, s, L, identity ? (const unsigned*)nullptr : (const unsigned*)ia, 0, d2, row, td, tr);
-    hipLaunchKernelGGL(k_radius_long_move<T>, dim3(rad_blocks(nl)), dim3(kBlock), 0, s, L, (const unsigned*)nullptr, 1, d2, row, td, tr);
+    hipLaunchKernelGGL(k_radius_long_move<T>, dim3(blocks_for(nl)), dim3(kBlock), 0, s, L, identity ? (const unsigned*)nullptr : (const unsigned*)ia, 0, d2, row, td, tr);
+    hipLaunchKernelGGL(k_radius_long_move<T>, dim3(blocks_for(nl)), dim3(kBlock), 0, s, L, (const unsigned*)nullptr, 1, d2, row, td, tr);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -67,16 +66,16 @@ static int radius_impl(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         // the records of every cell in ascending row order: the walk's order is then a function of the input (normals.h: k_cells_by_row)
         Pt4<T>* by_row = nullptr;
         if (aalloc(ar, &by_row, (size_t)nr)) return -1;
-        hipLaunchKernelGGL(k_cells_by_row<T>, dim3(rad_blocks((size_t)nr)), dim3(kBlock), 0, s, gi.gp, gi.sorted, gi.cell_start, (int)nr, by_row);
+        hipLaunchKernelGGL(k_cells_by_row<T>, dim3(blocks_for((size_t)nr)), dim3(kBlock), 0, s, gi.gp, gi.sorted, gi.cell_start, (int)nr, by_row);
         // the queries in the cell order of the dataset's grid (a stable sort of their cell keys: equal cells keep the caller's order)
         unsigned long long *ka = nullptr, *kb = nullptr; unsigned *ia = nullptr, *ib = nullptr, *counts = nullptr;
         if (aalloc(ar, &ka, (size_t)nq) || aalloc(ar, &kb, (size_t)nq) || aalloc(ar, &ia, (size_t)nq) || aalloc(ar, &ib, (size_t)nq) || aalloc(ar, &counts, (size_t)nq)) return -1;
-        hipLaunchKernelGGL(k_radius_qkeys<T>, dim3(rad_blocks((size_t)nq)), dim3(kBlock), 0, s, gi.gp, dq, (int)nq, ka);
+        hipLaunchKernelGGL(k_radius_qkeys<T>, dim3(blocks_for((size_t)nq)), dim3(kBlock), 0, s, gi.gp, dq, (int)nq, ka);
         if (own_radix_sort(ar, s, &ka, &kb, &ia, &ib, /*ids_identity=*/true, (int)nq, std::max(1, bits_of((unsigned long long)gi.max_cells)))) return -1;
         RadiusArgs<T> a{};
         a.gp = gi.gp; a.by_row = by_row; a.cell_start = gi.cell_start; a.nr = (int)nr; a.query = dq; a.order = ia; a.nq = (int)nq; a.r2 = r2; a.reach = reach; a.counts = counts;
         a.cancel_word = g_cancel_mirror.load(std::memory_order_relaxed); a.cancel_gen = t_call_gen;
-        const unsigned walk_blocks = (unsigned)((nq + kBlock - 1) / kBlock);           // a wave per 64 queries
+        const unsigned walk_blocks = blocks_for((size_t)nq);           // a wave per 64 queries
         tm.mark(1);
         hipLaunchKernelGGL((k_radius_walk<T, false>), dim3(walk_blocks), dim3(kBlock), 0, s, a);
         HIP_TRY(hipGetLastError());
@@ -85,12 +84,13 @@ static int radius_impl(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         int nf = 0;
         if (!pidx) if (int rc = nonfinite_fetch(gi.gp, &nf, s)) return rc;
         if (st) { st->n_grid_builds = ds.built; st->n_queries = nq; st->n_passes = 1; }
+        long long* const h_out = reinterpret_cast<long long*>(out);
         if (count_only) {
-            long long* d_out = reinterpret_cast<long long*>(out);
-            if (!on_dev && aalloc(ar, &d_out, (size_t)nq)) return -1;
-            hipLaunchKernelGGL(k_radius_counts_out, dim3(rad_blocks((size_t)nq)), dim3(kBlock), 0, s, (const unsigned*)counts, (int)nq, d_out);
+            long long* d_out = nullptr;
+            if (out_room(ar, on_dev, h_out, (size_t)nq, &d_out)) return -1;
+            hipLaunchKernelGGL(k_radius_counts_out, dim3(blocks_for((size_t)nq)), dim3(kBlock), 0, s, (const unsigned*)counts, (int)nq, d_out);
             HIP_TRY(hipGetLastError());
-            if (!on_dev) HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
+            if (out_give(s, on_dev, h_out, d_out, (size_t)nq)) return -1;
             HIP_WAIT(s);
             if (nf & (kNfNaN | kNfBothInf)) return nonfinite_error(false);
             if (st) { st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_total = tm.span(0, 2); }
@@ -100,7 +100,7 @@ static int radius_impl(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         if (aalloc(ar, &len64, (size_t)nq) || aalloc(ar, &offs, (size_t)nq + 1) || aalloc(ar, &mid_list, (size_t)nq) || aalloc(ar, &long_len, (size_t)nq) || aalloc(ar, &tally, 4)) return -1;
         HIP_TRY(hipMemsetAsync(tally, 0, 16, s));
         HIP_TRY(hipMemsetAsync(offs, 0, 8, s));
-        hipLaunchKernelGGL(k_radius_lengths, dim3(rad_blocks((size_t)nq)), dim3(kBlock), 0, s, (const unsigned*)counts, (int)nq, len64, mid_list, long_len, tally);
+        hipLaunchKernelGGL(k_radius_lengths, dim3(blocks_for((size_t)nq)), dim3(kBlock), 0, s, (const unsigned*)counts, (int)nq, len64, mid_list, long_len, tally);
         if (own_inclusive_scan<unsigned long long>(ar, s, len64, offs + 1, (size_t)nq)) return -1;
         unsigned long long total = 0; unsigned tiers[2] = {0, 0};
         HIP_TRY(hipMemcpyAsync(&total, offs + nq, 8, hipMemcpyDeviceToHost, s));
@@ -111,9 +111,9 @@ static int radius_impl(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
             return fail(PCU_HIP_ERR_INVALID, "radius_search: the result would hold %llu neighbours; one call returns at most 2147483647 (2^31 - 1). Use a smaller radius or "
                         "fewer queries per call (radius_count has no such limit).", total);
         // the result's segments -- indices, and the distances, which hold d2 until the rows leave -- and the members' rows behind them
-        char *seg0 = nullptr, *seg1 = nullptr, *wk = nullptr;
-        if (park_reserve(c, (size_t)total * 8, (size_t)total * sizeof(T), &seg0, &seg1, (size_t)total * 4, &wk)) return -1;
-        T* d2 = reinterpret_cast<T*>(seg1); int* row = reinterpret_cast<int*>(wk);
+        char *seg[kParkSegs], *wk = nullptr;
+        if (park_reserve(c, {(size_t)total * 8, (size_t)total * sizeof(T)}, seg, (size_t)total * 4, &wk)) return -1;
+        T* d2 = reinterpret_cast<T*>(seg[1]); int* row = reinterpret_cast<int*>(wk);
         if (total > 0) {
             a.offsets = offs; a.d2 = d2; a.row = row;
             hipLaunchKernelGGL((k_radius_walk<T, true>), dim3(walk_blocks), dim3(kBlock), 0, s, a);
@@ -128,10 +128,10 @@ static int radius_impl(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
         }
         tm.mark(4);
         if (total > 0)
-            hipLaunchKernelGGL(k_radius_out<T>, dim3(rad_blocks((size_t)total)), dim3(kBlock), 0, s, (const T*)d2, (const int*)row, total, (flags & PCU_HIP_SQUARED) ? 1 : 0,
-                               reinterpret_cast<long long*>(seg0), d2);
+            hipLaunchKernelGGL(k_radius_out<T>, dim3(blocks_for((size_t)total)), dim3(kBlock), 0, s, (const T*)d2, (const int*)row, total, (flags & PCU_HIP_SQUARED) ? 1 : 0,
+                               reinterpret_cast<long long*>(seg[0]), d2);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, offs, ((size_t)nq + 1) * 8, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        if (out_give(s, on_dev, h_out, reinterpret_cast<const long long*>(offs), (size_t)nq + 1)) return -1;
         HIP_WAIT(s);
         park_commit(c, Parked::RadiusRows, nq, (int64_t)total);
         *out_total = (int64_t)total;
@@ -145,6 +145,6 @@ static int radius_impl(pcu_hip_ctx* c, const T* query, int64_t nq, const T* data
 // The rows of this context's last pcu_hip_radius_search_* / pcu_hip_index_radius_search_*. Once.
 static int radius_take_impl(pcu_hip_ctx* c, int64_t nq, int64_t total, int64_t* out_idx, void* out_d, unsigned flags, void* stream) {
     if (!c || ((!out_idx || !out_d) && total > 0)) return fail(PCU_HIP_ERR_INVALID, "null context / out_indices / out_dists");
-    return park_take(c, Parked::RadiusRows, nq, total, out_idx, out_d, flags, stream,
+    return park_take(c, Parked::RadiusRows, nq, total, {out_idx, out_d}, flags, stream,
                      "pcu_hip_radius_search_take: this context holds no radius result of %lld queries and %lld neighbours");
 }

@@ -65,8 +65,8 @@ static int surfel_build(Arena& ari, Arena& ar, hipStream_t s, const T* p, const 
     if (aalloc(ari, &M.head, 1) || surfel_table<T>(ari, s, subdivs, table) || aalloc(ari, &M.tri, (size_t)np * 9) || aalloc(ari, &M.face, (size_t)np) ||
         aalloc(ari, &M.box, (size_t)M.P * 12) ||
         aalloc(ar, &ka, (size_t)np) || aalloc(ar, &kb, (size_t)np) || aalloc(ar, &ia, (size_t)np) || aalloc(ar, &ib, (size_t)np)) return -1;
-    const int nbp = (int)((np + kBlock - 1) / kBlock), nbl = (M.P + kBlock - 1) / kBlock;
-    int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
+    const unsigned nbp = blocks_for((size_t)np), nbl = blocks_for((size_t)M.P);
+    int* d_bad = mesh_head_flag(M.head);
     hipLaunchKernelGGL(k_mesh_head_init<T>, dim3(1), dim3(64), 0, s, M.head);
     if (np > 0) hipLaunchKernelGGL(k_surfel_check<T>, dim3(nbp), dim3(kBlock), 0, s, dp, dn, dr, (int)np, subdivs, *table, M.head);
     else hipLaunchKernelGGL(k_surfel_head_empty<T>, dim3(1), dim3(64), 0, s, M.head);
@@ -79,10 +79,10 @@ static int surfel_build(Arena& ari, Arena& ar, hipStream_t s, const T* p, const 
         hipLaunchKernelGGL(k_surfel_gather<T>, dim3(nbp), dim3(kBlock), 0, s, dp, dn, dr, (const unsigned*)ia, (int)np, M.tri, M.face);
     }
     hipLaunchKernelGGL(k_surfel_leaves<T>, dim3(nbl), dim3(kBlock), 0, s, (const T*)M.tri, (int)np, M.P, subdivs, *table, (const MeshHead<T>*)M.head, M.box);
-    for (int m = M.P / 2; m >= 1; m /= 2) hipLaunchKernelGGL(k_mesh_refit<T>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s, M.box, m);
+    for (int m = M.P / 2; m >= 1; m /= 2) hipLaunchKernelGGL(k_mesh_refit<T>, dim3(blocks_for((size_t)m)), dim3(kBlock), 0, s, M.box, m);
     HIP_TRY(hipGetLastError());
     int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (flag_fetch(s, d_bad, &bad)) return -1;
     HIP_WAIT(s);
     return surfel_refuse(bad);
 }
@@ -148,17 +148,12 @@ static int surfel_geometry_impl(pcu_hip_ctx* c, const T* p, const T* n, const T*
         const T *dp = nullptr, *dn = nullptr, *dr = nullptr, *table = nullptr;
         if (stage_in(ar, p, np, on_dev, s, &dp) || stage_in(ar, n, np, on_dev, s, &dn) || stage_any(ar, r, (size_t)np, on_dev, s, &dr) ||
             surfel_table<T>(ar, s, subdivs, &table)) return -1;
-        T* d_v = out_v; int* d_f = out_f; int* d_bad = nullptr;
-        if (aalloc(ar, &d_bad, 1) || (!on_dev && (aalloc(ar, &d_v, nv * 3) || aalloc(ar, &d_f, nf * 3)))) return -1;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_surfel_geometry<T>, dim3((unsigned)((np + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, dp, dn, dr, (int)np, subdivs, table, d_v, d_f, d_bad);
+        T* d_v = nullptr; int *d_f = nullptr, *d_bad = nullptr;
+        if (flag_word(ar, s, &d_bad) || out_room(ar, on_dev, out_v, nv * 3, &d_v) || out_room(ar, on_dev, out_f, nf * 3, &d_f)) return -1;
+        hipLaunchKernelGGL(k_surfel_geometry<T>, dim3(blocks_for((size_t)np)), dim3(kBlock), 0, s, dp, dn, dr, (int)np, subdivs, table, d_v, d_f, d_bad);
         HIP_TRY(hipGetLastError());
         int bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-        if (!on_dev) {
-            HIP_TRY(hipMemcpyAsync(out_v, d_v, nv * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_f, d_f, nf * 12, hipMemcpyDeviceToHost, s));
-        }
+        if (flag_fetch(s, d_bad, &bad) || out_give(s, on_dev, out_v, d_v, nv * 3) || out_give(s, on_dev, out_f, d_f, nf * 3)) return -1;
         HIP_WAIT(s);
         if (int rc = surfel_refuse(bad)) return rc;
         if (st) { st->n_queries = np; st->n_passes = 1; }

@@ -1,6 +1,6 @@
 // csrc/voxel_host.h -- host orchestration of the SURVEY.md 8f-4 operators: Morton codes (morton.h), voxel-grid downsampling and duplicate
 // removal (voxel.h), and the sort, scan and sort-and-rank steps every later *_host.h builds on. Included by pcu_hip.hip after the operator
-// frame (pick_stream, stage_any, op_run), first of the *_host.h headers.
+// frame (pick_stream, stage_any, op_run, out_room / out_give, flag_fetch), first of the *_host.h headers.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------- Morton codes
@@ -19,14 +19,14 @@ static int morton_map_impl(pcu_hip_ctx* c, int kind, const In* in, const In2* in
         const In* d_in; const In2* d_in2 = in2;
         if (stage_any(ar, in, in_count, on_dev, s, &d_in)) return -1;
         if (kind >= 2 && stage_any(ar, in2, (size_t)n, on_dev, s, &d_in2)) return -1;
-        void* d_out = out;
-        if (!on_dev) { char* t = nullptr; if (aalloc(ar, &t, out_bytes)) return -1; d_out = t; }
+        char *const h_out = static_cast<char*>(out), *d_out = nullptr;
+        if (out_room(ar, on_dev, h_out, out_bytes, &d_out)) return -1;
         const int blocks = (int)std::min<int64_t>((n + 255) / 256, 65536);
         if (kind == 0) hipLaunchKernelGGL((k_morton_encode<In>), dim3(blocks), dim3(256), 0, s, d_in, (long long)n, (uint64_t*)d_out);
         else if (kind == 1) hipLaunchKernelGGL((k_morton_decode<In>), dim3(blocks), dim3(256), 0, s, d_in, (long long)n, (int32_t*)d_out);
         else hipLaunchKernelGGL((k_morton_addsub<In, In2>), dim3(blocks), dim3(256), 0, s, d_in, d_in2, (long long)n, kind == 3 ? 1 : 0, (uint64_t*)d_out);
         HIP_TRY(hipGetLastError());
-        if (!on_dev) HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+        if (out_give(s, on_dev, h_out, d_out, out_bytes)) return -1;
         HIP_WAIT(s);
         return 0;
     });
@@ -43,11 +43,11 @@ static int morton_knn_impl(pcu_hip_ctx* c, const C* codes, int64_t n, const C* q
         auto& [c, s, on_dev, ar, tm] = fr;
         const C *d_codes, *d_q;
         if (stage_any(ar, codes, (size_t)n, on_dev, s, &d_codes) || stage_any(ar, qcodes, (size_t)m, on_dev, s, &d_q)) return -1;
-        long long* d_nn = (long long*)out_nn;
-        if (!on_dev && aalloc(ar, &d_nn, (size_t)m * k)) return -1;
+        long long *const h_nn = (long long*)out_nn, *d_nn = nullptr;
+        if (out_room(ar, on_dev, h_nn, (size_t)m * k, &d_nn)) return -1;
         hipLaunchKernelGGL((k_morton_knn<C>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, d_codes, (long long)n, d_q, (long long)m, k, sort_dist, d_nn);
         HIP_TRY(hipGetLastError());
-        if (!on_dev) HIP_TRY(hipMemcpyAsync(out_nn, d_nn, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
+        if (out_give(s, on_dev, h_nn, d_nn, (size_t)m * k)) return -1;
         HIP_WAIT(s);
         return 0;
     });
@@ -111,13 +111,13 @@ static int rank_flags(Arena& ar, hipStream_t s, SortedRuns& r, int n, WriteFlags
 // ... with the first entry of every run of equal sorted keys marked
 static int rank_runs(Arena& ar, hipStream_t s, SortedRuns& r, int n) {
     return rank_flags(ar, s, r, n, [&](unsigned* flag) {
-        hipLaunchKernelGGL(k_run_heads_sorted, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, n, flag);
+        hipLaunchKernelGGL(k_run_heads_sorted, dim3(blocks_for((size_t)n)), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, n, flag);
     });
 }
 // Enqueues the read-back of "flag word and one count" (the last element of a scan); the caller waits once for these and whatever else it reads.
 template <typename U>
 static int read_flag_and_last(hipStream_t s, const int* d_bad, const U* scan, size_t n, int* bad, U* last) {
-    HIP_TRY(hipMemcpyAsync(bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (flag_fetch(s, d_bad, bad)) return -1;
     HIP_TRY(hipMemcpyAsync(last, scan + (n - 1), sizeof(U), hipMemcpyDeviceToHost, s));
     return 0;
 }
@@ -133,7 +133,7 @@ static int sort_by_triple(Arena& ar, hipStream_t s, const K* k0, const K* k1, co
     if (aalloc(ar, &rng, 1) || aalloc(ar, &ka, (size_t)n) || aalloc(ar, &kb, (size_t)n) || aalloc(ar, &alt, (size_t)n)) return -1;
     HIP_TRY(hipMemsetAsync(rng->lo, 0xff, sizeof rng->lo, s));
     HIP_TRY(hipMemsetAsync(rng->hi, 0, sizeof rng->hi, s));
-    const int nb = (n + kBlock - 1) / kBlock;
+    const int nb = blocks_for((size_t)n);
     hipLaunchKernelGGL((k_key_range<K>), dim3(std::min(nb, 256)), dim3(kBlock), 0, s, k0, k1, k2, n, rng);
     KeyRange h;
     HIP_TRY(hipMemcpyAsync(&h, rng, sizeof h, hipMemcpyDeviceToHost, s));
@@ -163,7 +163,7 @@ template <typename K>
 static int runs_of(Arena& ar, hipStream_t s, const K* k0, const K* k1, const K* k2, const unsigned* perm, int n, SortedRuns& r) {
     if (r.keys) return rank_runs(ar, s, r, n);
     return rank_flags(ar, s, r, n, [&](unsigned* flag) {
-        hipLaunchKernelGGL((k_run_heads<K>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, k0, k1, k2, perm, n, flag);
+        hipLaunchKernelGGL((k_run_heads<K>), dim3(blocks_for((size_t)n)), dim3(kBlock), 0, s, k0, k1, k2, perm, n, flag);
     });
 }
 
@@ -193,11 +193,11 @@ static int voxel_downsample_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const 
         const T* d_pts; const A* d_attr = attrib;
         if (stage_any(ar, pts, N * 3, on_dev, s, &d_pts)) return -1;
         if (has_attr && stage_any(ar, attrib, N * (size_t)cols, on_dev, s, &d_attr)) return -1;
-        T* d_out_v = out_v; A* d_out_a = out_a;
-        if (!on_dev) { if (aalloc(ar, &d_out_v, N * 3)) return -1; if (has_attr && aalloc(ar, &d_out_a, N * (size_t)cols)) return -1; }
+        T* d_out_v = nullptr; A* d_out_a = out_a;
+        if (out_room(ar, on_dev, out_v, N * 3, &d_out_v) || (has_attr && out_room(ar, on_dev, out_a, N * (size_t)cols, &d_out_a))) return -1;
         int *k0 = nullptr, *k1 = nullptr, *k2 = nullptr; unsigned* ids = nullptr;
         if (aalloc(ar, &k0, N) || aalloc(ar, &k1, N) || aalloc(ar, &k2, N) || aalloc(ar, &ids, N)) return -1;
-        const int nb = (int)((n + kBlock - 1) / kBlock);
+        const int nb = blocks_for((size_t)n);
         hipLaunchKernelGGL((k_voxel_keys<T>), dim3(nb), dim3(kBlock), 0, s, d_pts, (int)n, vs[0], vs[1], vs[2], mn[0], mn[1], mn[2], k0, k1, k2, ids);
         unsigned* perm = nullptr; SortedRuns r;
         if (sort_by_triple<int>(ar, s, k0, k1, k2, ids, (int)n, &perm, &r.keys)) return -1;
@@ -216,11 +216,9 @@ static int voxel_downsample_impl(pcu_hip_ctx* c, const T* pts, int64_t n, const 
         HIP_TRY(hipMemcpyAsync(&n_out, keep_scan + (n - 1), 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         *out_count = (int64_t)n_out;
-        if (!on_dev && n_out) {
-            HIP_TRY(hipMemcpyAsync(out_v, d_out_v, (size_t)n_out * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
-            if (has_attr) HIP_TRY(hipMemcpyAsync(out_a, d_out_a, (size_t)n_out * cols * sizeof(A), hipMemcpyDeviceToHost, s));
-            HIP_WAIT(s);
-        }
+        bool copied = false;                    // the rows, now that their number is known
+        if (out_give(s, on_dev, out_v, d_out_v, (size_t)n_out * 3, &copied) || out_give(s, on_dev, out_a, d_out_a, (size_t)n_out * cols, &copied)) return -1;
+        if (copied) HIP_WAIT(s);
         return 0;
     });
 }
@@ -238,7 +236,7 @@ static int dedup_device(Arena& ar, hipStream_t s, const T* d_pts, int n, double 
     const size_t N = (size_t)n;
     K *k0 = nullptr, *k1 = nullptr, *k2 = nullptr; unsigned* ids = nullptr;
     if (aalloc(ar, &k0, N) || aalloc(ar, &k1, N) || aalloc(ar, &k2, N) || aalloc(ar, &ids, N)) return -1;
-    const int nb = (n + kBlock - 1) / kBlock;
+    const int nb = blocks_for((size_t)n);
     hipLaunchKernelGGL((k_round_keys<T>), dim3(nb), dim3(kBlock), 0, s, d_pts, n, (T)epsilon, k0, k1, k2, ids);
     unsigned* perm = nullptr; SortedRuns r;
     if (sort_by_triple<K>(ar, s, k0, k1, k2, ids, n, &perm, &r.keys)) return -1;
@@ -260,20 +258,18 @@ static int dedup_impl(pcu_hip_ctx* c, const T* pts, int64_t n, double epsilon, T
         auto& [c, s, on_dev, ar, tm] = fr;
         const T* d_pts;
         if (stage_any(ar, pts, N * 3, on_dev, s, &d_pts)) return -1;
-        T* d_out = out_pts; int *d_svi = out_svi, *d_svj = out_svj;
-        if (!on_dev) { if (aalloc(ar, &d_out, N * 3) || aalloc(ar, &d_svi, N) || aalloc(ar, &d_svj, N)) return -1; }
+        T* d_out = nullptr; int *d_svi = nullptr, *d_svj = nullptr;
+        if (out_room(ar, on_dev, out_pts, N * 3, &d_out) || out_room(ar, on_dev, out_svi, N, &d_svi) || out_room(ar, on_dev, out_svj, N, &d_svj)) return -1;
         const unsigned* n_out_dev = nullptr;
         if (dedup_device<T>(ar, s, d_pts, (int)n, epsilon, d_out, d_svi, d_svj, &n_out_dev)) return -1;
         unsigned n_out = 0;
         HIP_TRY(hipMemcpyAsync(&n_out, n_out_dev, 4, hipMemcpyDeviceToHost, s));
         HIP_WAIT(s);
         *out_count = (int64_t)n_out;
-        if (!on_dev) {
-            HIP_TRY(hipMemcpyAsync(out_pts, d_out, (size_t)n_out * 3 * sizeof(T), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_svi, d_svi, (size_t)n_out * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_svj, d_svj, N * 4, hipMemcpyDeviceToHost, s));
-            HIP_WAIT(s);
-        }
+        bool copied = false;                    // the rows, now that their number is known
+        if (out_give(s, on_dev, out_pts, d_out, (size_t)n_out * 3, &copied) || out_give(s, on_dev, out_svi, d_svi, (size_t)n_out, &copied) ||
+            out_give(s, on_dev, out_svj, d_svj, N, &copied)) return -1;
+        if (copied) HIP_WAIT(s);
         return 0;
     });
 }
@@ -292,15 +288,15 @@ static int pairwise_impl(pcu_hip_ctx* c, const T* a, const T* b, int64_t nb, int
         auto& [c, s, on_dev, ar, tm] = fr;
         const T *da, *db;
         if (stage_any(ar, a, na, on_dev, s, &da) || stage_any(ar, b, nbb, on_dev, s, &db)) return -1;
-        T* dout = out;
-        if (!on_dev && aalloc(ar, &dout, no)) return -1;
+        T* dout = nullptr;
+        if (out_room(ar, on_dev, out, no, &dout)) return -1;
         const int pc = std::isnan(p_norm) ? P_TWO : pcode_of(p_norm);                 // ord=None: the 2-norm
         const long long pw_cols = (n + 63) / 64, pw_blocks = pw_cols * ((m + 3) / 4);
         if (pw_blocks > 0x7fffffffll || nb > 65535) return fail(PCU_HIP_ERR_INVALID, "pairwise_distances: problem too large (more than 2^31-1 tiles of 4 x 64 entries per batch, or more than 65535 batches)");
         if (d > 128) hipLaunchKernelGGL((k_pairwise<T, true>), dim3((unsigned)pw_blocks, (unsigned)nb), dim3(256), 0, s, da, db, (int)m, (int)n, (int)d, pc, p_norm, dout, (int)pw_cols);
         else hipLaunchKernelGGL((k_pairwise<T, false>), dim3((unsigned)pw_blocks, (unsigned)nb), dim3(256), 0, s, da, db, (int)m, (int)n, (int)d, pc, p_norm, dout, (int)pw_cols);
         HIP_TRY(hipGetLastError());
-        if (!on_dev) HIP_TRY(hipMemcpyAsync(out, dout, no * sizeof(T), hipMemcpyDeviceToHost, s));
+        if (out_give(s, on_dev, out, dout, no)) return -1;
         HIP_WAIT(s);
         return 0;
     });
@@ -319,8 +315,8 @@ static int sinkhorn_impl(pcu_hip_ctx* c, const T* a, const T* b, const T* M, int
         auto& [c, s, on_dev, ar, tm] = fr;
         SinkArgs<T> k;
         if (stage_any(ar, a, nu, on_dev, s, &k.a) || stage_any(ar, b, nv, on_dev, s, &k.b) || stage_any(ar, M, nM, on_dev, s, &k.M)) return -1;
-        T* dP = out_P;
-        if (!on_dev && aalloc(ar, &dP, nM)) return -1;
+        T* dP = nullptr;
+        if (out_room(ar, on_dev, out_P, nM, &dP)) return -1;
         int* flagsd = nullptr;
         if (aalloc(ar, &k.u, nu) || aalloc(ar, &k.v, nv) || aalloc(ar, &k.du, nu) || aalloc(ar, &k.dv, nv) || aalloc(ar, &flagsd, 16)) return -1;
         HIP_TRY(hipMemsetAsync(k.u, 0, nu * sizeof(T), s)); HIP_TRY(hipMemsetAsync(k.v, 0, nv * sizeof(T), s));      // u = zeros_like(a), v = zeros_like(b) (:99-100)
@@ -368,7 +364,7 @@ static int sinkhorn_impl(pcu_hip_ctx* c, const T* a, const T* b, const T* M, int
         hipLaunchKernelGGL((k_sink_plan<T>), dim3((unsigned)(pl_cols * m), (unsigned)nb), dim3(256), 0, s, k, dP, (int)pl_cols);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(host_flags, flagsd, sizeof host_flags, hipMemcpyDeviceToHost, s));
-        if (!on_dev) HIP_TRY(hipMemcpyAsync(out_P, dP, nM * sizeof(T), hipMemcpyDeviceToHost, s));
+        if (out_give(s, on_dev, out_P, dP, nM)) return -1;
         HIP_WAIT(s);
         if (out_iters) *out_iters = host_flags[1];
         return 0;

@@ -30,6 +30,7 @@ constexpr double kVxRange = 1048576.0;                      // voxel coordinates
 constexpr unsigned long long kVxMaxCandidates = 1ull << 32; // the candidate cap of one call. A choice (it bounds the time one call can hold a GPU), not a measured limit.
 constexpr unsigned long long kVxFaceSat = 1ull << 33;       // a face's count saturates here, above the cap: 2^27 faces cannot overflow the 64-bit scan
 constexpr int kVxBadRange = 4;                              // next to kMeshBadVertex / kMeshBadFace in the call's flag word
+constexpr int kVxBadCoord = 8;                              // a voxel coordinate of the input outside [-2^20, 2^20) (k_vb_codes, k_hx_codes of marching_cubes.h)
 
 struct VxGrid { double size[3], origin[3]; };
 struct VxHead { int lo[3], hi[3]; };                        // extent of all candidates (atomics; lo starts at INT_MAX, hi at INT_MIN)
@@ -248,15 +249,12 @@ __global__ __launch_bounds__(kBlock) void k_vx_rows(const unsigned long long* __
 }
 
 // ---------------------------------------------------------------------------------------------------- sparse_voxel_grid_boundary
-// A coordinate of any of the four integer types (kind as for faces), and whether it lies in [-2^20, 2^20).
+// A coordinate of any of the four integer types (index_kinds.h), and whether it lies in [-2^20, 2^20). The window is signed for the signed
+// kinds only: an unsigned value of 2^63 or more is out of range, not a negative coordinate.
 __device__ __forceinline__ bool vx_coord(const void* __restrict__ p, int kind, size_t at, int& out) {
-    long long x; bool ok = true;
-    if (kind == 0) x = static_cast<const int*>(p)[at];
-    else if (kind == 1) x = static_cast<const long long*>(p)[at];
-    else if (kind == 2) x = static_cast<const unsigned*>(p)[at];
-    else { const unsigned long long u = static_cast<const unsigned long long*>(p)[at]; ok = u < (1ull << 20); x = (long long)(ok ? u : 0ull); }
-    ok = ok && x >= -(1ll << 20) && x < (1ll << 20);
-    out = ok ? (int)x : 0;
+    const unsigned long long u = index_in(p, kind, at);
+    const bool ok = index_kind_signed(kind) ? u + (1ull << 20) < (1ull << 21) : u < (1ull << 20);
+    out = ok ? (int)(long long)u : 0;
     return ok;
 }
 __global__ __launch_bounds__(kBlock) void k_vb_codes(const void* __restrict__ ijk, int kind, int n, unsigned long long* __restrict__ codes, unsigned long long* __restrict__ sorted,
@@ -271,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void k_vb_codes(const void* __restrict__ ij
         const unsigned long long c = morton_encode3(x, y, z);
         codes[i] = c; sorted[i] = c;
     }
-    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
+    if (__ballot(out) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, kVxBadCoord);
 }
 // flag[i] = 1 if one of the six face neighbours of row i is not among the codes (a neighbour outside [-2^20, 2^20) is absent)
 __global__ __launch_bounds__(kBlock) void k_vb_flag(const unsigned long long* __restrict__ codes, const unsigned long long* __restrict__ sorted, int n, unsigned* __restrict__ flag) {
@@ -292,9 +290,12 @@ __global__ __launch_bounds__(kBlock) void k_vb_flag(const unsigned long long* __
     }
     flag[i] = missing ? 1u : 0u;
 }
-__global__ __launch_bounds__(kBlock) void k_vb_rows(const unsigned* __restrict__ flag, const unsigned* __restrict__ scan, int n, long long* __restrict__ out) {
+// (bad: the finished flag word of k_vb_codes. With its bit raised the call will be refused, and nothing is written to out, which is the caller's
+// own memory when the call's pointers are device memory.)
+__global__ __launch_bounds__(kBlock) void k_vb_rows(const unsigned* __restrict__ flag, const unsigned* __restrict__ scan, int n, long long* __restrict__ out,
+                                                    const int* __restrict__ bad) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < n && flag[i]) out[scan[i] - 1u] = i;
+    if (i < n && flag[i] && !(*bad & kVxBadCoord)) out[scan[i] - 1u] = i;
 }
 
 // ---------------------------------------------------------------------------------------------------- voxel_grid_geometry
@@ -317,12 +318,8 @@ __global__ __launch_bounds__(kBlock) void k_vg_geometry(const void* __restrict__
         const double unit[3] = {(double)(vi & 1), (double)((vi >> 1) & 1), (double)(vi < 4 ? 1 : 0)};
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            double c;
-            const size_t at = 3 * (size_t)row + k;
-            if (kind == 0) c = (double)static_cast<const int*>(ijk)[at];
-            else if (kind == 1) c = (double)static_cast<const long long*>(ijk)[at];
-            else if (kind == 2) c = (double)static_cast<const unsigned*>(ijk)[at];
-            else c = (double)static_cast<const unsigned long long*>(ijk)[at];
+            const unsigned long long u = index_in(ijk, kind, 3 * (size_t)row + k);
+            const double c = index_kind_signed(kind) ? (double)(long long)u : (double)u;
             double x = unit[k] * (1.0 - gap) + 0.5 * gap;
             x = x + c;
             x = x * g.size[k];

@@ -20,9 +20,9 @@ static int vx_bits_between(int lo, int hi) { return bits_of((unsigned long long)
 // The rows of the context's last voxelization are parked for pcu_hip_voxelize_take: the row count is the one value the host has to see
 // before the caller's output can exist.
 static int vx_park(pcu_hip_ctx* c, hipStream_t s, const int* rows, int64_t m) {
-    char *seg0 = nullptr, *seg1 = nullptr;
-    if (park_reserve(c, (size_t)m * 12, 0, &seg0, &seg1)) return -1;
-    HIP_TRY(hipMemcpyAsync(seg0, rows, (size_t)m * 12, hipMemcpyDeviceToDevice, s));
+    char* seg[kParkSegs];
+    if (park_reserve(c, {(size_t)m * 12}, seg)) return -1;
+    HIP_TRY(hipMemcpyAsync(seg[0], rows, (size_t)m * 12, hipMemcpyDeviceToDevice, s));
     HIP_WAIT(s);
     park_commit(c, Parked::VoxelRows, m, 0);
     return 0;
@@ -48,10 +48,10 @@ static int voxelize_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, const double* si
         if (ms_mesh_stage(ar, s, m, on_dev, M)) return -1;
         int* ext = nullptr; unsigned long long *cnt = nullptr, *C = nullptr; VxHead* head = nullptr;
         if (aalloc(ar, &ext, NF * 6) || aalloc(ar, &cnt, NF) || aalloc(ar, &C, NF) || aalloc(ar, &head, 1)) return -1;
-        int* d_bad = reinterpret_cast<int*>(reinterpret_cast<char*>(M.head) + offsetof(MeshHead<T>, bad));
+        int* d_bad = mesh_head_flag(M.head);
         const int nf = (int)m.nf;
         hipLaunchKernelGGL(k_vx_head_init, dim3(1), dim3(64), 0, s, head);
-        hipLaunchKernelGGL(k_vx_extent<T>, dim3((unsigned)((nf + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, M.v, (const int*)M.fidx, nf, g, ext, cnt, d_bad, head);
+        hipLaunchKernelGGL(k_vx_extent<T>, dim3(blocks_for((size_t)nf)), dim3(kBlock), 0, s, M.v, (const int*)M.fidx, nf, g, ext, cnt, d_bad, head);
         if (own_inclusive_scan(ar, s, (const unsigned long long*)cnt, C, NF)) return -1;
         tm.mark(1);
         unsigned long long total = 0; VxHead hh;
@@ -98,7 +98,7 @@ static int voxelize_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, const double* si
         tm.mark(5);
         const int bits = 3 * std::max(vx_bits_between(hh.lo[0], hh.hi[0]), std::max(vx_bits_between(hh.lo[1], hh.hi[1]), vx_bits_between(hh.lo[2], hh.hi[2])));
         if (sort_keys(ar, s, r, K, bits) || rank_runs(ar, s, r, K)) return -1;
-        hipLaunchKernelGGL(k_vx_rows, dim3((K + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, (const unsigned*)r.flag, (const unsigned*)r.scan, K,
+        hipLaunchKernelGGL(k_vx_rows, dim3(blocks_for((size_t)K)), dim3(kBlock), 0, s, (const unsigned long long*)r.keys, (const unsigned*)r.flag, (const unsigned*)r.scan, K,
                            rows);
         HIP_TRY(hipGetLastError());
         tm.mark(6);
@@ -117,7 +117,7 @@ static int voxelize_impl(pcu_hip_ctx* c, const MeshGiven<T>& m, const double* si
 // The rows of this context's last pcu_hip_voxelize_triangle_mesh_*: out_ijk (rows, 3) int32. They can be taken once.
 static int voxelize_take_impl(pcu_hip_ctx* c, int64_t rows, int32_t* out_ijk, unsigned flags, void* stream) {
     if (!c || !out_ijk) return fail(PCU_HIP_ERR_INVALID, "null context / out_ijk");
-    return park_take(c, Parked::VoxelRows, rows, 0, out_ijk, nullptr, flags, stream, "pcu_hip_voxelize_take: this context holds no voxelization of %lld rows");
+    return park_take(c, Parked::VoxelRows, rows, 0, {out_ijk}, flags, stream, "pcu_hip_voxelize_take: this context holds no voxelization of %lld rows");
 }
 
 // sparse_voxel_grid_boundary (src/sparse_voxel_grid.cpp:473-522). out_idx (n) worst case; *out_count rows are written, ascending.
@@ -133,24 +133,25 @@ static int voxel_boundary_impl(pcu_hip_ctx* c, const void* ijk, int64_t n, int k
     return op_run(c, flags, stream, nullptr, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;
         const char* d_in = nullptr;
-        if (stage_any(ar, static_cast<const char*>(ijk), N * 3 * int_kind_bytes(kind), on_dev, s, &d_in)) return -1;
+        if (stage_faces(ar, ijk, N, kind, on_dev, s, &d_in)) return -1;
         unsigned long long* codes = nullptr; SortedRuns r; int* d_bad = nullptr;
-        long long* d_out = reinterpret_cast<long long*>(out_idx);
-        if (aalloc(ar, &codes, N) || aalloc(ar, &r.keys, N) || aalloc(ar, &d_bad, 1) || (!on_dev && aalloc(ar, &d_out, N))) return -1;
-        const int nn = (int)n, nb = (nn + kBlock - 1) / kBlock;
-        HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+        long long *const h_out = reinterpret_cast<long long*>(out_idx), *d_out = nullptr;
+        if (aalloc(ar, &codes, N) || aalloc(ar, &r.keys, N) || flag_word(ar, s, &d_bad) || out_room(ar, on_dev, h_out, N, &d_out)) return -1;
+        const int nn = (int)n; const unsigned nb = blocks_for(N);
         hipLaunchKernelGGL(k_vb_codes, dim3(nb), dim3(kBlock), 0, s, (const void*)d_in, kind, nn, codes, r.keys, d_bad);
         if (sort_keys(ar, s, r, nn, 63)) return -1;
         if (rank_flags(ar, s, r, nn, [&, s = s](unsigned* flag) {
                 hipLaunchKernelGGL(k_vb_flag, dim3(nb), dim3(kBlock), 0, s, (const unsigned long long*)codes, (const unsigned long long*)r.keys, nn, flag);
             })) return -1;
-        hipLaunchKernelGGL(k_vb_rows, dim3(nb), dim3(kBlock), 0, s, (const unsigned*)r.flag, (const unsigned*)r.scan, nn, d_out);
+        hipLaunchKernelGGL(k_vb_rows, dim3(nb), dim3(kBlock), 0, s, (const unsigned*)r.flag, (const unsigned*)r.scan, nn, d_out, (const int*)d_bad);
         HIP_TRY(hipGetLastError());
         int bad = 0; unsigned m = 0;
         if (read_flag_and_last(s, d_bad, r.scan, N, &bad, &m)) return -1;
         HIP_WAIT(s);
         if (bad) return fail(PCU_HIP_ERR_INVALID, "Invalid vertex leads to an overflow integer. Perhaps grid_size is too small.");
-        if (!on_dev && m) { HIP_TRY(hipMemcpyAsync(out_idx, d_out, (size_t)m * 8, hipMemcpyDeviceToHost, s)); HIP_WAIT(s); }
+        bool copied = false;
+        if (out_give(s, on_dev, h_out, d_out, (size_t)m, &copied)) return -1;
+        if (copied) HIP_WAIT(s);
         *out_count = (int64_t)m;
         return 0;
     });
@@ -170,15 +171,12 @@ static int voxel_geometry_impl(pcu_hip_ctx* c, const void* ijk, int64_t n, int k
     return op_run(c, flags, stream, nullptr, bytes, [&](OpFrame& fr) -> int {
         auto& [c, s, on_dev, ar, tm] = fr;
         const char* d_in = nullptr;
-        if (stage_any(ar, static_cast<const char*>(ijk), N * 3 * int_kind_bytes(kind), on_dev, s, &d_in)) return -1;
-        float* d_v = out_v; int* d_f = out_f;
-        if (!on_dev && (aalloc(ar, &d_v, N * 24) || aalloc(ar, &d_f, N * 36))) return -1;
-        hipLaunchKernelGGL(k_vg_geometry, dim3((unsigned)((12 * n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, (const void*)d_in, kind, (long long)n, g, gap, d_v, d_f);
+        if (stage_faces(ar, ijk, N, kind, on_dev, s, &d_in)) return -1;
+        float* d_v = nullptr; int* d_f = nullptr;
+        if (out_room(ar, on_dev, out_v, N * 24, &d_v) || out_room(ar, on_dev, out_f, N * 36, &d_f)) return -1;
+        hipLaunchKernelGGL(k_vg_geometry, dim3(blocks_for(12 * N)), dim3(kBlock), 0, s, (const void*)d_in, kind, (long long)n, g, gap, d_v, d_f);
         HIP_TRY(hipGetLastError());
-        if (!on_dev) {
-            HIP_TRY(hipMemcpyAsync(out_v, d_v, N * 96, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_f, d_f, N * 144, hipMemcpyDeviceToHost, s));
-        }
+        if (out_give(s, on_dev, out_v, d_v, N * 24) || out_give(s, on_dev, out_f, d_f, N * 36)) return -1;
         HIP_WAIT(s);
         return 0;
     });

@@ -6,8 +6,10 @@ import ctypes
 import numpy as np
 import pytest
 
+import decimate_contract as dc
 import marching_cubes_contract as mc
 import mesh_smooth_contract as ms
+import radius_contract as rc
 import voxelize_contract as vc
 
 pytestmark = pytest.mark.gpu
@@ -112,7 +114,41 @@ class Adjacency(Kind):
         return L.pcu_hip_mesh_adjacency_take
 
 
-KINDS = [Voxelization(), Surface(), HexMesh(), Adjacency()]
+class Decimated(Kind):
+    """Four segments: vertices, faces and the two correspondences. The octahedron, down to four faces."""
+    text = "holds no decimated mesh"
+    V, F = (a.astype(t) for a, t in zip(dc.mesh("octahedron"), (np.float32, np.int32)))
+    want = list(dc.decimate(V, F, 4))
+    counts = (len(want[0]), len(want[1]))
+
+    def park(self, L, ctx):
+        nv, nf = ctypes.c_int64(0), ctypes.c_int64(0)
+        rc_ = L.pcu_hip_decimate_triangle_mesh_f32(ctx, self.V.ctypes.data, len(self.V), self.F.ctypes.data, len(self.F), INT32, 4, ctypes.addressof(nv),
+                                                   ctypes.addressof(nf), 0, None, None)
+        return rc_, (nv.value, nf.value)
+
+    def take_fn(self, L):
+        return L.pcu_hip_decimate_triangle_mesh_take
+
+
+class RadiusRows(Kind):
+    """The rows of a radius search of the 64 points among themselves; the offsets come back with the call that parks them."""
+    text = "holds no radius result"
+    RADIUS = 0.3
+    offsets, *want = rc.radius_search(POINTS, POINTS, RADIUS)
+    counts = (64, len(want[0]))
+
+    def park(self, L, ctx):
+        off, total = np.empty(65, dtype=np.int64), ctypes.c_int64(0)
+        rc_ = L.pcu_hip_radius_search_f32(ctx, POINTS.ctypes.data, 64, POINTS.ctypes.data, 64, self.RADIUS, 1, off.ctypes.data, ctypes.addressof(total), 0, None, None)
+        assert rc_ != 0 or np.array_equal(off, self.offsets)
+        return rc_, (64, total.value)
+
+    def take_fn(self, L):
+        return L.pcu_hip_radius_search_take
+
+
+KINDS = [Voxelization(), Surface(), HexMesh(), Adjacency(), Decimated(), RadiusRows()]
 IDS = [type(k).__name__ for k in KINDS]
 
 
@@ -164,7 +200,7 @@ def test_every_later_use_of_the_block_drops_the_parked_result(gpu):
                 outs = b.outs(False)
                 assert b.take(L, ctx, b.counts, outs) == 0 and b.matches(outs), (type(a).__name__, type(b).__name__)
             pairs.append((a, b))
-    assert len(pairs) == 4 * 4 + 1
+    assert len(pairs) == len(KINDS) * len(KINDS) + 1
 
 
 # ---------------------------------------------------------------------------------------------------- 3. operators that do not use the block
