@@ -2,6 +2,8 @@
 (src/common/common.h) and the k-NN family's pair checks (src/point_cloud_distance.cpp), this package's row limit, what the library checks on the device found on the host for host arrays, and the placing of
 further arrays beside the resolved ones of a call. Order, texts and exception types are part of the contract (tests/test_check_texts.py).
 It imports _call only."""
+import math
+
 import numpy as np
 
 from ._call import _FACE_KINDS, _Dev, _dtype_name, _is_torch, _shape2
@@ -127,6 +129,14 @@ def _check_beta(beta, noun):
     if not beta > 0.0:
         raise ValueError(f"beta must be greater than 0 (finite, or +inf for the plain sum over all {noun})")
     return beta
+
+
+def _check_radius(radius):
+    """The radius of the fixed-radius calls, and eps of the clustering built on them."""
+    radius = float(radius)
+    if not (radius >= 0.0) or math.isinf(radius):
+        raise ValueError(f"Invalid radius ({radius}): must be finite and not negative.")
+    return radius
 
 
 def _check_bounds(lower_bound, upper_bound):

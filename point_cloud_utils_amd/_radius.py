@@ -2,20 +2,12 @@
 reference's exported API (its kd-tree's radiusSearch, which it uses inside estimate_point_cloud_normals_ball only); the values follow this
 library's stated contract (in numpy: tests/radius_contract.py). DatasetIndex.radius_search / radius_count end here too."""
 import ctypes
-import math
 
 import numpy as np
 
 from . import _lib
 from ._call import _Dev, _call, _shape2, _take
-from ._checks import _KNN_DIM, _KNN_ROW_LIMIT, _KNN_ZERO, _check_pair, _check_rows
-
-
-def _check_radius(radius):
-    radius = float(radius)
-    if not (radius >= 0.0) or math.isinf(radius):
-        raise ValueError(f"Invalid radius ({radius}): must be finite and not negative.")
-    return radius
+from ._checks import _KNN_DIM, _KNN_ROW_LIMIT, _KNN_ZERO, _check_pair, _check_radius, _check_rows
 
 
 def _search(name, d, head, radius, squared_distances, sort_results):

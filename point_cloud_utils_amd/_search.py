@@ -10,6 +10,7 @@ import numpy as np
 from . import _lib
 from ._call import _Dev, _Handle, _call, _shape2
 from ._checks import _HD_DIM, _HD_ZERO, _KNN_DIM, _KNN_ROW_LIMIT, _KNN_ZERO, _check_float, _check_pair, _check_rows
+from ._dbscan import _index_cluster_dbscan
 from ._fps import _index_farthest_point_sample
 from ._radius import _index_radius_count, _index_radius_search
 
@@ -244,3 +245,9 @@ class DatasetIndex(_Handle):
         size the sampling walks the index's own cell order: cells sized for a small k_hint make its buckets long and thin, which costs
         speed, never exactness."""
         return _index_farthest_point_sample(self, num_samples, start_index, return_distances, squared_distances)
+
+    def cluster_dbscan(self, eps, min_points, return_core=False):
+        """See point_cloud_utils_amd.cluster_point_cloud_dbscan; the cloud is the indexed dataset, nothing is rebuilt, and the bytes returned
+        are the free function's (numpy arrays if the index was built from one, tensors on its device otherwise). The walks run over the
+        index's own grid: when eps is large against its cells they visit more cells, which costs speed, never exactness."""
+        return _index_cluster_dbscan(self, eps, min_points, return_core)

@@ -50,6 +50,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "decimate.h"
 #include "radius.h"
 #include "fps.h"
+#include "dbscan.h"
 
 using namespace pcu;
 
@@ -2553,6 +2554,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "decimate_host.h"
 #include "radius_host.h"
 #include "fps_host.h"
+#include "dbscan_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2985,6 +2987,18 @@ int pcu_hip_fps_geometry(int out[4]) {
     out[0] = kFpsBlockRows; out[1] = kFpsBucket; out[2] = kFpsBlocks; out[3] = kFpsChain;
     return 0;
 }
+// cluster_point_cloud_dbscan (dbscan.h, dbscan_host.h)
+#define PCU_DBSCAN_ABI(SUF, T)                                                                                                                        \
+int pcu_hip_dbscan_##SUF(pcu_hip_ctx* c, const T* pts, int64_t n, double eps, int64_t min_points, int64_t* out_labels, unsigned char* out_core,      \
+                         int64_t* out_num_clusters, unsigned flags, void* stream, pcu_hip_stats* st) {                                               \
+    CallGuard dg(c); return abi_rc(dbscan_impl<T>(c, pts, n, nullptr, eps, min_points, out_labels, out_core, out_num_clusters, flags, stream, st)); } \
+int pcu_hip_index_dbscan_##SUF(pcu_hip_ctx* c, const pcu_hip_index* ix, double eps, int64_t min_points, int64_t* out_labels, unsigned char* out_core, \
+                               int64_t* out_num_clusters, unsigned flags, void* stream, pcu_hip_stats* st) {                                         \
+    if (!ix) return fail(PCU_HIP_ERR_INVALID, "null index");                                                                                         \
+    CallGuard dg(c); return abi_rc(dbscan_impl<T>(c, nullptr, ix->n, ix, eps, min_points, out_labels, out_core, out_num_clusters, flags, stream, st)); }
+PCU_DBSCAN_ABI(f32, float)
+PCU_DBSCAN_ABI(f64, double)
+#undef PCU_DBSCAN_ABI
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
