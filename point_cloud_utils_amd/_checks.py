@@ -139,6 +139,49 @@ def _check_radius(radius):
     return radius
 
 
+def _check_target_normals(target_normals, dtype_name, m):
+    """The normals of register_point_clouds_icp's target: an (m, 3) array of the clouds' dtype (their kind is _beside's business)."""
+    dn = _dtype_name(target_normals)
+    if dn != dtype_name:
+        raise ValueError(f"Invalid scalar type ({dn}) for argument 'target_normals'. Expected it to match argument "
+                         f"'target_points' which is of type {dtype_name}.")
+    sn = tuple(target_normals.shape)
+    if sn != (m, 3):
+        raise ValueError(f"Invalid shape for target_normals: must have shape ({m}, 3), one normal per target point. "
+                         f"Got target_normals.shape = {sn}.")
+
+
+def _check_max_correspondence_distance(distance):
+    """Not _check_radius: +inf is allowed (and the default) -- every source row with a finite nearest distance then is an inlier."""
+    distance = float(distance)
+    if not distance >= 0.0:
+        raise ValueError(f"Invalid max_correspondence_distance ({distance}): must not be NaN or negative.")
+    return distance
+
+
+def _check_tolerance(value, name):
+    value = float(value)
+    if not (value >= 0.0) or math.isinf(value):
+        raise ValueError(f"Invalid {name} ({value}): must be finite and not negative.")
+    return value
+
+
+def _check_init_transform(init_transform):
+    """None (identity), or anything numpy turns into a finite (4, 4) float64 matrix with last row [0, 0, 0, 1]. Returns a C-contiguous copy."""
+    text = "Invalid init_transform: must be a finite (4, 4) matrix with last row [0, 0, 0, 1]."
+    if init_transform is None:
+        return np.eye(4, dtype=np.float64)
+    if _is_torch(init_transform):
+        init_transform = init_transform.detach().cpu().numpy()
+    try:
+        m = np.array(init_transform, dtype=np.float64, order="C")
+    except (TypeError, ValueError):
+        raise ValueError(text) from None
+    if m.shape != (4, 4) or not bool(np.isfinite(m).all()) or m[3].tolist() != [0.0, 0.0, 0.0, 1.0]:
+        raise ValueError(text)
+    return m
+
+
 def _check_bounds(lower_bound, upper_bound):
     lower_bound, upper_bound = float(lower_bound), float(upper_bound)
     if lower_bound != lower_bound or upper_bound != upper_bound:

@@ -69,6 +69,7 @@ def estimate_point_cloud_normals_knn(points, num_neighbors, view_directions=None
         idx : an (m,)-shaped array of indices into points (the points that were kept, ascending)
         n : an (m, 3)-shaped array of unit normals for each of those points. Without view_directions the sign of a normal is
             not defined (in the reference it is whatever Eigen's JacobiSVD returns).
+            These are what register_point_clouds_icp takes as target_normals (point-to-plane): the sign of a normal does not matter there.
     """
     num_neighbors = int(num_neighbors)
     if num_neighbors <= 0:     # src/point_cloud_normals.cpp:385-389
@@ -98,6 +99,7 @@ def estimate_point_cloud_normals_ball(points, ball_radius, view_directions=None,
     Returns:
         idx : an (m,)-shaped array of indices into points (the points that were kept, ascending)
         n : an (m, 3)-shaped array of unit normals for each of those points
+            These are what register_point_clouds_icp takes as target_normals (point-to-plane): the sign of a normal does not matter there.
     """
     # src/point_cloud_normals.cpp:318-329
     if ball_radius <= 0.0:

@@ -4,6 +4,7 @@
 signatures, defaults, dtypes, shapes and error behaviour. DatasetIndex's radius and farthest-point methods delegate to _radius and _fps: this
 is the one module that composes them ("The Python layer")."""
 import ctypes
+import math
 
 import numpy as np
 
@@ -12,6 +13,7 @@ from ._call import _Dev, _Handle, _call, _shape2
 from ._checks import _HD_DIM, _HD_ZERO, _KNN_DIM, _KNN_ROW_LIMIT, _KNN_ZERO, _check_float, _check_pair, _check_rows
 from ._dbscan import _index_cluster_dbscan
 from ._fps import _index_farthest_point_sample
+from ._icp import _index_register_icp
 from ._radius import _index_radius_count, _index_radius_search
 
 
@@ -251,3 +253,11 @@ class DatasetIndex(_Handle):
         are the free function's (numpy arrays if the index was built from one, tensors on its device otherwise). The walks run over the
         index's own grid: when eps is large against its cells they visit more cells, which costs speed, never exactness."""
         return _index_cluster_dbscan(self, eps, min_points, return_core)
+
+    def register_icp(self, source_points, target_normals=None, init_transform=None, max_correspondence_distance=math.inf, max_iterations=30,
+                     relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False):
+        """See point_cloud_utils_amd.register_point_clouds_icp; the target is the indexed dataset, its grid is built once for all calls, and
+        the bytes returned are the free function's for every k_hint. source_points and target_normals are of the dataset's dtype; results
+        are of source_points' kind."""
+        return _index_register_icp(self, source_points, target_normals, init_transform, max_correspondence_distance, max_iterations,
+                                   relative_fitness, relative_rmse, return_correspondences)

@@ -51,6 +51,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "radius.h"
 #include "fps.h"
 #include "dbscan.h"
+#include "icp.h"
 
 using namespace pcu;
 
@@ -2555,6 +2556,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "radius_host.h"
 #include "fps_host.h"
 #include "dbscan_host.h"
+#include "icp_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -2999,6 +3001,18 @@ int pcu_hip_index_dbscan_##SUF(pcu_hip_ctx* c, const pcu_hip_index* ix, double e
 PCU_DBSCAN_ABI(f32, float)
 PCU_DBSCAN_ABI(f64, double)
 #undef PCU_DBSCAN_ABI
+// register_point_clouds_icp (icp.h, icp_host.h)
+#define PCU_ICP_ABI(SUF, T)                                                                                                                           \
+int pcu_hip_icp_##SUF(pcu_hip_ctx* c, const T* src, int64_t n, const T* tgt, int64_t m, const T* nrm, const double* init, double max_dist, int64_t max_it,    \
+                      double tol_f, double tol_r, pcu_hip_icp_result* out, int64_t* out_corr, unsigned flags, void* stream, pcu_hip_stats* st) {            \
+    CallGuard dg(c); return abi_rc(icp_impl<T>(c, src, n, tgt, m, nullptr, nrm, init, max_dist, max_it, tol_f, tol_r, out, out_corr, flags, stream, st)); } \
+int pcu_hip_index_icp_##SUF(pcu_hip_ctx* c, const pcu_hip_index* ix, const T* src, int64_t n, const T* nrm, const double* init, double max_dist, int64_t max_it, \
+                            double tol_f, double tol_r, pcu_hip_icp_result* out, int64_t* out_corr, unsigned flags, void* stream, pcu_hip_stats* st) {      \
+    if (!ix) return fail(PCU_HIP_ERR_INVALID, "null index");                                                                                         \
+    CallGuard dg(c); return abi_rc(icp_impl<T>(c, src, n, nullptr, ix->n, ix, nrm, init, max_dist, max_it, tol_f, tol_r, out, out_corr, flags, stream, st)); }
+PCU_ICP_ABI(f32, float)
+PCU_ICP_ABI(f64, double)
+#undef PCU_ICP_ABI
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
