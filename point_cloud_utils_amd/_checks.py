@@ -3,6 +3,8 @@
 further arrays beside the resolved ones of a call. Order, texts and exception types are part of the contract (tests/test_check_texts.py).
 It imports _call only."""
 import math
+import operator
+import time
 
 import numpy as np
 
@@ -68,6 +70,21 @@ def _check_finite(x, text):
         finite = bool(np.isfinite(x).all())
     if not finite:
         raise ValueError(text)
+
+
+def _check_finite_cloud(points):
+    """The cloud of the calls that take one cloud and no non-finite coordinate (farthest-point sampling, plane segmentation): dtype, shape,
+    zero rows, the row limit, then the Poisson-disk call's rule. Returns the number of rows."""
+    _check_float(points, "points")
+    sp = _shape2(points)
+    if sp[1] != 3:
+        raise ValueError(_NOT_3D.format(*sp))
+    if sp[0] == 0:
+        raise ValueError(_ZERO_POINTS.format(*sp))
+    _check_rows(sp[0])
+    # no stable meaning for non-finite coordinates: refused before any work on them
+    _check_finite(points, "points must not contain NaN or infinite coordinates")
+    return sp[0]
 
 
 def _size(a):
@@ -180,6 +197,42 @@ def _check_init_transform(init_transform):
     if m.shape != (4, 4) or not bool(np.isfinite(m).all()) or m[3].tolist() != [0.0, 0.0, 0.0, 1.0]:
         raise ValueError(text)
     return m
+
+
+_NUM_ITERATIONS_TOP = 2 ** 20      # hypotheses of segment_point_cloud_plane (csrc/plane_host.h)
+
+
+def _check_plane_rows(n):
+    if n < 3:
+        raise ValueError(f"Invalid number of points ({n}): a plane needs at least 3.")
+    return n
+
+
+def _check_distance_threshold(distance_threshold):
+    distance_threshold = float(distance_threshold)
+    if not (distance_threshold >= 0.0) or math.isinf(distance_threshold):
+        raise ValueError(f"Invalid distance_threshold ({distance_threshold}): must be finite and not negative.")
+    return distance_threshold
+
+
+def _check_num_iterations(num_iterations):
+    try:
+        m = operator.index(num_iterations)
+    except TypeError:
+        m = 0
+    if m < 1 or m > _NUM_ITERATIONS_TOP:
+        raise ValueError(f"Invalid num_iterations ({num_iterations}): must be an integer in [1, 2**20].")
+    return m
+
+
+def _check_seed(random_seed):
+    """The seed rule of the sampling calls: an unsigned 32-bit integer, 0 means "from the clock". Returns the seed actually used, never 0."""
+    seed = int(random_seed)
+    if seed < 0 or seed > 0xFFFFFFFF:
+        raise ValueError(f"random_seed must be an unsigned 32-bit integer, got {seed}")
+    if seed == 0:
+        seed = (time.time_ns() & 0xFFFFFFFF) or 1
+    return seed
 
 
 def _check_bounds(lower_bound, upper_bound):

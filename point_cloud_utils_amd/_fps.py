@@ -6,8 +6,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._call import _Dev, _call, _shape2
-from ._checks import _NOT_3D, _ZERO_POINTS, _check_finite, _check_float, _check_rows
+from ._call import _Dev, _call
+from ._checks import _check_finite_cloud as _check_cloud
 
 
 def _check_counts(n, num_samples, start_index):
@@ -17,19 +17,6 @@ def _check_counts(n, num_samples, start_index):
     if start_index < 0 or start_index >= n:
         raise ValueError(f"Invalid start_index ({start_index}): must be a row of points, in [0, {n}).")
     return num_samples, start_index
-
-
-def _check_cloud(points):
-    _check_float(points, "points")
-    sp = _shape2(points)
-    if sp[1] != 3:
-        raise ValueError(_NOT_3D.format(*sp))
-    if sp[0] == 0:
-        raise ValueError(_ZERO_POINTS.format(*sp))
-    _check_rows(sp[0])
-    # the Poisson-disk call's rule: no stable meaning for non-finite coordinates, refused before any work on them
-    _check_finite(points, "points must not contain NaN or infinite coordinates")
-    return sp[0]
 
 
 def _sample(name, d, head, num_samples, start_index, return_distances, squared_distances, force=0, counters=None):

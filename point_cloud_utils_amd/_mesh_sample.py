@@ -4,22 +4,12 @@ order of checks, error texts and return order; the sample sets follow this libra
 libigl's rand()-driven ones."""
 import ctypes
 import math
-import time
 
 import numpy as np
 
 from . import _lib
 from ._call import Stats, _Dev, _call, _fn, _record
-from ._checks import _MAX_ROWS, _check_mesh, _check_rows, _face_rows, _mesh_args, _resolve
-
-
-def _seed(random_seed):
-    seed = int(random_seed)
-    if seed < 0 or seed > 0xFFFFFFFF:
-        raise ValueError(f"random_seed must be an unsigned 32-bit integer, got {seed}")
-    if seed == 0:                                          # the reference's documented behaviour: a seed from the clock
-        seed = (time.time_ns() & 0xFFFFFFFF) or 1
-    return seed
+from ._checks import _MAX_ROWS, _check_mesh, _check_rows, _check_seed as _seed, _face_rows, _mesh_args, _resolve
 
 
 def mesh_face_areas(v, f, num_threads=-1):

@@ -52,6 +52,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "fps.h"
 #include "dbscan.h"
 #include "icp.h"
+#include "plane.h"
 
 using namespace pcu;
 
@@ -2557,6 +2558,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "fps_host.h"
 #include "dbscan_host.h"
 #include "icp_host.h"
+#include "plane_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -3013,6 +3015,19 @@ int pcu_hip_index_icp_##SUF(pcu_hip_ctx* c, const pcu_hip_index* ix, const T* sr
 PCU_ICP_ABI(f32, float)
 PCU_ICP_ABI(f64, double)
 #undef PCU_ICP_ABI
+// segment_point_cloud_plane (plane.h, plane_host.h)
+#define PCU_PLANE_ABI(SUF, T)                                                                                                                         \
+int pcu_hip_plane_##SUF(pcu_hip_ctx* c, const T* pts, int64_t n, double distance_threshold, int64_t num_iterations, uint32_t seed, int refit,        \
+                        int64_t launch_tests, pcu_hip_plane_result* out, int64_t* out_inliers, unsigned flags, void* stream, pcu_hip_stats* st) {   \
+    CallGuard dg(c); return abi_rc(plane_impl<T>(c, pts, n, distance_threshold, num_iterations, seed, refit, launch_tests, out, out_inliers, flags, stream, st)); }
+PCU_PLANE_ABI(f32, float)
+PCU_PLANE_ABI(f64, double)
+#undef PCU_PLANE_ABI
+int pcu_hip_plane_geometry(int64_t out[2]) {
+    if (!out) return fail(PCU_HIP_ERR_INVALID, "null output");
+    out[0] = kPlaneRows; out[1] = kPlaneLaunchTests;
+    return 0;
+}
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
