@@ -285,6 +285,17 @@ def _host_finite(**arrays):
             raise ValueError(f"{name} must not contain NaN or infinite " + ("values" if name == "a" else "coordinates"))
 
 
+_KNN_NONFINITE = ("Invalid input: dataset_points contains NaN coordinates, or both +inf and -inf along one axis. The reference builds its kd-tree over "
+                  "NaN bounds for such data and returns rows that depend on the traversal; not supported (non-finite query points and single-signed "
+                  "infinities in the dataset are handled as the reference handles them).")       # (csrc/pcu_hip.hip: nonfinite_error)
+
+
+def _host_searched_cloud(points):
+    """The rule of every searched cloud, which the search checks on the device, found on the host for a host array: with the search's text."""
+    if bool(np.isnan(points).any()) or bool(((points == np.inf).any(axis=0) & (points == -np.inf).any(axis=0)).any()):
+        raise ValueError(_KNN_NONFINITE)
+
+
 def _host_ray_checks(ray_o, ray_d):
     _host_finite(ray_o=ray_o, ray_d=ray_d)
 

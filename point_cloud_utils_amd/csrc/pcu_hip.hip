@@ -53,6 +53,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "dbscan.h"
 #include "icp.h"
 #include "plane.h"
+#include "orient.h"
 
 using namespace pcu;
 
@@ -2559,6 +2560,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "dbscan_host.h"
 #include "icp_host.h"
 #include "plane_host.h"
+#include "orient_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -3028,6 +3030,14 @@ int pcu_hip_plane_geometry(int64_t out[2]) {
     out[0] = kPlaneRows; out[1] = kPlaneLaunchTests;
     return 0;
 }
+// orient_point_cloud_normals (orient.h, orient_host.h)
+#define PCU_ORIENT_ABI(SUF, T)                                                                                                                        \
+int pcu_hip_orient_normals_##SUF(pcu_hip_ctx* c, const T* pts, const T* nrm, int64_t n, int64_t k, int max_leaf, T* out_normals, unsigned char* out_flipped, \
+                                 unsigned flags, void* stream, pcu_hip_stats* st) {                                                                  \
+    CallGuard dg(c); return abi_rc(orient_impl<T>(c, pts, nrm, n, k, max_leaf, out_normals, out_flipped, flags, stream, st)); }
+PCU_ORIENT_ABI(f32, float)
+PCU_ORIENT_ABI(f64, double)
+#undef PCU_ORIENT_ABI
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
