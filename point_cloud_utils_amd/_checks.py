@@ -156,6 +156,31 @@ def _check_radius(radius):
     return radius
 
 
+_FEATURE_DIM_TOP = 128             # match_point_features (csrc/feature_match.h: kFmMaxD)
+_FEATURE_ZERO = ("Invalid input set with zero elements: query_features and dataset_features must have shape (n, D) and (m, D). "
+                 "Got query_features.shape = ({}, {}), dataset_features.shape = ({}, {}).")
+_FEATURE_DIM_PAIR = ("Invalid feature dimension: query_features and dataset_features must have the same number of columns. "
+                     "Got query_features.shape = ({}, {}), dataset_features.shape = ({}, {}).")
+
+
+def _check_features(query_features, dataset_features):
+    """The two feature arrays of match_point_features: scalar types as _check_pair states them, zero rows, one D for both, D in [1, 128],
+    the k-NN row limit. Returns (n, m, D)."""
+    dq, dd = _check_float(query_features, "query_features"), _dtype_name(dataset_features)
+    if dd != dq:
+        raise ValueError(f"Invalid scalar type ({dd}) for argument 'dataset_features'. Expected it to match argument "
+                         f"'query_features' which is of type {dq}.")
+    sq, sd = _shape2(query_features), _shape2(dataset_features)
+    if sq[0] == 0 or sd[0] == 0:
+        raise ValueError(_FEATURE_ZERO.format(sq[0], sq[1], sd[0], sd[1]))
+    if sq[1] != sd[1]:
+        raise ValueError(_FEATURE_DIM_PAIR.format(sq[0], sq[1], sd[0], sd[1]))
+    if sq[1] < 1 or sq[1] > _FEATURE_DIM_TOP:
+        raise ValueError(f"Invalid feature dimension ({sq[1]}): must be in [1, 128].")
+    _check_rows(sq[0], sd[0], text=_KNN_ROW_LIMIT)
+    return sq[0], sd[0], sq[1]
+
+
 def _check_target_normals(target_normals, dtype_name, m):
     """The normals of register_point_clouds_icp's target: an (m, 3) array of the clouds' dtype (their kind is _beside's business)."""
     dn = _dtype_name(target_normals)

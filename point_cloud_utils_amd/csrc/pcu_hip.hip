@@ -54,6 +54,8 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "icp.h"
 #include "plane.h"
 #include "orient.h"
+#include "fpfh.h"
+#include "feature_match.h"
 
 using namespace pcu;
 
@@ -2561,6 +2563,8 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "icp_host.h"
 #include "plane_host.h"
 #include "orient_host.h"
+#include "fpfh_host.h"
+#include "feature_match_host.h"
 
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -3038,6 +3042,22 @@ int pcu_hip_orient_normals_##SUF(pcu_hip_ctx* c, const T* pts, const T* nrm, int
 PCU_ORIENT_ABI(f32, float)
 PCU_ORIENT_ABI(f64, double)
 #undef PCU_ORIENT_ABI
+// compute_point_cloud_fpfh and match_point_features (fpfh.h, fpfh_host.h, feature_match.h, feature_match_host.h)
+#define PCU_FPFH_ABI(SUF, T)                                                                                                                          \
+int pcu_hip_fpfh_##SUF(pcu_hip_ctx* c, const T* pts, const T* nrm, int64_t n, double radius, T* out_features, int32_t* out_counts, unsigned flags,    \
+                       void* stream, pcu_hip_stats* st) {                                                                                            \
+    CallGuard dg(c); return abi_rc(fpfh_impl<T>(c, pts, nrm, n, radius, out_features, out_counts, flags, stream, st)); }                             \
+int pcu_hip_match_features_##SUF(pcu_hip_ctx* c, const T* q, int64_t n, const T* d, int64_t m, int64_t dims, int64_t* out_nearest, T* out_d2,        \
+                                 unsigned char* out_mutual, unsigned flags, void* stream, pcu_hip_stats* st) {                                       \
+    CallGuard dg(c); return abi_rc(match_features_impl<T>(c, q, n, d, m, dims, out_nearest, out_d2, out_mutual, flags, stream, st)); }
+PCU_FPFH_ABI(f32, float)
+PCU_FPFH_ABI(f64, double)
+#undef PCU_FPFH_ABI
+int pcu_hip_match_features_geometry(int out[3]) {
+    if (!out) return fail(PCU_HIP_ERR_INVALID, "null output");
+    out[0] = kFmQueries; out[1] = kFmTile; out[2] = kFmRows;
+    return 0;
+}
 // connected_components and flood_fill_3d (components.h, components_host.h)
 int pcu_hip_connected_components(pcu_hip_ctx* c, const void* f, int64_t nf, int f_kind, int64_t nv, void* out_cv, void* out_cf, void* out_nv, void* out_nf,
                                  int64_t* out_count, unsigned flags, void* stream, pcu_hip_stats* st) {
