@@ -48,6 +48,7 @@ from ._plane import segment_point_cloud_plane, PlaneResult  # noqa: F401
 from ._orient import orient_point_cloud_normals  # noqa: F401
 from ._fpfh import compute_point_cloud_fpfh  # noqa: F401
 from ._feature_match import match_point_features  # noqa: F401
+from ._ransac import register_point_clouds_ransac, RansacRegistrationResult  # noqa: F401
 
 __all__ = ["k_nearest_neighbors", "one_sided_hausdorff_distance", "hausdorff_distance", "chamfer_distance",
            "estimate_point_cloud_normals_knn", "estimate_point_cloud_normals_ball",
@@ -67,6 +68,7 @@ __all__ = ["k_nearest_neighbors", "one_sided_hausdorff_distance", "hausdorff_dis
            "radius_search", "radius_count", "downsample_point_cloud_farthest_point", "cluster_point_cloud_dbscan",
            "register_point_clouds_icp", "IcpResult", "segment_point_cloud_plane", "PlaneResult",
            "orient_point_cloud_normals", "compute_point_cloud_fpfh", "match_point_features",
+           "register_point_clouds_ransac", "RansacRegistrationResult",
            "last_stats", "set_timing", "set_cell_occupancy", "device_count", "DatasetIndex", "cancel"]
 
 

@@ -260,6 +260,39 @@ def _check_seed(random_seed):
     return seed
 
 
+_CORRESPONDENCE_LIMIT = "correspondences with more than 2^27-16 rows are not supported"       # (csrc/ransac_host.h)
+
+
+def _check_ransac_clouds(source_points, target_points):
+    """The two clouds of register_point_clouds_ransac: each by _check_finite_cloud, then one dtype for both. Returns (n, m)."""
+    n = _check_finite_cloud(source_points)
+    m = _check_finite_cloud(target_points)
+    _match(target_points, "target_points", _dtype_name(source_points), "argument 'source_points'")
+    return n, m
+
+
+def _check_correspondences(correspondences):
+    """A (c, 2) int64 array with 3 <= c <= 2**27 - 16 (what its entries name is the library's to check, on the device). Returns c."""
+    dc = _face_dtype_name(correspondences)
+    if dc != "int64":
+        raise ValueError(f"Invalid scalar type ({dc}) for argument 'correspondences'. Expected one of ['int64'].")
+    sc = tuple(correspondences.shape)
+    if len(sc) != 2 or sc[1] != 2:
+        raise ValueError("Invalid shape for correspondences: must have shape (c, 2), one [source row, target row] per row. "
+                         f"Got correspondences.shape = {sc}.")
+    if sc[0] < 3:
+        raise ValueError(f"Invalid number of correspondences ({sc[0]}): a rigid transform needs at least 3.")
+    _check_rows(sc[0], text=_CORRESPONDENCE_LIMIT)
+    return sc[0]
+
+
+def _check_edge_length_ratio(edge_length_ratio):
+    ratio = float(edge_length_ratio)
+    if not (0.0 <= ratio <= 1.0):
+        raise ValueError(f"Invalid edge_length_ratio ({ratio}): must be in [0, 1].")
+    return ratio
+
+
 def _check_bounds(lower_bound, upper_bound):
     lower_bound, upper_bound = float(lower_bound), float(upper_bound)
     if lower_bound != lower_bound or upper_bound != upper_bound:

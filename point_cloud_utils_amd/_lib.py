@@ -47,7 +47,7 @@ _COMPUTE_ENTRY_POINTS = [f"pcu_hip_{op}_{suf}" for suf in ("f32", "f64") for op 
     "surfel_geometry", "surfel_rays", "surfel_index_create", "surfel_index_rays", "voxelize_triangle_mesh", "marching_cubes",
     "mesh_vertex_normals", "laplacian_smooth_mesh", "remove_mesh_vertices", "remove_unreferenced_mesh_vertices",
     "deduplicate_mesh_vertices", "decimate_triangle_mesh", "radius_search", "radius_count", "index_radius_search", "index_radius_count", "fps",
-    "index_fps", "dbscan", "index_dbscan", "icp", "index_icp", "plane", "orient_normals", "fpfh", "match_features")] + [
+    "index_fps", "dbscan", "index_dbscan", "icp", "index_icp", "plane", "orient_normals", "fpfh", "match_features", "ransac")] + [
     "pcu_hip_orient_mesh_faces", "pcu_hip_decimate_triangle_mesh_take", "pcu_hip_radius_search_take"] + [
     "pcu_hip_morton_encode", "pcu_hip_morton_decode", "pcu_hip_morton_addsub", "pcu_hip_morton_knn",
     "pcu_hip_voxelize_take", "pcu_hip_sparse_voxel_grid_boundary", "pcu_hip_voxel_grid_geometry",
@@ -173,9 +173,11 @@ def lib():
             getattr(L, "pcu_hip_orient_normals_" + sp).argtypes = [vp, vp, vp, i64, i64, ci, vp, vp, u, vp, vp]
             getattr(L, "pcu_hip_fpfh_" + sp).argtypes = [vp, vp, vp, i64, dbl, vp, vp, u, vp, vp]
             getattr(L, "pcu_hip_match_features_" + sp).argtypes = [vp, vp, i64, vp, i64, i64, vp, vp, vp, u, vp, vp]
+            getattr(L, "pcu_hip_ransac_" + sp).argtypes = [vp, vp, i64, vp, i64, vp, i64, dbl, i64, ctypes.c_uint32, dbl, ci, i64, vp, vp, u, vp, vp]
         L.pcu_hip_match_features_geometry.argtypes = [vp]
         L.pcu_hip_fps_geometry.argtypes = [vp]
         L.pcu_hip_plane_geometry.argtypes = [vp]
+        L.pcu_hip_ransac_geometry.argtypes = [vp]
         L.pcu_hip_radius_search_take.argtypes = [vp, i64, i64, vp, vp, u, vp]
         L.pcu_hip_orient_mesh_faces.argtypes = [vp, vp, i64, ci, i64, vp, vp, vp, u, vp, vp]
         L.pcu_hip_decimate_triangle_mesh_take.argtypes = [vp, i64, i64, vp, vp, vp, vp, u, vp]

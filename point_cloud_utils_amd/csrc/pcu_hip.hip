@@ -53,6 +53,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "dbscan.h"
 #include "icp.h"
 #include "plane.h"
+#include "ransac.h"
 #include "orient.h"
 #include "fpfh.h"
 #include "feature_match.h"
@@ -2562,6 +2563,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "dbscan_host.h"
 #include "icp_host.h"
 #include "plane_host.h"
+#include "ransac_host.h"
 #include "orient_host.h"
 #include "fpfh_host.h"
 #include "feature_match_host.h"
@@ -3032,6 +3034,21 @@ PCU_PLANE_ABI(f64, double)
 int pcu_hip_plane_geometry(int64_t out[2]) {
     if (!out) return fail(PCU_HIP_ERR_INVALID, "null output");
     out[0] = kPlaneRows; out[1] = kPlaneLaunchTests;
+    return 0;
+}
+// register_point_clouds_ransac (ransac.h, ransac_host.h)
+#define PCU_RANSAC_ABI(SUF, T)                                                                                                                        \
+int pcu_hip_ransac_##SUF(pcu_hip_ctx* c, const T* src, int64_t n, const T* tgt, int64_t m, const int64_t* corr, int64_t num_corr, double max_dist,    \
+                         int64_t num_iterations, uint32_t seed, double edge_length_ratio, int refit, int64_t launch_tests, pcu_hip_ransac_result* out, \
+                         int64_t* out_inliers, unsigned flags, void* stream, pcu_hip_stats* st) {                                                    \
+    CallGuard dg(c); return abi_rc(ransac_impl<T>(c, src, n, tgt, m, corr, num_corr, max_dist, num_iterations, seed, edge_length_ratio, refit, launch_tests, out, \
+                                                  out_inliers, flags, stream, st)); }
+PCU_RANSAC_ABI(f32, float)
+PCU_RANSAC_ABI(f64, double)
+#undef PCU_RANSAC_ABI
+int pcu_hip_ransac_geometry(int64_t out[2]) {
+    if (!out) return fail(PCU_HIP_ERR_INVALID, "null output");
+    out[0] = kRansacRows; out[1] = kPlaneLaunchTests;
     return 0;
 }
 // orient_point_cloud_normals (orient.h, orient_host.h)
