@@ -2,7 +2,8 @@
 //
 // One evaluation of the current transform M is: k_icp_transform (source rows to p = T(M * row)), the library's own k = 1 search of p in the
 // target (knn_impl, untouched), k_icp_sums (inliers, their terms, the first two levels of the sum tree), k_icp_fold (the remaining levels and
-// the record the host reads). Everything is float64 with one rounding per operation (the unit is built with -ffp-contract=off), no square root.
+// the record the host reads). The two levels are icp_sum_block, which plane.h's and ransac.h's sums use with their own terms. Everything is
+// float64 with one rounding per operation (the unit is built with -ffp-contract=off), no square root.
 //
 // The order of every sum is the contract's fold64: the terms in source-row order, padded with +0.0 to rows of 64; six times the upper half of a
 // row is added to its lower half; the row results are the next level's terms; until one value remains. On a wave that is the __shfl_xor
@@ -56,9 +57,10 @@ struct IcpSumsArgs {
     int* flags;
 };
 
-template <typename T, int MODE>
-__global__ __launch_bounds__(kIcpBlock) void k_icp_sums(const IcpSumsArgs<T> a) {
-    constexpr int NS = MODE == kIcpPlane ? kIcpSumsPlane : kIcpSumsPoint;
+// The first two levels of the sum tree of NS sums over n rows, for one block: the only copy of the tree's block shape. terms(i, t) fills the NS
+// terms of row i < n into t, which arrives as +0.0 and stays so for a row that contributes nothing; rows past n are +0.0. part: [sum][block].
+template <int NS, typename Terms>
+__device__ __forceinline__ void icp_sum_block(int n, double* __restrict__ part, int nblocks, Terms terms) {
     __shared__ double lv1[NS][kIcpGroups];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int g = 0; g < kIcpGroups / 16; ++g) {
@@ -67,41 +69,7 @@ __global__ __launch_bounds__(kIcpBlock) void k_icp_sums(const IcpSumsArgs<T> a) 
         double t[NS];
 #pragma unroll
         for (int k = 0; k < NS; ++k) t[k] = 0.0;
-        if (i < a.n) {
-            const T d2 = a.d2[i];
-            const long long jj = a.j[i];
-            bool in = d2 < a.r2;                        // strict; false for a non-finite d2
-            if (in && (unsigned long long)jj >= (unsigned long long)a.m) { in = false; atomicOr(a.flags, kIcpBadRow); }
-            if (a.corr) a.corr[i] = in ? jj : -1ll;
-            if (in) {
-                const size_t po = (size_t)i * 3, qo = (size_t)jj * 3;
-                const double p0 = (double)a.p[po], p1 = (double)a.p[po + 1], p2 = (double)a.p[po + 2];
-                const double q0 = (double)a.target[qo], q1 = (double)a.target[qo + 1], q2 = (double)a.target[qo + 2];
-                t[0] = 1.0; t[1] = (double)d2;
-                if (MODE == kIcpPoint) {
-                    const double pp[3] = {p0, p1, p2}, qq[3] = {q0, q1, q2};
-#pragma unroll
-                    for (int u = 0; u < 3; ++u) { t[2 + u] = pp[u]; t[5 + u] = qq[u]; }
-#pragma unroll
-                    for (int u = 0; u < 3; ++u)
-#pragma unroll
-                        for (int v = 0; v < 3; ++v) t[8 + 3 * u + v] = pp[u] * qq[v];
-                } else {
-                    const double n0 = (double)a.normals[qo], n1 = (double)a.normals[qo + 1], n2 = (double)a.normals[qo + 2];
-                    const double e0 = p0 - q0, e1 = p1 - q1, e2 = p2 - q2;
-                    const double r = ((e0 * n0) + (e1 * n1)) + (e2 * n2);
-                    const double J[6] = {p1 * n2 - p2 * n1, p2 * n0 - p0 * n2, p0 * n1 - p1 * n0, n0, n1, n2};
-                    int k = 2;
-#pragma unroll
-                    for (int u = 0; u < 6; ++u)
-#pragma unroll
-                        for (int v = u; v < 6; ++v) t[k++] = J[u] * J[v];
-#pragma unroll
-                    for (int u = 0; u < 6; ++u) t[23 + u] = J[u] * r;
-                    t[29] = r * r;
-                }
-            }
-        }
+        if (i < n) terms(i, t);
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             const double v = icp_fold_wave(t[k]);
@@ -110,12 +78,51 @@ __global__ __launch_bounds__(kIcpBlock) void k_icp_sums(const IcpSumsArgs<T> a) 
     }
     __syncthreads();
     // level 2 -- unless level 1 left one value (n <= 64): fold64 stops there
-    const bool single = a.n <= 64;
+    const bool single = n <= 64;
     for (int k = wave; k < NS; k += kIcpBlock / 64) {
         double v = lv1[k][single ? 0 : lane];
         if (!single) v = icp_fold_wave(v);
-        if (lane == 0) a.part[(size_t)k * a.nblocks + blockIdx.x] = v;
+        if (lane == 0) part[(size_t)k * nblocks + blockIdx.x] = v;
     }
+}
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(kIcpBlock) void k_icp_sums(const IcpSumsArgs<T> a) {
+    icp_sum_block<MODE == kIcpPlane ? kIcpSumsPlane : kIcpSumsPoint>(a.n, a.part, a.nblocks, [&](long long i, double* t) {
+        const T d2 = a.d2[i];
+        const long long jj = a.j[i];
+        bool in = d2 < a.r2;                            // strict; false for a non-finite d2
+        if (in && (unsigned long long)jj >= (unsigned long long)a.m) { in = false; atomicOr(a.flags, kIcpBadRow); }
+        if (a.corr) a.corr[i] = in ? jj : -1ll;
+        if (in) {
+            const size_t po = (size_t)i * 3, qo = (size_t)jj * 3;
+            const double p0 = (double)a.p[po], p1 = (double)a.p[po + 1], p2 = (double)a.p[po + 2];
+            const double q0 = (double)a.target[qo], q1 = (double)a.target[qo + 1], q2 = (double)a.target[qo + 2];
+            t[0] = 1.0; t[1] = (double)d2;
+            if (MODE == kIcpPoint) {
+                const double pp[3] = {p0, p1, p2}, qq[3] = {q0, q1, q2};
+#pragma unroll
+                for (int u = 0; u < 3; ++u) { t[2 + u] = pp[u]; t[5 + u] = qq[u]; }
+#pragma unroll
+                for (int u = 0; u < 3; ++u)
+#pragma unroll
+                    for (int v = 0; v < 3; ++v) t[8 + 3 * u + v] = pp[u] * qq[v];
+            } else {
+                const double n0 = (double)a.normals[qo], n1 = (double)a.normals[qo + 1], n2 = (double)a.normals[qo + 2];
+                const double e0 = p0 - q0, e1 = p1 - q1, e2 = p2 - q2;
+                const double r = ((e0 * n0) + (e1 * n1)) + (e2 * n2);
+                const double J[6] = {p1 * n2 - p2 * n1, p2 * n0 - p0 * n2, p0 * n1 - p1 * n0, n0, n1, n2};
+                int k = 2;
+#pragma unroll
+                for (int u = 0; u < 6; ++u)
+#pragma unroll
+                    for (int v = u; v < 6; ++v) t[k++] = J[u] * J[v];
+#pragma unroll
+                for (int u = 0; u < 6; ++u) t[23 + u] = J[u] * r;
+                t[29] = r * r;
+            }
+        }
+    });
 }
 
 // One block. x holds [sum][count] values (row stride: count); they are folded by 64 into y ([sum][ceil(count / 64)]), the two change roles,

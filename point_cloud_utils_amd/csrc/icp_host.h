@@ -17,24 +17,25 @@ static void icp_quat_to_rot(double w, double x, double y, double z, double R[3][
     R[1][0] = 2.0 * (xy + wz);       R[1][1] = 1.0 - 2.0 * (xx + zz); R[1][2] = 2.0 * (yz - wx);
     R[2][0] = 2.0 * (xz - wy);       R[2][1] = 2.0 * (yz + wx);       R[2][2] = 1.0 - 2.0 * (xx + yy);
 }
-// Cyclic Jacobi on a symmetric 4x4: pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), kIcpJacobiSweeps sweeps, a zero entry skipped.
-static void icp_jacobi4(double A[4][4], double V[4][4]) {
-    static const int pairs[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
-    for (int i = 0; i < 4; ++i) for (int k = 0; k < 4; ++k) V[i][k] = i == k ? 1.0 : 0.0;
+// Cyclic Jacobi on a symmetric NxN (4: Horn's solve here; 3: the plane refit of plane_host.h): the pairs of the upper triangle row by row --
+// (0,1) (0,2) .. (1,2) .. --, kIcpJacobiSweeps sweeps, a zero entry skipped.
+template <int N>
+static void jacobi_sym(double A[N][N], double V[N][N]) {
+    for (int i = 0; i < N; ++i) for (int k = 0; k < N; ++k) V[i][k] = i == k ? 1.0 : 0.0;
     for (int sweep = 0; sweep < kIcpJacobiSweeps; ++sweep)
-        for (const auto& pq : pairs) {
-            const int p = pq[0], q = pq[1];
-            const double apq = A[p][q];
-            if (apq == 0.0) continue;
-            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-            const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-            const double t = theta >= 0.0 ? 1.0 / den : -1.0 / den;
-            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-            for (int k = 0; k < 4; ++k) { const double akp = A[k][p], akq = A[k][q]; A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq; }
-            for (int k = 0; k < 4; ++k) { const double apk = A[p][k], aqk = A[q][k]; A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk; }
-            A[p][q] = A[q][p] = 0.0;
-            for (int k = 0; k < 4; ++k) { const double vkp = V[k][p], vkq = V[k][q]; V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq; }
-        }
+        for (int p = 0; p < N; ++p)
+            for (int q = p + 1; q < N; ++q) {
+                const double apq = A[p][q];
+                if (apq == 0.0) continue;
+                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+                const double den = fabs(theta) + sqrt(theta * theta + 1.0);
+                const double t = theta >= 0.0 ? 1.0 / den : -1.0 / den;
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < N; ++k) { const double akp = A[k][p], akq = A[k][q]; A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq; }
+                for (int k = 0; k < N; ++k) { const double apk = A[p][k], aqk = A[q][k]; A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk; }
+                A[p][q] = A[q][p] = 0.0;
+                for (int k = 0; k < N; ++k) { const double vkp = V[k][p], vkq = V[k][q]; V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq; }
+            }
 }
 // Point-to-point: Horn's closed form from the 17 sums.
 static void icp_horn(const double* S, long long count, IcpStep& D) {
@@ -49,7 +50,7 @@ static void icp_horn(const double* S, long long count, IcpStep& D) {
                       {Szx - Sxz, Sxy + Syx, (Syy - Sxx) - Szz, Syz + Szy},
                       {Sxy - Syx, Szx + Sxz, Syz + Szy, (Szz - Sxx) - Syy}};
     double V[4][4];
-    icp_jacobi4(N, V);
+    jacobi_sym<4>(N, V);
     int best = 0;
     for (int i = 1; i < 4; ++i) if (N[i][i] > N[best][best]) best = i;
     const double w = V[0][best], x = V[1][best], y = V[2][best], z = V[3][best];

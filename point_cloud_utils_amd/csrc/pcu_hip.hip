@@ -52,6 +52,7 @@ namespace pcu {          // the k > 1 search kernels are compiled in search_kern
 #include "fps.h"
 #include "dbscan.h"
 #include "icp.h"
+#include "consensus.h"
 #include "plane.h"
 #include "ransac.h"
 #include "orient.h"
@@ -175,7 +176,7 @@ static int wait_stream(hipStream_t s) {
     }
 }
 #define HIP_WAIT(s) do { const int w_ = wait_stream(s); if (w_) return w_; } while (0)
-// The same for an event recorded on stream s (long launches are enqueued in pieces with at most two in the queue: see kd_search_launch).
+// The same for an event recorded on stream s (long launches are enqueued in pieces with at most two in the queue: see launch_in_pieces).
 static int wait_event(hipEvent_t ev, hipStream_t s) {
     for (unsigned it = 0;; ++it) {
         const hipError_t e = hipEventQuery(ev);
@@ -238,7 +239,7 @@ struct pcu_hip_ctx {
     size_t extra_hint = 0;                    // largest overflow seen: added to the arena request of later calls
     hipEvent_t ev[8] = {};
     hipEvent_t kev[8] = {};                    // brackets of the main (pass-0) search launches of a call
-    hipEvent_t cev[2] = {};                    // progress marks of a launch that is enqueued in pieces (kd_search_launch; created on first use)
+    hipEvent_t cev[2] = {};                    // progress marks of a launch that is enqueued in pieces (launch_in_pieces; created on first use)
     int n_kev = 0;
     double occupancy = 0;                      // <=0: default
     int* h_pinned = nullptr;                   // small pinned readback buffer
@@ -1016,6 +1017,23 @@ static void kd_speculate_end(pcu_hip_ctx* c, bool call_completed) {
     if (sp.active) { sp.active = false; if (call_completed) c->kd_spec_hint = false; }
 }
 
+// The loop of every launch that is enqueued in pieces (kd_search_launch below, the scoring of consensus_host.h): enqueue(i) launches piece i on
+// s; at most two pieces are in the queue, the host waiting (cancellably) for piece i - 1 before it enqueues piece i + 1, so that the GPU never
+// idles between pieces. Several pieces are marked with the context's two events; a single one records and waits on nothing.
+template <typename Enqueue>
+static int launch_in_pieces(pcu_hip_ctx* c, hipStream_t s, int pieces, Enqueue enqueue) {
+    if (pieces > 1) for (auto& e : c->cev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (int i = 0; i < pieces; ++i) {
+        enqueue(i);
+        HIP_TRY(hipGetLastError());
+        if (pieces > 1) {
+            HIP_TRY(hipEventRecord(c->cev[i & 1], s));
+            if (i >= 1) { if (int w = wait_event(c->cev[(i - 1) & 1], s)) return w; }
+        }
+    }
+    return 0;
+}
+
 // The tie-order traversal of n queries (one wave each). A call whose queries are nearly all tied -- a cloud against a line, a lattice -- runs
 // hundreds of milliseconds here, and a kernel cannot be abandoned: beyond kKdSearchPiece queries the launch is enqueued in pieces, at most two
 // in the queue, the host waiting (cancellably) for piece i - 1 before it enqueues piece i + 1. The GPU never idles between pieces; a
@@ -1029,15 +1047,10 @@ static int kd_search_launch(pcu_hip_ctx* c, hipStream_t s, KdSearchArgs<T> a, in
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    for (auto& e : c->cev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (int t0 = 0, i = 0; t0 < n; t0 += kKdSearchPiece, ++i) {
-        a.t0 = t0;
-        hipLaunchKernelGGL(k_kd_search<T>, dim3(std::min(kKdSearchPiece, n - t0)), dim3(64), 0, s, a);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->cev[i & 1], s));
-        if (i >= 1) { if (int w = wait_event(c->cev[(i - 1) & 1], s)) return w; }
-    }
-    return 0;
+    return launch_in_pieces(c, s, (n + kKdSearchPiece - 1) / kKdSearchPiece, [&](int i) {
+        a.t0 = i * kKdSearchPiece;
+        hipLaunchKernelGGL(k_kd_search<T>, dim3(std::min(kKdSearchPiece, n - a.t0)), dim3(64), 0, s, a);
+    });
 }
 
 template <typename T>
@@ -2562,6 +2575,7 @@ static int debug_kd(pcu_hip_ctx* c, const T* pts, int64_t n, int leaf_max, int64
 #include "fps_host.h"
 #include "dbscan_host.h"
 #include "icp_host.h"
+#include "consensus_host.h"
 #include "plane_host.h"
 #include "ransac_host.h"
 #include "orient_host.h"
@@ -3023,7 +3037,7 @@ int pcu_hip_index_icp_##SUF(pcu_hip_ctx* c, const pcu_hip_index* ix, const T* sr
 PCU_ICP_ABI(f32, float)
 PCU_ICP_ABI(f64, double)
 #undef PCU_ICP_ABI
-// segment_point_cloud_plane (plane.h, plane_host.h)
+// segment_point_cloud_plane (plane.h, plane_host.h over consensus.h, consensus_host.h)
 #define PCU_PLANE_ABI(SUF, T)                                                                                                                         \
 int pcu_hip_plane_##SUF(pcu_hip_ctx* c, const T* pts, int64_t n, double distance_threshold, int64_t num_iterations, uint32_t seed, int refit,        \
                         int64_t launch_tests, pcu_hip_plane_result* out, int64_t* out_inliers, unsigned flags, void* stream, pcu_hip_stats* st) {   \
@@ -3033,10 +3047,10 @@ PCU_PLANE_ABI(f64, double)
 #undef PCU_PLANE_ABI
 int pcu_hip_plane_geometry(int64_t out[2]) {
     if (!out) return fail(PCU_HIP_ERR_INVALID, "null output");
-    out[0] = kPlaneRows; out[1] = kPlaneLaunchTests;
+    out[0] = kPlaneRows; out[1] = kConsensusLaunchTests;
     return 0;
 }
-// register_point_clouds_ransac (ransac.h, ransac_host.h)
+// register_point_clouds_ransac (ransac.h, ransac_host.h over consensus.h, consensus_host.h)
 #define PCU_RANSAC_ABI(SUF, T)                                                                                                                        \
 int pcu_hip_ransac_##SUF(pcu_hip_ctx* c, const T* src, int64_t n, const T* tgt, int64_t m, const int64_t* corr, int64_t num_corr, double max_dist,    \
                          int64_t num_iterations, uint32_t seed, double edge_length_ratio, int refit, int64_t launch_tests, pcu_hip_ransac_result* out, \
@@ -3048,7 +3062,7 @@ PCU_RANSAC_ABI(f64, double)
 #undef PCU_RANSAC_ABI
 int pcu_hip_ransac_geometry(int64_t out[2]) {
     if (!out) return fail(PCU_HIP_ERR_INVALID, "null output");
-    out[0] = kRansacRows; out[1] = kPlaneLaunchTests;
+    out[0] = kRansacRows; out[1] = kConsensusLaunchTests;
     return 0;
 }
 // orient_point_cloud_normals (orient.h, orient_host.h)

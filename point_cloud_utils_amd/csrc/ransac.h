@@ -1,18 +1,19 @@
-// csrc/ransac.h -- the kernels of register_point_clouds_ransac (the contract in numpy: tests/ransac_contract.py; host: ransac_host.h).
+// csrc/ransac.h -- the model and the own kernels of register_point_clouds_ransac (the contract in numpy:
+// tests/ransac_contract.py; host: ransac_host.h). The winner, mark and emit kernels are consensus.h's, instantiated for RansacModel; the scoring kernel is its own.
 //
 // RANSAC over H three-correspondence hypotheses: k_ransac_gather (a lane per correspondence: both indices checked, the six coordinates as
 // float64 into six planes of c values), k_ransac_hypotheses (a lane per hypothesis: the draw of plane.h over the c correspondences, the edge
 // pre-check, the two frames, the rigid motion as {R, tr, bound}), k_ransac_score (every correspondence against every hypothesis: the hot
-// path, on the shape of k_plane_score), k_ransac_best (the lowest h of the largest score; the winner stays on the device), k_ransac_sums +
-// icp.h's k_icp_fold (the 17 sums of Horn's solve, or [count, d2] alone, in the fold64 order), k_ransac_mark / the scan of voxel_host.h /
-// plane.h's k_plane_emit for the inliers' rows in ascending order.
+// path), k_consensus_best (the lowest h of the largest score; the winner stays on the device), k_ransac_sums + icp.h's k_icp_fold (the 17
+// sums of Horn's solve, or [count, d2] alone, in the fold64 order), k_consensus_mark / the scan of voxel_host.h / k_consensus_emit for the
+// inliers' rows in ascending order.
 // Everything is float64 with one rounding per operation (the unit is built with -ffp-contract=off). Division and square root appear in
-// k_ransac_hypotheses alone and are the IEEE ones. The score is an integer count: no floating-point atomic anywhere, and no result depends on
-// how a kernel was launched.
+// k_ransac_hypotheses alone and are the IEEE ones.
 #pragma once
 #include "pcu_types.h"
 #include "plane.h"
 #include "icp.h"
+#include "consensus.h"
 
 namespace pcu {
 
@@ -20,12 +21,11 @@ namespace pcu {
 #define PCU_RANSAC_ROWS 4                           // (2 and 8 measured: DESIGN.md 8.17)
 #endif
 constexpr int kRansacRows = PCU_RANSAC_ROWS;        // R: correspondences a lane of k_ransac_score keeps in registers (six doubles each)
-constexpr int kRansacScoreBlock = 256;              // threads of a k_ransac_score block: 4 waves, 4 * 64 * R correspondences
 constexpr int kRansacBadSource = 1, kRansacBadTarget = 2;      // flag word: column 0 / column 1 of correspondences names a row that is not there
 
 struct RansacHyp { double R[9], tr[3], bound; };    // correspondence i is an inlier iff |R s + tr - t|^2 < bound
 static_assert(sizeof(RansacHyp) == 104, "RansacHyp layout");
-// What k_ransac_best leaves on the device (and the host reads with its first wait).
+// What k_consensus_best leaves on the device (and the host reads with its first wait).
 struct RansacBest { RansacHyp hyp; unsigned score, h; };
 static_assert(sizeof(RansacBest) == 112, "RansacBest layout");
 
@@ -110,15 +110,30 @@ __global__ __launch_bounds__(256) void k_ransac_hypotheses(const double* __restr
     out[h] = q;
 }
 
-// The hot path, on the shape of k_plane_score. A wave owns 64 * R consecutive correspondences, lane l the rows base + r * 64 + l: read once
-// from the six planes, kept in registers over the launch's hypotheses [hbeg, hend) -- of which blockIdx.y takes one slice of `slice` (a
-// multiple of 64). A row past c is NaN: never an inlier. The record of a hypothesis is read at a wave-uniform address (scalar loads). The
-// wave's count for a hypothesis is the popcount of a ballot; the counts of 64 consecutive hypotheses are gathered into the 64 lanes and leave
-// as one vector atomicAdd on unsigned counters.
-__global__ __launch_bounds__(kRansacScoreBlock) void k_ransac_score(const double* __restrict__ pk, unsigned c, const RansacHyp* __restrict__ hyp, unsigned hbeg, unsigned hend,
+// The motion as a model of consensus.h: a row is a correspondence, read from the six planes.
+struct RansacModel {
+    using Elem = double; using Hyp = RansacHyp; using Best = RansacBest;
+    static constexpr int kRows = kRansacRows;
+    struct Row { double sx, sy, sz, tx, ty, tz; };
+    struct Draw {};
+    static __device__ __forceinline__ Row load(const double* __restrict__ pk, unsigned c, unsigned long long i) {
+        const bool live = i < c;
+        const size_t o = live ? (size_t)i : 0;
+        return {live ? pk[o] : __builtin_nan(""), pk[(size_t)c + o], pk[2 * (size_t)c + o], pk[3 * (size_t)c + o], pk[4 * (size_t)c + o], pk[5 * (size_t)c + o]};
+    }
+    static __device__ __forceinline__ bool inlier(const RansacHyp& q, const Row& p) { return ransac_inlier(q, p.sx, p.sy, p.sz, p.tx, p.ty, p.tz); }
+    static __device__ __forceinline__ void won(const Draw&, unsigned, RansacBest&) {}
+};
+
+// The hot path: consensus.h's k_consensus_score with the motion's rows and test written out. It is kept as a kernel of its own because
+// k_consensus_score<RansacModel> measured 0.6 to 1.6 % slower on every figure of profiles/ransac_record.py when the two ran alternately
+// (profiles/consensus_frame_refactor.txt, part 5): the same opcodes, but the compiler orders the operands of twelve additions of the hypothesis
+// loop differently and places the loop 12 bytes earlier -- which does not explain it: the cause is not found (look at the loop's alignment
+// first). A change to the loop of k_consensus_score is to be made here too.
+__global__ __launch_bounds__(kConsensusScoreBlock) void k_ransac_score(const double* __restrict__ pk, unsigned c, const RansacHyp* __restrict__ hyp, unsigned hbeg, unsigned hend,
                                                                     unsigned slice, unsigned* __restrict__ scores) {
     const unsigned lane = threadIdx.x & 63u;
-    const unsigned long long wave = (unsigned long long)blockIdx.x * (kRansacScoreBlock / 64) + (threadIdx.x >> 6);
+    const unsigned long long wave = (unsigned long long)blockIdx.x * (kConsensusScoreBlock / 64) + (threadIdx.x >> 6);
     const unsigned long long base = wave * (64ull * kRansacRows);
     if (base >= c) return;                          // (wave-uniform)
     double sx[kRansacRows], sy[kRansacRows], sz[kRansacRows], tx[kRansacRows], ty[kRansacRows], tz[kRansacRows];
@@ -148,80 +163,29 @@ __global__ __launch_bounds__(kRansacScoreBlock) void k_ransac_score(const double
     }
 }
 
-// One block: the largest score, the lowest h among equal ones; the winner's record, for the kernels that follow.
-__global__ __launch_bounds__(1024) void k_ransac_best(const unsigned* __restrict__ scores, const RansacHyp* __restrict__ hyp, unsigned H, RansacBest* __restrict__ out) {
-    __shared__ unsigned long long top[16];
-    unsigned long long key = 0;                     // (score, ~h): the maximum is the largest score at the lowest h
-    for (unsigned h = threadIdx.x; h < H; h += 1024u) {
-        const unsigned long long k = ((unsigned long long)scores[h] << 32) | (0xffffffffu - h);
-        key = k > key ? k : key;
-    }
-#pragma unroll
-    for (int w = 32; w >= 1; w >>= 1) { const unsigned long long o = __shfl_xor(key, w, 64); key = o > key ? o : key; }
-    if ((threadIdx.x & 63) == 0) top[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w) key = top[w] > key ? top[w] : key;
-        const unsigned h = 0xffffffffu - (unsigned)(key & 0xffffffffull);
-        RansacBest bst;
-        bst.hyp = hyp[h]; bst.score = (unsigned)(key >> 32); bst.h = h;
-        *out = bst;
-    }
-}
-
-// The sums of the inliers of a motion -- the winner on the device (best), or the host's (given) --, in the fold64 order: the block shape and
-// the two levels of k_icp_sums (icp.h); the further levels are k_icp_fold's. NS = 17: [count, d2, p(3), q(3), p_u*q_v (9)] with p the source
-// point as it is and q its partner (the point mode of icp.h); NS = 2: [count, d2]. A non-inlier contributes +0.0. part: [sum][block].
+// The sums of the inliers of a motion -- the winner on the device (best), or the host's (given) --, in the fold64 order: icp.h's sum block over
+// the terms of a correspondence; the further levels are k_icp_fold's. NS = 17: [count, d2, p(3), q(3), p_u*q_v (9)] with p the source point as
+// it is and q its partner (the point mode of icp.h); NS = 2: [count, d2]. A non-inlier contributes +0.0. part: [sum][block].
 template <int NS>
 __global__ __launch_bounds__(kIcpBlock) void k_ransac_sums(const double* __restrict__ pk, int c, const RansacBest* __restrict__ best, const RansacHyp given,
                                                            double* __restrict__ part, int nblocks) {
-    __shared__ double lv1[NS][kIcpGroups];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const RansacHyp q = best ? best->hyp : given;
-    for (int g = 0; g < kIcpGroups / 16; ++g) {
-        const int grp = g * 16 + wave;
-        const long long i = (long long)blockIdx.x * kIcpRows + grp * 64 + lane;
-        double t[NS];
+    icp_sum_block<NS>(c, part, nblocks, [&](long long i, double* t) {
+        const size_t o = (size_t)i, C = (size_t)c;
+        const double pp[3] = {pk[o], pk[C + o], pk[2 * C + o]}, qq[3] = {pk[3 * C + o], pk[4 * C + o], pk[5 * C + o]};
+        const double d2 = ransac_d2(q, pp[0], pp[1], pp[2], qq[0], qq[1], qq[2]);
+        if (d2 < q.bound) {
+            t[0] = 1.0; t[1] = d2;
+            if constexpr (NS == kIcpSumsPoint) {
 #pragma unroll
-        for (int k = 0; k < NS; ++k) t[k] = 0.0;
-        if (i < c) {
-            const size_t o = (size_t)i, C = (size_t)c;
-            const double pp[3] = {pk[o], pk[C + o], pk[2 * C + o]}, qq[3] = {pk[3 * C + o], pk[4 * C + o], pk[5 * C + o]};
-            const double d2 = ransac_d2(q, pp[0], pp[1], pp[2], qq[0], qq[1], qq[2]);
-            if (d2 < q.bound) {
-                t[0] = 1.0; t[1] = d2;
-                if constexpr (NS == kIcpSumsPoint) {
+                for (int u = 0; u < 3; ++u) { t[2 + u] = pp[u]; t[5 + u] = qq[u]; }
 #pragma unroll
-                    for (int u = 0; u < 3; ++u) { t[2 + u] = pp[u]; t[5 + u] = qq[u]; }
+                for (int u = 0; u < 3; ++u)
 #pragma unroll
-                    for (int u = 0; u < 3; ++u)
-#pragma unroll
-                        for (int v = 0; v < 3; ++v) t[8 + 3 * u + v] = pp[u] * qq[v];
-                }
+                    for (int v = 0; v < 3; ++v) t[8 + 3 * u + v] = pp[u] * qq[v];
             }
         }
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const double v = icp_fold_wave(t[k]);
-            if (lane == 0) lv1[k][grp] = v;
-        }
-    }
-    __syncthreads();
-    const bool single = c <= 64;                    // level 1 left one value: fold64 stops there
-    for (int k = wave; k < NS; k += kIcpBlock / 64) {
-        double v = lv1[k][single ? 0 : lane];
-        if (!single) v = icp_fold_wave(v);
-        if (lane == 0) part[(size_t)k * nblocks + blockIdx.x] = v;
-    }
-}
-
-// flag[i] = 1 for an inlier of the final motion: the winner on the device (refit off), or the host's.
-__global__ __launch_bounds__(256) void k_ransac_mark(const double* __restrict__ pk, int c, const RansacBest* __restrict__ best, const RansacHyp given, unsigned* __restrict__ flag) {
-    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
-    if (i >= c) return;
-    const RansacHyp q = best ? best->hyp : given;
-    const size_t o = (size_t)i, C = (size_t)c;
-    flag[i] = ransac_inlier(q, pk[o], pk[C + o], pk[2 * C + o], pk[3 * C + o], pk[4 * C + o], pk[5 * C + o]) ? 1u : 0u;
+    });
 }
 
 }  // namespace pcu

@@ -1,34 +1,12 @@
-// csrc/ransac_host.h -- host side of register_point_clouds_ransac (kernels: ransac.h; the contract in numpy: tests/ransac_contract.py). Included
-// by pcu_hip.hip after the operator frame, voxel_host.h (own_inclusive_scan, scan_bytes), icp_host.h (icp_horn) and plane_host.h (plane_mods).
+// csrc/ransac_host.h -- host side of register_point_clouds_ransac (kernels: ransac.h, consensus.h; the contract in numpy:
+// tests/ransac_contract.py). Included by pcu_hip.hip after the operator frame, voxel_host.h (scan_bytes), icp_host.h (icp_horn),
+// consensus_host.h (the scoring launcher, the result tail, the shared refusals) and plane_host.h (plane_mods).
 //
 // The one solve of the call -- Horn's closed form on the winner's inliers -- is icp_horn as it stands: float64 on the host, written as
 // icp_contract.py writes it.
 #pragma once
 
 enum { kRansacOk = 0, kRansacNoAlignment = 1 };     // pcu_hip_ransac_result::status
-
-// The hypotheses [0, H) against every correspondence, in launches of about launch_tests tests: at most two in the queue, the host waiting
-// (cancellably) for launch i - 1 before it enqueues launch i + 1, as plane_score_launch does.
-static int ransac_score_launch(pcu_hip_ctx* c, hipStream_t s, const double* pk, int64_t nc, const RansacHyp* hyp, unsigned H, int64_t launch_tests, unsigned* scores,
-                               int* n_launches) {
-    const unsigned per = (unsigned)std::min<int64_t>(std::max<int64_t>(launch_tests / nc / 64, 1) * 64, 1 << 20);     // hypotheses of a launch: a multiple of 64
-    const unsigned waves = (unsigned)((nc + 64 * kRansacRows - 1) / (64 * kRansacRows)), bx = (waves + kRansacScoreBlock / 64 - 1) / (kRansacScoreBlock / 64);
-    const bool pieces = H > per;
-    if (pieces) for (auto& e : c->cev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    int i = 0;
-    for (unsigned h0 = 0; h0 < H; h0 += per, ++i) {
-        const unsigned h1 = std::min(H, h0 + per), groups = (h1 - h0 + 63) / 64;
-        const unsigned by = std::min(groups, std::max(1u, (unsigned)kPlaneScoreWaves / waves)), slice = (groups + by - 1) / by * 64;
-        hipLaunchKernelGGL(k_ransac_score, dim3(bx, (groups * 64 + slice - 1) / slice), dim3(kRansacScoreBlock), 0, s, pk, (unsigned)nc, hyp, h0, h1, slice, scores);
-        HIP_TRY(hipGetLastError());
-        if (pieces) {
-            HIP_TRY(hipEventRecord(c->cev[i & 1], s));
-            if (i >= 1) { if (int w = wait_event(c->cev[(i - 1) & 1], s)) return w; }
-        }
-    }
-    *n_launches = i;
-    return 0;
-}
 
 template <typename T>
 static size_t ransac_bytes(int64_t n, int64_t m, int64_t nc, int64_t H, bool on_dev) {
@@ -45,10 +23,8 @@ static void ransac_transform(const RansacHyp& q, double* M) {
 }
 
 // corr: nc rows [source row, target row]. out: host memory. out_inliers: room for nc int64 rows (the first out->num_inliers are the result,
-// ascending). launch_tests: 0 (the default, kPlaneLaunchTests) or the tests of a scoring launch (tests). One wait without refit, two with it;
-// the flag word of k_ransac_gather arrives with the first.
-// stats: n_queries = nc, n_passes = scoring launches, n_escalated = the winner's score, ms_index (gather and hypotheses), ms_search (scoring),
-// ms_total.
+// ascending). launch_tests: 0 (the default, kConsensusLaunchTests) or the tests of a scoring launch (tests). One wait without refit, two with
+// it; the flag word of k_ransac_gather arrives with the first. stats: consensus_report's (ms_index: gather and hypotheses).
 template <typename T>
 static int ransac_impl(pcu_hip_ctx* c, const T* source, int64_t n, const T* target, int64_t m, const int64_t* corr, int64_t nc, double thr, int64_t H, unsigned seed,
                        double ratio, int refit, int64_t launch_tests, pcu_hip_ransac_result* out, int64_t* out_inliers, unsigned flags, void* stream, pcu_hip_stats* st) {
@@ -57,10 +33,9 @@ static int ransac_impl(pcu_hip_ctx* c, const T* source, int64_t n, const T* targ
     if (n > kMeshMaxRows || m > kMeshMaxRows) return fail(PCU_HIP_ERR_INVALID, "meshes and point clouds with more than 2^27-16 rows are not supported");
     if (nc < 3) return fail(PCU_HIP_ERR_INVALID, "Invalid number of correspondences (%lld): a rigid transform needs at least 3.", (long long)nc);
     if (nc > kMeshMaxRows) return fail(PCU_HIP_ERR_INVALID, "correspondences with more than 2^27-16 rows are not supported");
-    if (!(thr >= 0.0) || std::isinf(thr)) return fail(PCU_HIP_ERR_INVALID, "Invalid max_correspondence_distance (%g): must be finite and not negative.", thr);
-    if (H < 1 || H > (1 << 20)) return fail(PCU_HIP_ERR_INVALID, "Invalid num_iterations (%lld): must be an integer in [1, 2**20].", (long long)H);
+    if (int rc = consensus_check("max_correspondence_distance", thr, H)) return rc;
     if (!(ratio >= 0.0 && ratio <= 1.0)) return fail(PCU_HIP_ERR_INVALID, "Invalid edge_length_ratio (%g): must be in [0, 1].", ratio);
-    if (launch_tests < 0) return fail(PCU_HIP_ERR_INVALID, "Invalid launch_tests (%lld): must not be negative.", (long long)launch_tests);
+    if (int rc = consensus_check_launch_tests(launch_tests)) return rc;
     if (!source || !target || !corr || !out || !out_inliers) return fail(PCU_HIP_ERR_INVALID, "null source / target / correspondences / result / out_inliers");
     memset(out, 0, sizeof *out);
     const bool dev_ptrs = (flags & PCU_HIP_PTRS_ON_DEVICE) != 0;
@@ -86,9 +61,10 @@ static int ransac_impl(pcu_hip_ctx* c, const T* source, int64_t n, const T* targ
         hipLaunchKernelGGL(k_ransac_hypotheses, dim3((uH + 255) / 256), dim3(256), 0, s, (const double*)d_pk, (unsigned)nc, md, seed, uH, r2, t2, d_hyp);
         HIP_TRY(hipGetLastError());
         tm.mark(1);
+        using M = RansacModel;
         int launches = 0;
-        if (int rc = ransac_score_launch(c, s, d_pk, nc, d_hyp, uH, launch_tests ? launch_tests : kPlaneLaunchTests, d_scores, &launches)) return rc;
-        hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(1024), 0, s, (const unsigned*)d_scores, (const RansacHyp*)d_hyp, uH, d_best);
+        if (int rc = consensus_score_launch<M>(k_ransac_score, c, s, d_pk, nc, d_hyp, uH, launch_tests, d_scores, &launches)) return rc;
+        hipLaunchKernelGGL(k_consensus_best<M>, dim3(1), dim3(1024), 0, s, (const unsigned*)d_scores, (const RansacHyp*)d_hyp, uH, M::Draw{}, d_best);
         HIP_TRY(hipGetLastError());
         tm.mark(2);
         auto bad_rows = [&](int f) -> int {
@@ -114,37 +90,21 @@ static int ransac_impl(pcu_hip_ctx* c, const T* source, int64_t n, const T* targ
             }
         }
         unsigned count = 0;
-        if (!refit || best.score) {
-            const RansacBest* const from = refit ? (const RansacBest*)nullptr : (const RansacBest*)d_best;
-            hipLaunchKernelGGL(k_ransac_mark, dim3(blocks_for(C)), dim3(kBlock), 0, s, (const double*)d_pk, (int)nc, from, final_q, flag);
-            if (own_inclusive_scan<unsigned>(ar, s, flag, rank, C)) return -1;
-            hipLaunchKernelGGL(k_plane_emit, dim3(blocks_for(C)), dim3(kBlock), 0, s, (const unsigned*)flag, (const unsigned*)rank, (int)nc, d_inl);
-            hipLaunchKernelGGL(k_ransac_sums<2>, dim3((unsigned)nblocks), dim3(kIcpBlock), 0, s, (const double*)d_pk, (int)nc, from, final_q, d_part, nblocks);
-            hipLaunchKernelGGL(k_icp_fold, dim3(1), dim3(kIcpBlock), 0, s, d_part, d_part2, nblocks, 2, (const int*)d_flags, d_rec);
-            HIP_TRY(hipGetLastError());
-            tm.mark(3);
-            HIP_TRY(hipMemcpyAsync(&count, rank + (C - 1), 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(&rec, d_rec, sizeof rec, hipMemcpyDeviceToHost, s));
-            if (!refit) HIP_TRY(hipMemcpyAsync(&best, d_best, sizeof best, hipMemcpyDeviceToHost, s));
-            // (host memory: all nc rows travel with this wait -- the count is not known before it; the caller keeps the first num_inliers)
-            if (out_give(s, on_dev, h_inl, d_inl, C)) return -1;
-            HIP_WAIT(s);                                                // the results
-            if (rec.flags) return bad_rows(rec.flags);
-            if (!refit) final_q = best.hyp;
-        } else tm.mark(3);
+        if (int rc = consensus_inliers<M>(fr, {d_pk, nc, d_best, flag, rank, d_inl, h_inl, d_rec, &rec}, refit != 0, best, final_q, &count, [&](const RansacBest* from) {
+                hipLaunchKernelGGL(k_ransac_sums<2>, dim3((unsigned)nblocks), dim3(kIcpBlock), 0, fr.s, (const double*)d_pk, (int)nc, from, final_q, d_part, nblocks);
+                hipLaunchKernelGGL(k_icp_fold, dim3(1), dim3(kIcpBlock), 0, fr.s, d_part, d_part2, nblocks, 2, (const int*)d_flags, d_rec);
+            })) return rc;
+        if (rec.flags) return bad_rows(rec.flags);
+        if (!refit) final_q = best.hyp;
         static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-        if (best.score == 0) { out->status = kRansacNoAlignment; count = 0; memcpy(out->transform, eye, sizeof eye); }
+        if (best.score == 0) { out->status = kRansacNoAlignment; memcpy(out->transform, eye, sizeof eye); }
         else {
             ransac_transform(final_q, out->transform);
-            out->status = kRansacOk; out->best_iteration = (int64_t)best.h;
+            out->status = kRansacOk;
             out->fitness = (double)count / (double)nc;
             out->inlier_rmse = count ? sqrt(rec.sums[1] / (double)count) : 0.0;
         }
-        out->num_inliers = (int64_t)count; out->score = (int64_t)best.score;
-        if (st) {
-            st->n_queries = nc; st->n_passes = launches; st->n_escalated = (int64_t)best.score;
-            st->ms_index = tm.span(0, 1); st->ms_search = tm.span(1, 2); st->ms_total = tm.span(0, 3);
-        }
+        consensus_report(fr, nc, launches, best.score, best.h, count, out, st);
         return 0;
     });
 }

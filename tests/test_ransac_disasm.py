@@ -1,15 +1,16 @@
-"""The no-FMA and no-scratch rules for the kernels of csrc/ransac.h, checked on the shipped binary with the method of tests/test_fpfh_disasm.py
-and tests/test_plane_disasm.py: the pre-check, the motion of a hypothesis, the test of a correspondence, the terms and every level of the sum
+"""The no-FMA and no-scratch rules for the kernels of csrc/ransac.h and their instantiations of csrc/consensus.h (the kernels over RansacModel),
+checked on the shipped binary with the method of tests/test_fpfh_disasm.py and tests/test_plane_disasm.py: the pre-check, the motion of a hypothesis, the test of a correspondence, the terms and every level of the sum
 tree are separate multiplies and adds (a fused one would round differently from tests/ransac_contract.py). The contract's float64 divisions and
 square roots are IEEE ones, which the compiler expands into a reciprocal (or reciprocal square root) estimate and fused fix-up steps: those are
-accounted for by count, and k_ransac_hypotheses alone has any. No k_ransac kernel uses scratch or spills a register. No GPU."""
+accounted for by count, and k_ransac_hypotheses alone has any. None of these kernels uses scratch or spills a register. No GPU."""
 import re
 import subprocess
 
 import test_disasm as td
 from test_fpfh_disasm import PER_DIV_F64
 
-EXPECTED = (("k_ransac_gather", 2), ("k_ransac_hypotheses", 1), ("k_ransac_score", 1), ("k_ransac_best", 1), ("k_ransac_sums", 2), ("k_ransac_mark", 1))
+EXPECTED = (("k_ransac_gather", 2), ("k_ransac_hypotheses", 1), ("k_ransac_score", 1), ("k_consensus_best", 1), ("k_ransac_sums", 2), ("k_consensus_mark", 1))
+MINE = re.compile(r"k_ransac|RansacModel")                     # (on mangled names)
 TOTAL = 8
 
 
@@ -17,7 +18,7 @@ def _kernels(tmp_path):
     counts, divs, notes = {}, {}, ""
     for co in td._code_object(tmp_path):
         syms = subprocess.run([f"{td.LLVM}/llvm-readelf", "-s", "--wide", co], capture_output=True, text=True, check=True).stdout
-        names = sorted({ln.split()[-1] for ln in syms.splitlines() if " FUNC " in ln and "k_ransac" in ln})
+        names = sorted({ln.split()[-1] for ln in syms.splitlines() if " FUNC " in ln and MINE.search(ln)})
         td._count_fma(co, names, counts)
         for name in names:
             out = subprocess.run([f"{td.LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--disassemble-symbols=" + name, co],
@@ -48,7 +49,7 @@ def test_ransac_kernels_use_no_scratch(tmp_path):
     seen = 0
     for blk in notes.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        if "k_ransac" not in name:
+        if not MINE.search(name):
             continue
         seen += 1
         assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, name
